@@ -8,7 +8,9 @@ forward, L1 + multi-resolution STFT loss, backward (gradient all-reduce over RCC
 N > 1), clip_grad_norm_(10), fused Adam, LR schedule -- on synthetic 10 s @ 16 kHz clips, 16 per GPU
 (BASELINE configs[2]/[3]), random-init E8 weights.  Rank 0 prints ONE JSON line.
 
-value = global_batch * 160000 * K / (max-over-ranks time of K steps).
+value = global_batch * 160000 * K / (max-over-ranks time of K steps); ms_per_step = that time / K.
+--dump-outputs DIR: after the timed steps rank 0 writes what the last one computed as DIR/<name>.npy (step_outputs);
+the inputs and the initial weights are seeded, so two builds run with the same arguments compare output for output.
 roofline: the kernel VERDICT names (rocprofv3 --stats: gemm_tn9_kernel + gemm_tn_kernel, the conv-stack weight
 gradients), timed live with HIP events over the 16 encoder launch shapes of the step; each shape is priced against the
 roof that binds it, the headline is the MFMA-bound group (enc3-enc7) against the dense 16-bit MFMA peak.  `kernels` lists the other heavy kernels the same way
@@ -60,7 +62,12 @@ def parse():
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-roofline", action="store_true")
     ap.add_argument("--cpu-clip", type=int, default=CLIP, help="samples in the CPU-baseline clip")
-    return ap.parse_args()
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="rank 0 writes what the last timed step computed to DIR/<name>.npy (see step_outputs)")
+    args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 MFMA_PEAK_TFS = 2500.0      # MI355X_MICROARCH.md: bf16 / f16 dense
@@ -84,6 +91,37 @@ SCAN_BWD_ISSUE_ROOF = 3.34e12
 B16 = 16
 ENC_T = [160254, 80126, 40062, 20030, 10014, 5006, 2502, 1250, 624]
 ENC_C = [1, 64, 128, 256, 512, 768, 768, 768, 768]
+
+
+DUMP_SAMPLE = 1 << 20      # parameter / gradient elements --dump-outputs keeps (of 41.4M): 4 MB each in f32
+DUMP_SEED = 20240601
+
+
+def step_outputs(net, loss, grad_norm):
+    """What the last timed step gave its caller: the loss and the gradient norm it returned, and the parameters and
+    gradients it left in place.  Those two as one fixed, seeded sample of the parameters concatenated in
+    named_parameters() order (the state_dict order, not the flat buffer's layout), so that the dumps of two builds
+    compare element for element; `sample_index` holds the positions taken.  -> {name: float32 / float64 ndarray}."""
+    import numpy as np
+    params = [p for _, p in net.named_parameters()]
+    with torch.no_grad():
+        w = torch.cat([p.detach().reshape(-1) for p in params]).float()
+        gr = torch.cat([(p.grad if p.grad is not None else torch.zeros_like(p)).detach().reshape(-1)
+                        for p in params]).float()
+    idx = torch.randperm(w.numel(), generator=torch.Generator().manual_seed(DUMP_SEED))[:DUMP_SAMPLE].sort().values
+    idx_dev = idx.to(w.device)
+    return {"loss": np.asarray([float(loss)], dtype=np.float64),
+            "grad_norm": np.asarray([float(grad_norm)], dtype=np.float64),
+            "params_sample": w[idx_dev].cpu().numpy().astype(np.float32),
+            "grads_sample": gr[idx_dev].cpu().numpy().astype(np.float32),
+            "sample_index": idx.numpy().astype(np.float64)}
+
+
+def dump_outputs(outdir, arrays):
+    import numpy as np
+    os.makedirs(outdir, exist_ok=True)
+    for name, a in arrays.items():
+        np.save(os.path.join(outdir, name + ".npy"), a)
 
 
 def _time(fn, iters=10, warm=3):
@@ -726,7 +764,7 @@ def main():
         host0 = step.host_seconds
         t0 = time.perf_counter()
         for _ in range(args.steps):
-            loss, _ = step(clean, noisy)
+            loss, grad_norm = step(clean, noisy)
         host_ms = 1e3 * (step.host_seconds - host0) / max(args.steps, 1)  # enqueue time only: nothing inside synchronises
         barrier()
         elapsed = time.perf_counter() - t0
@@ -747,8 +785,9 @@ def main():
             sv = step.optimizer.state_vec.cpu()
             info.update(loss_scale=float(sv[3]) if ac == torch.float16 else None, settle_steps=settle,
                         skipped_steps_in_timed_region=float(sv[9]) - skipped_before, adam_steps_total=float(sv[5]))
+        outputs = step_outputs(net, loss, grad_norm) if args.dump_outputs and rank == 0 else None
         return {"ms": 1e3 * elapsed / args.steps, "elapsed": elapsed, "host": host_ms_ranks, "loss": float(loss),
-                "graph": step.graph_status, "optim": info, "net": net, "buckets": bucket_times}
+                "graph": step.graph_status, "optim": info, "net": net, "buckets": bucket_times, "outputs": outputs}
 
     exchanging = world > 1 or alone
     modes = {}
@@ -785,6 +824,8 @@ def main():
         dist.all_reduce(one)                              # the rank count the collective itself observes
         rccl_ranks = int(one.item())
 
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, best["outputs"])
     if rank == 0:
         gb = B * world
         out = {"metric": "audio samples/sec/node (train step, E8, 10s@16kHz)",

@@ -166,11 +166,14 @@ def test_bench_launcher_starts_ranks_and_fails_fast_without_a_gpu():
     assert time.time() - t0 < 100
 
 
-def test_bench_pins_ranks_to_the_numa_node_of_their_gpu(tmp_path):
+def test_bench_pins_ranks_to_the_numa_node_of_their_gpu(tmp_path, monkeypatch):
     """bench.py --gpus N: every rank's CPU set comes from the NUMA node of its GPU (AMD display-class PCI devices in bus
     order), shared with the other ranks of that node; an even split when sysfs does not tell."""
     import importlib.util
     import os
+    # visible=None reads the device masks from the environment: the unmasked case must not see the run's own masks
+    for var in ("HIP_VISIBLE_DEVICES", "CUDA_VISIBLE_DEVICES", "ROCR_VISIBLE_DEVICES"):
+        monkeypatch.delenv(var, raising=False)
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
     bench = importlib.util.module_from_spec(spec)
