@@ -46,6 +46,14 @@ class ConvShape(ctypes.Structure):
                 ("silu", c_i32), ("io_dtype", c_i32)]
 
 
+class SsdShape(ctypes.Structure):
+    """cum_ssd_shape (include/cleanumamba_hip.h): the Mamba2 chunked scan's sizes and row strides (elements)."""
+    _fields_ = [("batch", c_i32), ("len", c_i32), ("nheads", c_i32), ("headdim", c_i32), ("dstate", c_i32),
+                ("x_sb", c_i64), ("x_sl", c_i64), ("dt_sb", c_i64), ("dt_sl", c_i64),
+                ("B_sb", c_i64), ("B_sl", c_i64), ("C_sb", c_i64), ("C_sl", c_i64),
+                ("y_sb", c_i64), ("y_sl", c_i64), ("io_dtype", c_i32)]
+
+
 class GemmDesc(ctypes.Structure):
     _fields_ = [("dtype", c_i32), ("epilogue", c_i32), ("M", c_i32), ("N", c_i32), ("K", c_i32),
                 ("lda", c_i64), ("ldw", c_i64), ("ldc", c_i64), ("ldr", c_i64), ("ldz", c_i64),
@@ -142,6 +150,16 @@ SIGNATURES = {
     "cum_optim_sumsq": (c_i32, [_P, c_i64, _P, _P]),
     "cum_optim_prepare": (c_i32, [_P, _P, c_i32, ctypes.c_float, ctypes.c_double, ctypes.c_double, c_i32, ctypes.c_float,
                                   ctypes.c_float, c_i32, _P]),
+    "cum_ssd_chunk": (c_i32, []),
+    "cum_ssd_states_elems": (c_i64, [c_i32] * 5),
+    "cum_ssd_bwd_workspace_elems": (c_i64, [c_i32] * 5),
+    "cum_ssd_fwd": (c_i32, [ctypes.POINTER(SsdShape)] + [_P] * 11),
+    "cum_ssd_bwd": (c_i32, [ctypes.POINTER(SsdShape)] + [_P] * 12 + [c_i64, c_i64, _P, c_i64, c_i64] + [_P] * 5),
+    "cum_gated_rmsnorm_fwd": (c_i32, [c_i32, c_i64, c_i32, _P, c_i64, _P, c_i64, _P, ctypes.c_float, _P, c_i64, _P, _P]),
+    "cum_gated_rmsnorm_bwd_workspace_elems": (c_i64, [c_i32]),
+    "cum_gated_rmsnorm_bwd": (c_i32, [c_i32, c_i64, c_i32, _P, c_i64, _P, c_i64, _P, _P, _P, c_i64, _P, c_i64, _P, c_i64,
+                                      _P, _P, _P]),
+    "cum_ssd_step": (c_i32, [c_i32] * 5 + [ctypes.c_float, _P, c_i64] + [_P] * 9 + [c_i64, _P]),
     "cum_optim_adam": (c_i32, [_P, _P, _P, _P, c_i64, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float,
                                _P]),
 }

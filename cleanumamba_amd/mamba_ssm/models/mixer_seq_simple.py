@@ -7,6 +7,7 @@ import torch
 import torch.nn as nn
 
 from ..modules.mamba_simple import Block, Mamba
+from ..modules.mamba2 import Mamba2
 
 
 def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, rms_norm=False, residual_in_fp32=False,
@@ -14,10 +15,12 @@ def create_block(d_model, ssm_cfg=None, norm_epsilon=1e-5, rms_norm=False, resid
     if rms_norm:
         raise NotImplementedError("rms_norm=True needs the Triton RMSNorm; the reference runs with LayerNorm "
                                   "(src/network/CleanUMamba.py:45)")
-    if ssm_cfg is None:
-        ssm_cfg = {}
+    ssm_cfg = {} if ssm_cfg is None else dict(ssm_cfg)    # (one dict serves every layer: pop from a copy)
+    layer = ssm_cfg.pop("layer", "Mamba1")
+    if layer not in ("Mamba1", "Mamba2"):
+        raise NotImplementedError(f"ssm_cfg layer={layer!r}")
     factory_kwargs = {"device": device, "dtype": dtype}
-    mixer_cls = partial(Mamba, layer_idx=layer_idx, **ssm_cfg, **factory_kwargs)
+    mixer_cls = partial(Mamba2 if layer == "Mamba2" else Mamba, layer_idx=layer_idx, **ssm_cfg, **factory_kwargs)
     norm_cls = partial(nn.LayerNorm, eps=norm_epsilon, **factory_kwargs)
     block = Block(d_model, mixer_cls, norm_cls=norm_cls, fused_add_norm=fused_add_norm,
                   residual_in_fp32=residual_in_fp32)

@@ -14,8 +14,9 @@ Differences from the reference, on purpose:
     ``forward`` output with normalize_input=False).  The reference's own feed()
     raises on every shipped model (skip order at :474) and its flush() drops the
     decoder overlap of the tail (:364); see SURVEY.md fact 9.
-  * ablation variants (LSTM, Mamba2, MambaS4, residual_projection, rms_norm,
-    fused_add_norm) are out of scope and raise NotImplementedError.
+  * ablation variants (LSTM, MambaS4, residual_projection, rms_norm, fused_add_norm)
+    are out of scope and raise NotImplementedError.  ``mamba_v2=True`` (the Mamba2
+    bottleneck) is supported: mamba_ssm/modules/mamba2.py, csrc/ssd.hip.
 """
 import os
 import warnings
@@ -48,8 +49,7 @@ class CleanUMamba(nn.Module):
                  dtype=None):
         super().__init__()
         assert glu_activation in ["Sigmoid", "ReLU", "SiLU", "GELU"], f"glu_activation={glu_activation} not supported"
-        for flag, name in ((mamba_s4, "mamba_s4"), (LSTM, "LSTM"), (mamba_v2, "mamba_v2"),
-                           (residual_projection, "residual_projection"), (rms_norm, "rms_norm"),
+        for flag, name in ((mamba_s4, "mamba_s4"), (LSTM, "LSTM"), (residual_projection, "residual_projection"), (rms_norm, "rms_norm"),
                            (fused_add_norm, "fused_add_norm")):
             if flag:
                 raise NotImplementedError(f"{name}=True is an ablation variant outside the MI355X hot path")
@@ -93,8 +93,13 @@ class CleanUMamba(nn.Module):
             channels_H = min(channels_H * 2, max_H)
 
         self.tsfm_conv1 = nn.Conv1d(channels_output, tsfm_d_model, kernel_size=1, **factory_kwargs)
-        ssm_cfg = {"d_state": tsfm_d_model // tsfm_n_head, "d_conv": 4, "expand": tsfm_d_inner // tsfm_d_model,
-                   "use_fast_path": use_fast_path}
+        ssm_cfg = {"d_state": tsfm_d_model // tsfm_n_head, "d_conv": 4, "expand": tsfm_d_inner // tsfm_d_model}
+        if mamba_v2:        # as the reference builds it (src/network/CleanUMamba.py:141-151)
+            ssm_cfg["layer"] = "Mamba2"
+            ssm_cfg["headdim"] = tsfm_d_model // tsfm_n_head
+            ssm_cfg["use_mem_eff_path"] = False
+        else:
+            ssm_cfg["use_fast_path"] = use_fast_path
         self.rms_norm = rms_norm
         self.residual_in_fp32 = True
         self.fused_add_norm = fused_add_norm
@@ -906,6 +911,13 @@ class CleanUMamba(nn.Module):
                 module.d_inner = module.x_proj.in_features
                 module.dt_rank = module.dt_proj.in_features
                 module.d_state = (module.x_proj.out_features - module.dt_rank) // 2
+                module.expand = module.d_inner / module.d_model
+            elif type(module).__name__ == "Mamba2":
+                module.d_model = module.in_proj.in_features
+                module.nheads = module.A_log.shape[0]
+                module.d_ssm = module.d_inner = module.norm.weight.shape[0]
+                module.headdim = module.d_ssm // module.nheads
+                module.d_state = (module.in_proj.out_features - 2 * module.d_ssm - module.nheads) // 2
                 module.expand = module.d_inner / module.d_model
         self.load_state_dict(pruned_state_dict, strict=True)
         self.invalidate_packed_weights()

@@ -158,6 +158,8 @@ def unsupported_reason(model):
         return "parameters are not f32"
     for blk in model.tsfm_Mamba_layers:
         m = blk.mixer
+        if type(m).__name__ == "Mamba2":
+            return "Mamba2 bottleneck (mamba_v2=True): the one-launch hop covers Mamba1 blocks only"
         if type(m).__name__ != "Mamba" or not isinstance(blk.norm, nn.LayerNorm) or not blk.norm.elementwise_affine:
             return "bottleneck block is not LayerNorm + Mamba"
         if m.activation not in ("silu", "swish") or m.conv1d.weight.shape[-1] > 8:

@@ -608,6 +608,53 @@ int cum_optim_adam(float *p, const float *g, float *m, float *v, int64_t n, cons
                    double beta2, float eps, float weight_decay, void *stream);   /* betas as double: 1 - beta must not
                                                                                     be formed in f32 (0.999f: 5e-5 off) */
 
+/* ---- Mamba2 bottleneck (mamba_v2=True; csrc/ssd.hip).  ngroups 1, headdim and dstate in {16, 32, 64}, any len, any
+ * batch.  Per head h: dt_t = softplus(dt_raw_t + dt_bias_h), A_h = -exp(A_log_h),
+ *   state_t = exp(dt_t A_h) state_{t-1} + dt_t x_t B_t^T   (headdim x dstate),   y_t = state_t C_t + D_h x_t.
+ * x, y: rows of nheads * headdim elements; dt: rows of nheads; B, C: rows of dstate; row (b, t) of each starts at
+ * b * *_sb + t * *_sl elements (elements within a row contiguous).  io_dtype is the element type of x, dt, B, C, y and
+ * of their gradients; dt_bias, A_log, D, the states and the parameter gradients are f32.
+ * cum_ssd_fwd      <- mamba_ssm.ops.triton.ssd_combined.mamba_chunk_scan_combined (z = None, dt_softplus, dt_bias, D
+ *                     per head, no dt limit).  states: f32, cum_ssd_states_elems() (opaque: the chunk-start states the
+ *                     backward reads, chunks of cum_ssd_chunk() steps); final_state: NULL or (batch, nheads, headdim,
+ *                     dstate) contiguous.
+ * cum_ssd_bwd      <- its backward.  dy has y's strides, dx x's, ddt dt's (d dt_raw: the softplus is included); dB / dC
+ *                     are summed over heads in a fixed order; dA_log, dD, ddt_bias (nheads each) are overwritten.
+ *                     workspace: f32, cum_ssd_bwd_workspace_elems().  No atomics: bitwise reproducible. */
+typedef struct {
+  int32_t batch, len, nheads, headdim, dstate;
+  int64_t x_sb, x_sl, dt_sb, dt_sl, B_sb, B_sl, C_sb, C_sl, y_sb, y_sl;
+  int32_t io_dtype;
+} cum_ssd_shape;
+int cum_ssd_chunk(void);
+int64_t cum_ssd_states_elems(int32_t batch, int32_t len, int32_t nheads, int32_t headdim, int32_t dstate);
+int64_t cum_ssd_bwd_workspace_elems(int32_t batch, int32_t len, int32_t nheads, int32_t headdim, int32_t dstate);
+int cum_ssd_fwd(const cum_ssd_shape *s, const void *x, const void *dt, const float *dt_bias, const float *A_log,
+                const float *D, const void *B, const void *C, void *y, float *states, float *final_state, void *stream);
+int cum_ssd_bwd(const cum_ssd_shape *s, const void *x, const void *dt, const float *dt_bias, const float *A_log,
+                const float *D, const void *B, const void *C, const void *dy, const float *states, void *dx, void *ddt,
+                void *dB, int64_t dB_sb, int64_t dB_sl, void *dC, int64_t dC_sb, int64_t dC_sl, float *dA_log,
+                float *dD, float *ddt_bias, float *workspace, void *stream);
+/* cum_gated_rmsnorm_fwd/bwd <- mamba_ssm.ops.triton.layernorm_gated.RMSNormGated (norm_before_gate=False, one group):
+ * out = y * silu(z) * rsqrt(mean((y * silu(z))^2) + eps) * w over rows of `dim` elements (row pitches in elements,
+ * dtype for y, z, out, dout, dy, dz; w, rstd, dw f32).  rstd: NULL or one f32 per row, saved for the backward.
+ * dw is overwritten (per-workgroup slabs + fixed-order reduce); workspace: cum_gated_rmsnorm_bwd_workspace_elems(). */
+int cum_gated_rmsnorm_fwd(int32_t dtype, int64_t rows, int32_t dim, const void *y, int64_t y_ld, const void *z,
+                          int64_t z_ld, const float *w, float eps, void *out, int64_t out_ld, float *rstd, void *stream);
+int64_t cum_gated_rmsnorm_bwd_workspace_elems(int32_t dim);
+int cum_gated_rmsnorm_bwd(int32_t dtype, int64_t rows, int32_t dim, const void *y, int64_t y_ld, const void *z,
+                          int64_t z_ld, const float *w, const float *rstd, const void *dout, int64_t d_ld, void *dy,
+                          int64_t dy_ld, void *dz, int64_t dz_ld, float *dw, float *workspace, void *stream);
+/* cum_ssd_step <- Mamba2.step of mamba-ssm 2.x (causal_conv1d_update over xBC with SiLU, selective_state_update with a
+ * scalar decay per head, RMSNormGated): one token of every stream, f32, one launch.  zxbcdt: the in_proj output rows
+ * [z (d_ssm) | xBC (d_ssm + 2 dstate) | dt (nheads)], pitch ld; conv_state (streams, d_ssm + 2 dstate, width) and
+ * ssm_state (streams, nheads, d_ssm / nheads, dstate) contiguous, updated in place; out: (streams, d_ssm) rows, the
+ * gated-norm output that goes to out_proj. */
+int cum_ssd_step(int32_t streams, int32_t d_ssm, int32_t nheads, int32_t dstate, int32_t width, float eps,
+                 const float *zxbcdt, int64_t ld, float *conv_state, const float *conv_w, const float *conv_b,
+                 const float *dt_bias, const float *A_log, const float *D, const float *norm_w, float *ssm_state,
+                 float *out, int64_t out_ld, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
