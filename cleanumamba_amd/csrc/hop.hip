@@ -323,15 +323,39 @@ __device__ __forceinline__ void hop_gemm(const float *__restrict__ wb, const Hop
   }
 }
 
+// A slotted launch (cum_stream_hop_slots: the stream pool, cleanumamba_amd/network/streampool.py) gives each workgroup a
+// record of the item table instead of the stream blockIdx.x: which state row (slot) it owns, how many hops it walks and
+// where its input / output rows start.  Records are uniform per workgroup and read with scalar loads, as the op list is.
+constexpr int kHopItemInts = 8;      // {slot, n_hops, in_row, in_col, out_row, out_col, -, -}
+
+// SLOTS = false (cum_stream_hop): workgroup b owns stream b -- state row, input and output row b -- for all n_hops hops;
+// SLOTS = true (cum_stream_hop_slots): the workgroup's record names them, n_hops and `capacity` are the record's bounds.
+// (A template KERNEL, not a device function both kernels inline: inlined, the same body comes out with one more SGPR
+// spill in the lock-step kernel.  As it stands the lock-step instance has the registers, LDS and scratch it had.)
+template <bool SLOTS>
 __global__ __launch_bounds__(kHopThreads) void stream_hop_kernel(const HopPlan *__restrict__ plan,
                                                                   const float *__restrict__ w, float *state,
                                                                   int64_t state_stride, const float *__restrict__ in,
                                                                   int64_t in_stride, float *__restrict__ out,
-                                                                  int64_t out_stride, int n_hops) {
+                                                                  int64_t out_stride, int n_hops,
+                                                                  const int32_t *__restrict__ items, int capacity) {
   float *lds = hop_lds;
   __shared__ float red[kHopWaves];
   const int tid = threadIdx.x, lane = tid & 63, wave = uniform(tid >> 6);
-  float *st = state + (int64_t)blockIdx.x * state_stride;
+  float *st;
+  const float *in_base = in;
+  float *out_base = out;
+  if constexpr (SLOTS) {
+    const hop_cint rec = (hop_cint)(uintptr_t)items + blockIdx.x * kHopItemInts;
+    const int slot = rec[0];
+    n_hops = rec[1];
+    if (slot < 0 || slot >= capacity) return;     // (the host checked the table; a record that disagrees does nothing)
+    st = state + (int64_t)slot * state_stride;
+    in_base = in + (int64_t)rec[2] * in_stride + rec[3];
+    out_base = out + (int64_t)rec[4] * out_stride + rec[5];
+  } else {
+    st = state + (int64_t)blockIdx.x * state_stride;
+  }
   const int n_ops = plan->n_ops, frame_len = plan->frame_len, hop_len = plan->hop_len, phase_off = plan->phase_off;
   // ops are read with SCALAR loads from the plan (constant address space: s_load_dwordx8 / x16 straight into scalar
   // registers, served by the scalar cache all workgroups share) -- through LDS they cost 24 v_readfirstlane per op
@@ -348,8 +372,15 @@ __global__ __launch_bounds__(kHopThreads) void stream_hop_kernel(const HopPlan *
   }
 
   for (int hop = 0; hop < n_hops; ++hop) {
-    const float *frame = in + (int64_t)blockIdx.x * in_stride + (int64_t)hop * hop_len;
-    float *o = out + (int64_t)blockIdx.x * out_stride + (int64_t)hop * hop_len;
+    const float *frame;
+    float *o;
+    if constexpr (SLOTS) {
+      frame = in_base + (int64_t)hop * hop_len;
+      o = out_base + (int64_t)hop * hop_len;
+    } else {
+      frame = in + (int64_t)blockIdx.x * in_stride + (int64_t)hop * hop_len;
+      o = out + (int64_t)blockIdx.x * out_stride + (int64_t)hop * hop_len;
+    }
     const int phase = (int)st[phase_off];
     float stdv = 1.f;
     HOP_STAMP(0);
@@ -626,6 +657,27 @@ __global__ __launch_bounds__(kHopThreads) void stream_hop_kernel(const HopPlan *
   }
 }
 
+// Input rows of a pool call (cum_stream_pool_stage).  Record r = {slot, pend, len, consumed, x_row, stage_row, -, -}:
+//   stage[stage_row][0, pend + len) = hist[slot][0, pend) ++ x[x_row][0, len)         (what the slot's hops read)
+//   hist[slot][0, pend + len - consumed) = stage[stage_row][consumed, pend + len)     (what they leave unconsumed)
+// One workgroup per record.  The history is rewritten in place from the staged row, behind the barrier that ends every
+// read of the old history (a workgroup-scope fence: the row was written by this workgroup).
+constexpr int kStageThreads = 256, kStageRecInts = 8;
+__global__ __launch_bounds__(kStageThreads) void stream_pool_stage_kernel(float *hist, int64_t hist_stride,
+                                                                          const int32_t *__restrict__ recs,
+                                                                          const float *__restrict__ x, int64_t x_stride,
+                                                                          float *stage, int64_t stage_stride) {
+  const hop_cint rec = (hop_cint)(uintptr_t)recs + blockIdx.x * kStageRecInts;
+  const int slot = rec[0], pend = rec[1], len = rec[2], consumed = rec[3];
+  float *h = hist + (int64_t)slot * hist_stride;
+  const float *xr = x + (int64_t)rec[4] * x_stride;
+  float *sr = stage + (int64_t)rec[5] * stage_stride;
+  const int total = pend + len;
+  for (int t = threadIdx.x; t < total; t += kStageThreads) sr[t] = t < pend ? h[t] : xr[t - pend];
+  __syncthreads();
+  for (int t = threadIdx.x; t < total - consumed; t += kStageThreads) h[t] = sr[consumed + t];
+}
+
 }  // namespace cum
 
 using namespace cum;
@@ -650,13 +702,75 @@ extern "C" int cum_stream_hop(const void *plan, const float *weights, float *sta
   if (streams == 0 || n_hops == 0) return CUM_OK;
   CUM_REQUIRE(plan && weights && state && in && out, "stream_hop: null pointer");
   CUM_REQUIRE(((uintptr_t)weights & 15) == 0 && ((uintptr_t)state & 15) == 0, "stream_hop: weights / state must be 16-byte aligned");
-  hipError_t e = hipFuncSetAttribute((const void *)stream_hop_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
+  hipError_t e = hipFuncSetAttribute((const void *)stream_hop_kernel<false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_bytes);
   if (e != hipSuccess) {
     cum_set_error(hipGetErrorString(e));
     return CUM_ELAUNCH;
   }
-  hipLaunchKernelGGL(stream_hop_kernel, dim3(streams), dim3(kHopThreads), lds_bytes, (hipStream_t)stream,
-                     (const HopPlan *)plan, weights, state, state_stride, in, in_stride, out, out_stride, n_hops);
+  hipLaunchKernelGGL(stream_hop_kernel<false>, dim3(streams), dim3(kHopThreads), lds_bytes, (hipStream_t)stream,
+                     (const HopPlan *)plan, weights, state, state_stride, in, in_stride, out, out_stride, n_hops,
+                     nullptr, 0);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+static int hop_check_items(const int32_t *items_host, int32_t n_items, int32_t capacity, int ints, bool hops) {
+  for (int32_t i = 0; i < n_items; ++i) {
+    const int32_t *r = items_host + (int64_t)i * ints;
+    CUM_REQUIRE(r[0] >= 0 && r[0] < capacity, "stream_pool: a record names a slot outside the pool (slot < capacity)");
+    if (hops) {
+      CUM_REQUIRE(r[1] >= 1, "stream_hop_slots: a record with n_hops < 1 (name only slots that run a hop)");
+      CUM_REQUIRE(r[2] >= 0 && r[3] >= 0 && r[4] >= 0 && r[5] >= 0, "stream_hop_slots: negative row / column");
+    } else {
+      CUM_REQUIRE(r[1] >= 0 && r[2] >= 0 && r[3] >= 0 && r[3] <= r[1] + r[2] && r[4] >= 0 && r[5] >= 0,
+                  "stream_pool_stage: bad record");
+    }
+  }
+  return CUM_OK;
+}
+
+extern "C" int cum_stream_hop_slots(const void *plan, const float *weights, float *state, int64_t state_stride,
+                                    int32_t capacity, const int32_t *items_host, const int32_t *items, int32_t n_items,
+                                    const float *in, int64_t in_stride, float *out, int64_t out_stride,
+                                    int32_t lds_bytes, void *stream) {
+  CUM_REQUIRE(n_items >= 0 && capacity >= 0 && state_stride > 0, "stream_hop_slots: bad shape");
+  CUM_REQUIRE(lds_bytes > 0 && lds_bytes <= cum_stream_hop_max_lds_bytes() && lds_bytes % 16 == 0,
+              "stream_hop_slots: LDS size outside the kernel's limit (cum_stream_hop_max_lds_bytes)");
+  if (n_items == 0) return CUM_OK;
+  CUM_REQUIRE(plan && weights && state && items_host && items && in && out, "stream_hop_slots: null pointer");
+  CUM_REQUIRE(((uintptr_t)weights & 15) == 0 && ((uintptr_t)state & 15) == 0,
+              "stream_hop_slots: weights / state must be 16-byte aligned");
+  const int rc = hop_check_items(items_host, n_items, capacity, kHopItemInts, true);
+  if (rc != CUM_OK) return rc;
+  hipError_t e = hipFuncSetAttribute((const void *)stream_hop_kernel<true>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                     lds_bytes);
+  if (e != hipSuccess) {
+    cum_set_error(hipGetErrorString(e));
+    return CUM_ELAUNCH;
+  }
+  hipLaunchKernelGGL(stream_hop_kernel<true>, dim3(n_items), dim3(kHopThreads), lds_bytes, (hipStream_t)stream,
+                     (const HopPlan *)plan, weights, state, state_stride, in, in_stride, out, out_stride, 0, items,
+                     capacity);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_stream_pool_stage(float *hist, int64_t hist_stride, int32_t capacity, const int32_t *recs_host,
+                                     const int32_t *recs, int32_t n_recs, const float *x, int64_t x_stride, float *stage,
+                                     int64_t stage_stride, void *stream) {
+  CUM_REQUIRE(n_recs >= 0 && capacity >= 0 && hist_stride > 0 && stage_stride > 0 && x_stride >= 0,
+              "stream_pool_stage: bad shape");
+  if (n_recs == 0) return CUM_OK;
+  CUM_REQUIRE(hist && recs_host && recs && x && stage, "stream_pool_stage: null pointer");
+  const int rc = hop_check_items(recs_host, n_recs, capacity, kStageRecInts, false);
+  if (rc != CUM_OK) return rc;
+  for (int32_t i = 0; i < n_recs; ++i) {
+    const int32_t *r = recs_host + (int64_t)i * kStageRecInts;
+    CUM_REQUIRE(r[1] <= hist_stride && r[1] + r[2] - r[3] <= hist_stride && r[1] + r[2] <= stage_stride,
+                "stream_pool_stage: a row does not fit its history / stage row");
+  }
+  hipLaunchKernelGGL(stream_pool_stage_kernel, dim3(n_recs), dim3(kStageThreads), 0, (hipStream_t)stream, hist,
+                     hist_stride, recs, x, x_stride, stage, stage_stride);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

@@ -21,6 +21,7 @@ Differences from the reference, on purpose:
 import os
 import warnings
 import time
+import weakref
 from functools import partial
 
 import numpy as np
@@ -156,6 +157,7 @@ class CleanUMamba(nn.Module):
         state.pop("_hop_graph", None)       # captured hipGraph of the streaming hop
         state.pop("_hop_plan", None)        # packed weights / plan of the one-launch hop
         state.pop("_hop_kernel_why", None)
+        state.pop("_stream_pools", None)    # (weak references to the stream pools of this model)
         if state.pop("_hop_state", None) is not None:
             # a live stream of the one-launch hop keeps its state in the plan's device blocks, which are not pickled: the
             # copy starts a fresh stream (what is left in the per-layer fields is the first frame's state, stale by now)
@@ -401,6 +403,8 @@ class CleanUMamba(nn.Module):
         if hs is not None:                              # a live stream of the one-launch hop holds its own weight blob:
             hs["plan_weights"] = None                   # re-pack it on the next call (``param.data`` writes are invisible
                                                         # to _weights_version)
+        for pool in self.__dict__.get("_stream_pools", ()):
+            pool.invalidate_packed_weights()            # (so do the stream pools)
 
     # ----------------------------------------------------------------- streaming
     def reset_time_per_frame(self):
@@ -471,16 +475,24 @@ class CleanUMamba(nn.Module):
         self.reset_stream()              # the next clip starts a fresh stream: its running std starts over too
         return out
 
-    def _drain(self):
+    def _drain(self, rows=None, std=None):
         """Output samples behind the last hop, (S, frame_length - total_stride): what ``forward`` produces there.
         Decoder layer j still holds 2 overhang rows of its transposed conv (``dec{j}``, bias excluded) and encoder
         layer i holds ``2^(E-i) - 2`` output rows no hop has consumed as skips yet; layer j maps its
-        ``2^(j+1) - 2`` trailing input rows to ``2^(j+2) - 2`` trailing output rows."""
-        hs = self.__dict__.get("_hop_state")
-        if hs is not None:                                      # the one-launch hop owns the state: bring it back
-            self.encoder_decoder_state = hs["plan"].export_state(self, hs["state"])
-        state, E = self.encoder_decoder_state, self.encoder_n_layers
-        S, dev = self.pending.shape[0], self.pending.device
+        ``2^(j+1) - 2`` trailing input rows to ``2^(j+2) - 2`` trailing output rows.
+        ``rows`` / ``std``: drain these streams instead of the model's own (a stream pool's closing slots: the layout of
+        hopplan.HopPlan.export_rows, and their running std, (S, 1), with normalize_input)."""
+        if rows is None:
+            hs = self.__dict__.get("_hop_state")
+            if hs is not None:                                  # the one-launch hop owns the state: bring it back
+                self.encoder_decoder_state = hs["plan"].export_state(self, hs["state"])
+            state = self.encoder_decoder_state
+            S, dev = self.pending.shape[0], self.pending.device
+            std = self.input_std
+        else:
+            state = rows
+            S, dev = rows["enc0"].shape[0], rows["enc0"].device
+        E = self.encoder_n_layers
 
         rows_layout = state["enc0"].dim() == 2                 # fused hop: 2-D row buffers; cached hop: (S, C, T)
 
@@ -535,7 +547,7 @@ class CleanUMamba(nn.Module):
             x = y
         out = x[:, 0]
         if self.normalize_input:
-            out = out * self.input_std
+            out = out * std
         return out
 
     @torch.no_grad()
@@ -647,6 +659,16 @@ class CleanUMamba(nn.Module):
         self.__dict__.pop("_hop_graph", None)
         return hs
 
+    def stream_pool(self, capacity):
+        """A pool of ``capacity`` stream slots on this model (network/streampool.py): streams that join, feed any number of
+        samples and leave independently, every call's hops in one launch of the one-launch hop.  The pool keeps its own
+        state; ``feed`` / ``feed_batch`` / ``flush`` of the model are not affected.  Models the one-launch hop declines
+        (hopplan.unsupported_reason: Mamba2, above hopplan.MAX_PARAMS, non-f32) raise ValueError."""
+        from .streampool import StreamPool
+        pool = StreamPool(self, capacity)
+        self.__dict__.setdefault("_stream_pools", weakref.WeakSet()).add(pool)
+        return pool
+
     @property
     def hop_kernel_status(self):
         """"active" while the one-launch hop owns the stream state, else why not ("off", "first frame pending", reason)."""
@@ -735,7 +757,7 @@ class CleanUMamba(nn.Module):
         with cs.small_m_gemms():
             return self._denoise_frame_fused_impl(frame)
 
-    def _denoise_frame_fused_impl(self, frame):
+    def _denoise_frame_fused_impl(self, frame, state=None, inference_params=None):
         """One hop on the fused GEMM kernels, same arithmetic as _denoise_frame.  Every encoder layer keeps a persistent
         window of its output (the decoder's skips read its oldest rows); the first hop of a stream computes the
         windows whole (S independent clips of valid_length(1) samples), later hops compute only the hop's new rows
@@ -743,12 +765,15 @@ class CleanUMamba(nn.Module):
         so older activations keep the input scaling of the hop that produced them, as with the reference's per-layer
         caches (``stream_incremental = False`` recomputes the windows every hop); a decoder layer is
         1x1+GLU GEMM, transposed-conv GEMM and one overlap-add kernel (cum_stream_overlap_add) that also applies
-        ReLU, adds the skip and keeps the tail for the next hop."""
+        ReLU, adds the skip and keeps the tail for the next hop.
+        ``state`` / ``inference_params``: run on these streams instead of the model's own (a stream pool's first frames)."""
         S, E, dev = frame.shape[0], self.encoder_n_layers, frame.device
         dt = torch.bfloat16 if getattr(self, "stream_bf16", False) else torch.float32
         self._activate_pack_plan(dt)
         geo = cs.Geo(S, frame.shape[1], self.encoder[0][0].weight.shape[1])
-        state, lib = self.encoder_decoder_state, hip.lib()
+        if state is None:
+            state, inference_params = self.encoder_decoder_state, self.inference_params
+        lib = hip.lib()
         # After the first hop of a stream only the hop's new rows of every layer are computed: layer i emits
         # n = total_stride >> (i + 1) rows from the 2 n + 2 newest rows of its input (2 carried + 2 n new ones).
         incremental = state.get("enc0") is not None and getattr(self, "stream_incremental", True)
@@ -797,7 +822,7 @@ class CleanUMamba(nn.Module):
             enc_geos.append((geo, g_mid, g_out))
             outs.append(window)
             buf, geo = window, g_out
-        x, _ = self._bottleneck(cs.from_rows(outs[-1], geo).float(), inference_params=self.inference_params,
+        x, _ = self._bottleneck(cs.from_rows(outs[-1], geo).float(), inference_params=inference_params,
                                 pointwise_as_linear=True)                                                     # (S, C, 1)
         L = x.shape[-1]
         x = x + cs.from_rows(outs[-1], geo)[..., :L].float()

@@ -1,0 +1,276 @@
+"""Stream pool: streams that join, feed and leave independently, on the one-launch hop (csrc/hop.hip).
+
+``feed_batch`` runs S streams in lock-step: they start together, every call gives each the same number of samples, and
+they end together.  A pool has a fixed number of SLOTS that share one packed weight blob and one state block
+([capacity, state_stride], the layout of hopplan.HopPlan); any subset of the open slots can be fed in a call, with any
+number of samples each, and every slot opens and closes on its own.  Per call:
+
+  1. the host schedules the call (``schedule``: a pure function of the slots' pending counts and chunk lengths) -- it
+     knows every slot's pending count, nothing is read back from the device;
+  2. one staging launch (``cum_stream_pool_stage``) builds each named slot's input row from its history (the samples no
+     hop has consumed yet, ``hist`` [capacity, frame_len - 1]) and the new chunk, and writes back what will be left;
+  3. slots that reach their FIRST frame in this call (whole windows, no history) run it together on the per-layer fused
+     path, in a private streaming context (the model's own stream is not touched), and their state rows are imported
+     into the block with a frame count of 1;
+  4. one launch of the slotted hop (``cum_stream_hop_slots``) runs every named slot's hops: one workgroup per slot that
+     has a hop to run, whatever the capacity, longest first.
+
+``close`` gives each slot what ``flush`` gives a lone stream: zeros up to the slot's own ``valid_length``, its remaining
+hops, the decoder drain from its state rows (each at its own ring phase), then the rows are zeroed and the slot id can be
+reused.  Reference semantics: CleanUMamba.feed / flush, src/network/CleanUMamba.py:358-418, as ``feed`` / ``flush`` of
+this package implement them.
+"""
+import collections
+
+import numpy as np
+import torch
+
+from .. import hip
+from . import convstack as cs
+from . import hopplan
+from ..mamba_ssm.utils.generation import InferenceParams
+
+_REC = 8        # int32 per record of both tables (csrc/hop.hip: kHopItemInts, kStageRecInts)
+
+Schedule = collections.namedtuple("Schedule", "first n_hops offset consumed remainder")
+
+
+def schedule(pending, started, lengths, frame_len, hop):
+    """One call of the pool for the named slots (arrays of one entry per slot):
+      pending   samples the slot holds that no hop has consumed (< frame_len);
+      started   whether the slot's first frame has run;
+      lengths   samples the call brings.
+    Returns ``Schedule`` arrays:
+      first     the slot runs its first frame in this call (the cohort of the per-layer path);
+      n_hops    hops of the slotted launch;
+      offset    where the slot's first kernel frame starts in its row (pending ++ chunk): ``hop`` behind a first frame;
+      consumed  samples the call consumes = samples it emits (a frame emits ``hop``);
+      remainder samples left pending (< frame_len)."""
+    pending = np.asarray(pending, dtype=np.int64)
+    lengths = np.asarray(lengths, dtype=np.int64)
+    started = np.asarray(started, dtype=bool)
+    total = pending + lengths
+    first = ~started & (total >= frame_len)
+    offset = np.where(first, hop, 0)
+    avail = total - offset
+    n_hops = np.where((started | first) & (avail >= frame_len), (avail - frame_len) // hop + 1, 0)
+    consumed = offset + n_hops * hop
+    return Schedule(first, n_hops, offset, consumed, total - consumed)
+
+
+class StreamPool:
+    """``capacity`` stream slots of one model; see the module docstring.  Made by ``CleanUMamba.stream_pool``.
+
+    Only models the one-launch hop runs can be pooled (``hopplan.unsupported_reason``: Mamba1 bottleneck, at most
+    ``hopplan.MAX_PARAMS`` parameters, f32): every slot re-reads the weight blob per hop, and a slot's whole state lives in
+    one row of the kernel's state block.  Others raise ``ValueError``."""
+
+    def __init__(self, model, capacity):
+        why = hopplan.unsupported_reason(model)
+        if why is not None:
+            raise ValueError(f"stream pool: {why}")
+        if not cs.supported(model):
+            raise ValueError("stream pool: the first frame of a slot runs on the fused per-layer hop, which does not "
+                             "cover this model")
+        capacity = int(capacity)
+        if capacity < 1:
+            raise ValueError("stream pool: capacity must be >= 1")
+        self.model, self.capacity = model, capacity
+        self._wv = model._weights_version()
+        self._stale = False
+        self.plan = hopplan.HopPlan(model)
+        self.hop, self.frame_len, self.device = self.plan.hop, self.plan.frame_len, self.plan.device
+        self.state = torch.zeros(capacity, self.plan.state_stride, dtype=torch.float32, device=self.device)
+        self.hist = torch.zeros(capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32, device=self.device)
+        self._open = np.zeros(capacity, dtype=bool)
+        self._pend = np.zeros(capacity, dtype=np.int64)       # samples in hist[slot]
+        self._frames = np.zeros(capacity, dtype=np.int64)     # frames run (the first one included)
+
+    # ------------------------------------------------------------------ slots
+    @property
+    def live(self):
+        """The open slots, ascending."""
+        return [int(s) for s in np.flatnonzero(self._open)]
+
+    def pending(self, slots):
+        """Samples each slot holds that no hop has consumed yet."""
+        return [int(self._pend[s]) for s in self._slots(slots)]
+
+    def open(self, n=1):
+        """Open ``n`` slots (the lowest free ids); returns their ids.  Each starts a fresh stream."""
+        n = int(n)
+        free = np.flatnonzero(~self._open)
+        if n < 0 or n > free.size:
+            raise ValueError(f"stream pool: {n} slots asked for, {free.size} of {self.capacity} free")
+        got = free[:n]
+        self._open[got] = True
+        return [int(s) for s in got]
+
+    def reset(self):
+        """Close every slot without output; all state is zeroed."""
+        self.state.zero_()
+        self.hist.zero_()
+        self._open[:] = False
+        self._pend[:] = 0
+        self._frames[:] = 0
+
+    def invalidate_packed_weights(self):
+        """Re-pack the weight blob on the next call (``CleanUMamba.invalidate_packed_weights`` calls this)."""
+        self._stale = True
+
+    def _slots(self, slots):
+        a = np.asarray([int(s) for s in slots], dtype=np.int64)
+        if a.size and (a.min() < 0 or a.max() >= self.capacity):
+            raise ValueError(f"stream pool: slot ids must lie in [0, {self.capacity})")
+        if np.unique(a).size != a.size:
+            raise ValueError("stream pool: a slot is named twice in one call")
+        shut = a[~self._open[a]]
+        if shut.size:
+            raise ValueError(f"stream pool: slot {int(shut[0])} is not open")
+        return a
+
+    # ------------------------------------------------------------------ feed / close
+    @torch.no_grad()
+    def feed(self, slots, x):
+        """New samples of the named slots: ``x`` (len(slots), L) f32 on the pool's GPU, or a list of 1-D tensors (one per
+        slot, any lengths).  Returns one 1-D tensor per slot, a multiple of ``total_stride`` long: views of one buffer."""
+        a = self._slots(slots)
+        if isinstance(x, (list, tuple)):
+            if len(x) != a.size or any(t.dim() != 1 for t in x):
+                raise ValueError("stream pool: feed takes one 1-D tensor per slot")
+            lengths = np.asarray([t.shape[0] for t in x], dtype=np.int64)
+            x = torch.nn.utils.rnn.pad_sequence(list(x), batch_first=True) if a.size else None
+        else:
+            if x.dim() != 2 or x.shape[0] != a.size:
+                raise ValueError("stream pool: x must be (len(slots), samples)")
+            lengths = np.full(a.size, x.shape[1], dtype=np.int64)
+            if x.shape[1] > 1 and x.stride(1) != 1:
+                x = x.contiguous()
+        if x is not None and (x.dtype != torch.float32 or x.device != self.device):
+            raise ValueError(f"stream pool: samples must be f32 on {self.device}")
+        return self._run(a, x, lengths)
+
+    @torch.no_grad()
+    def close(self, slots):
+        """End the named slots' streams: what ``flush`` gives a lone stream (its pending samples padded with the zeros
+        ``forward`` adds, the remaining hops, the decoder's drain), one 1-D tensor per slot.  The slots are free again."""
+        a = self._slots(slots)
+        hop = self.hop
+        pend, frames = self._pend[a].copy(), self._frames[a].copy()
+        total = frames * hop + pend
+        pad = np.asarray([self.model.valid_length(int(t)) - int(t) if t > 0 else 0 for t in total], dtype=np.int64)
+        x = torch.zeros(a.size, int(pad.max()) if a.size else 0, dtype=torch.float32, device=self.device)
+        heads = self._run(a, x, pad)
+        outs = [torch.zeros(0, dtype=torch.float32, device=self.device) for _ in range(a.size)]
+        live = np.flatnonzero(total > 0)
+        if live.size:
+            idx = self._index(a[live])
+            st = self.state.index_select(0, idx)
+            std = st[:, 0:1] if self.plan.hdr["normalize"] else None
+            tail = self.model._drain(rows=self.plan.export_rows(st), std=std)
+            for j, i in enumerate(live):
+                outs[i] = torch.cat([heads[i], tail[j].to(heads[i].dtype)])[:int(pend[i])]
+        if a.size:
+            idx = self._index(a)
+            self.state.index_fill_(0, idx, 0.0)
+            self.hist.index_fill_(0, idx, 0.0)
+        self._open[a] = False
+        self._pend[a] = 0
+        self._frames[a] = 0
+        return outs
+
+    def _index(self, a):
+        """Slot ids as a device int64 index (pinned host copy: no wait on the device)."""
+        if self.device.type != "cuda":
+            return torch.from_numpy(a.astype(np.int64))
+        return torch.from_numpy(a.astype(np.int64)).pin_memory().to(self.device, non_blocking=True)
+
+    def _refresh_weights(self):
+        wv = self.model._weights_version()
+        if wv == self._wv and not self._stale:
+            return
+        try:
+            plan = hopplan.HopPlan(self.model)
+        except ValueError as exc:
+            raise RuntimeError(f"stream pool: the weights changed into a model the one-launch hop cannot run ({exc}); "
+                               "close the slots before changing them") from exc
+        if plan.state_stride != self.plan.state_stride:
+            raise RuntimeError("stream pool: the model's shapes changed under live slots")
+        self.plan, self._wv, self._stale = plan, wv, False
+
+    def _run(self, a, x, lengths):
+        n = a.size
+        hop, F = self.hop, self.frame_len
+        if n == 0 or int(lengths.sum()) == 0:
+            # nothing arrives: no slot reaches a frame (pending < frame_len), nothing changes
+            return [torch.zeros(0, dtype=torch.float32, device=self.device) for _ in range(n)]
+        if self.device.type != "cuda":
+            raise RuntimeError("stream pool: the model is not on a GPU")
+        self._refresh_weights()
+        pend = self._pend[a]
+        sch = schedule(pend, self._frames[a] > 0, lengths, F, hop)
+        # stage / output rows: the first-frame cohort first (its frames are then one slice of the staged rows)
+        order = np.argsort(~sch.first, kind="stable")
+        row = np.empty(n, dtype=np.int64)
+        row[order] = np.arange(n)
+        k = int(sch.first.sum())
+        total = pend + lengths
+        stage = torch.empty(n, hopplan._rup(max(int(total.max()), 1), 4), dtype=torch.float32, device=self.device)
+        out = torch.empty(n, int(sch.consumed.max()), dtype=torch.float32, device=self.device)
+        # one host table, one copy: staging records, slotted-hop records (longest first), the cohort's slot ids
+        hops = np.flatnonzero(sch.n_hops > 0)
+        hops = hops[np.argsort(-sch.n_hops[hops], kind="stable")]
+        m = hops.size
+        tab = np.zeros((n + m) * _REC + k, dtype=np.int32)
+        srec = tab[:n * _REC].reshape(n, _REC)
+        srec[:, 0], srec[:, 1], srec[:, 2], srec[:, 3] = a, pend, lengths, sch.consumed
+        srec[:, 4], srec[:, 5] = np.arange(n), row
+        hrec = tab[n * _REC:(n + m) * _REC].reshape(m, _REC)
+        hrec[:, 0], hrec[:, 1] = a[hops], sch.n_hops[hops]
+        hrec[:, 2], hrec[:, 3] = row[hops], sch.offset[hops]
+        hrec[:, 4], hrec[:, 5] = row[hops], sch.offset[hops]
+        tab[(n + m) * _REC:] = a[order[:k]]
+        host = torch.from_numpy(tab).pin_memory()
+        dtab = host.to(self.device, non_blocking=True)
+        lib = hip.lib()
+        xs = x if x.numel() else stage              # (a call of empty chunks reads no sample)
+        with torch.cuda.device(self.device):
+            hip.check(lib.cum_stream_pool_stage(hip.ptr(self.hist), self.hist.stride(0), self.capacity, hip.ptr(host),
+                                                hip.ptr(dtab), n, hip.ptr(xs), xs.stride(0), hip.ptr(stage),
+                                                stage.stride(0), hip.stream_ptr()))
+        if k:
+            self._first_frames(stage[:k, :F], out[:k, :hop], dtab[(n + m) * _REC:].long())
+        if m:
+            p = self.plan
+            with torch.cuda.device(self.device):
+                hip.check(lib.cum_stream_hop_slots(
+                    hip.ptr(p.plan), hip.ptr(p.weights), hip.ptr(self.state), p.state_stride, self.capacity,
+                    hip.ptr(host[n * _REC:]), hip.ptr(dtab[n * _REC:]), m, hip.ptr(stage), stage.stride(0),
+                    hip.ptr(out), out.stride(0), p.lds_bytes, hip.stream_ptr()))
+        self._pend[a] = sch.remainder
+        self._frames[a] += sch.first + sch.n_hops
+        width = sch.consumed
+        if (width == width[0]).all():
+            rows = out.unbind(0)
+            return [rows[r] for r in row]
+        return [out[r, :w] for r, w in zip(row, width)]
+
+    def _first_frames(self, frame, dst, slot_idx):
+        """The first frame of the slots in ``slot_idx`` (k, frame_len) on the per-layer fused path, in a private streaming
+        context, as ``feed_batch`` runs a stream's first frame; their state rows go into the pool's block."""
+        model, k = self.model, frame.shape[0]
+        params = InferenceParams(max_seqlen=1, max_batch_size=k, key_value_memory_dict=model.allocate_inference_cache(k, 1),
+                                 seqlen_offset=1)
+        state, std = {}, None
+        if self.plan.hdr["normalize"]:
+            # (CleanUMamba.feed_batch: the running mean of the per-frame std after ONE frame)
+            std = frame.std(dim=1, keepdim=True) + 1e-3
+            frame = frame / std
+        with cs.small_m_gemms():
+            y = model._denoise_frame_fused_impl(frame, state=state, inference_params=params)[:, :self.hop]
+        if std is not None:
+            y = y * std
+        dst.copy_(y)
+        self.plan.import_state(model, k, state=state, inference_params=params, input_std=std, frames=1, into=self.state,
+                               at=slot_idx)
+

@@ -472,6 +472,29 @@ int cum_stream_hop(const void *plan, const float *weights, float *state, int64_t
                    const float *in, int64_t in_stride, float *out, int64_t out_stride, int32_t n_hops,
                    int32_t lds_bytes, void *stream);
 
+/* ---- the stream pool (csrc/hop.hip; cleanumamba_amd/network/streampool.py): streams that join and leave on their own.
+ * Replaces, for any subset of a fixed set of slots, what CleanUMamba.feed of src/network/CleanUMamba.py:370-418 does for
+ * one stream (its pending buffer, running std and per-layer state), with the hops of all named slots in ONE launch.
+ * cum_stream_hop_slots: the interpreter of cum_stream_hop over an ITEM TABLE instead of `streams` x `n_hops`: n_items
+ * workgroups, record i = 8 int32 {slot, n_hops, in_row, in_col, out_row, out_col, 0, 0}: the workgroup runs n_hops
+ * hops of the stream whose state is row `slot` of `state` (capacity rows), reading hop h's frame at
+ * in[in_row * in_stride + in_col + h * hop_len ...+ frame_len) and writing out[out_row * out_stride + out_col + h * hop_len
+ * ...+ hop_len).  `items` is the device table, `items_host` the same table in host memory: the entry point checks every
+ * record (0 <= slot < capacity, n_hops >= 1, no negative row or column) before the launch.  A slot named twice in one
+ * table is a race the caller excludes.  Plan, weights, LDS rules: as cum_stream_hop. */
+int cum_stream_hop_slots(const void *plan, const float *weights, float *state, int64_t state_stride, int32_t capacity,
+                         const int32_t *items_host, const int32_t *items, int32_t n_items, const float *in,
+                         int64_t in_stride, float *out, int64_t out_stride, int32_t lds_bytes, void *stream);
+/* Input rows of a pool call and the slots' unconsumed samples.  hist: [capacity][hist_stride] f32, slot s keeps its
+ * pending samples at hist[s][0, pend).  Record r = 8 int32 {slot, pend, len, consumed, x_row, stage_row, 0, 0}:
+ *   stage[stage_row][0, pend + len) = hist[slot][0, pend) ++ x[x_row][0, len)
+ *   hist[slot][0, pend + len - consumed) = stage[stage_row][consumed, pend + len)
+ * One launch for all records (recs: device table, recs_host: the same in host memory, checked: slot < capacity, the
+ * rows fit hist_stride / stage_stride).  Slots not named are not touched. */
+int cum_stream_pool_stage(float *hist, int64_t hist_stride, int32_t capacity, const int32_t *recs_host,
+                          const int32_t *recs, int32_t n_recs, const float *x, int64_t x_stride, float *stage,
+                          int64_t stage_stride, void *stream);
+
 /* ---- first encoder layer, fused (csrc/enc0.hip): Conv1d(1 -> 64, k 4, s 2) + ReLU + Conv1d(64 -> 128, 1x1) + GLU of
  * src/network/CleanUMamba.py:108-113 at channels_input = 1, channels_H = 64 (E6 / E8), 16-bit element types.  The ReLU
  * output of the one-input-channel conv is rebuilt from the four input samples wherever it is needed instead of being
