@@ -164,6 +164,13 @@ SIGNATURES = {
     "cum_ssd_step": (c_i32, [c_i32] * 5 + [ctypes.c_float, _P, c_i64] + [_P] * 9 + [c_i64, _P]),
     "cum_optim_adam": (c_i32, [_P, _P, _P, _P, c_i64, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float,
                                _P]),
+    "cum_metrics_frame_count": (c_i64, [c_i64]),
+    "cum_metrics_reduce_keep": (c_i64, [c_i64]),
+    "cum_metrics_workspace_bytes": (c_i64, [c_i64, c_i64]),
+    "cum_metrics_frames": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, c_i32] + [_P] * 5 + [c_i64] + [_P] * 3 + [c_i64, _P]),
+    "cum_metrics_clip_reduce": (c_i32, [_P, _P, c_i64, c_i32, _P, c_i64, _P, _P]),
+    "cum_metrics_stoi_workspace_bytes": (c_i64, [_P, c_i64, c_i32]),
+    "cum_metrics_stoi": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, c_i32, _P, c_i32] + [_P] * 4 + [c_i64, _P, _P]),
 }
 
 _lib = None

@@ -1,0 +1,118 @@
+"""Validation while training (reference src/util/denoise_eval.py:validate): denoise a test set and score it.
+
+The test set layouts are the reference's: DNS (``clean/clean_fileid_{i}.wav`` and ``noisy/*_fileid_{i}.wav``, or
+``fileid_{i}.wav`` in both folders with ``validation=False``) and VCTK_DEMAND (the same file name in ``clean/`` and
+``noisy/``).  Differences from the reference:
+  * clips of equal length are denoised together, ``batch_size`` per ``forward`` (the DNS test clips are all 10 s); a
+    batched forward need not be bit-identical to one clip at a time;
+  * the denoised signal is quantised with ``* 32767``, clamped to the int16 range and cast (truncating); the reference's
+    cast is unclamped and wraps on overshoot;
+  * every clip is scored in one batched call on the GPU (cleanumamba_amd.util.python_eval.eval_waveforms); PESQ and
+    the composites built on it are NaN unless the ``pesq`` package is installed.
+  * ``metrics`` is accepted and, as in the reference, not used.
+"""
+import os
+
+import numpy as np
+import torch
+from scipy.io import wavfile
+
+from .python_eval import eval_waveforms
+
+KEYS = ("pesq_wb", "pesq_nb", "stoi", "CSIG", "CBAK", "COVL", "wss_dist", "segSNR", "llr_mean", "count")
+
+
+def _read_float(path):
+    """(rate, (channels, samples) float32), int16 scaled by 1 / 32768 as torchaudio.load does."""
+    rate, x = wavfile.read(path)
+    if x.dtype == np.int16:
+        x = x.astype(np.float32) / 32768.0
+    elif x.dtype == np.int32:
+        x = x.astype(np.float32) / 2147483648.0
+    else:
+        x = x.astype(np.float32)
+    x = x.reshape(x.shape[0], -1).T if x.ndim == 2 else x[None]
+    return rate, torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _pairs(testset_path, validation, VCTK_DEMAND, test_factor):
+    """[(clean path, noisy path)] in the reference's order; missing files are skipped as the reference skips them."""
+    noisy_dir, clean_dir = os.path.join(testset_path, "noisy"), os.path.join(testset_path, "clean")
+    noisy_files = os.listdir(noisy_dir)
+    n = len(noisy_files) * (1 if VCTK_DEMAND else 2)
+    out = []
+    for i in range(int(n * test_factor)):
+        if VCTK_DEMAND:
+            if i >= len(noisy_files):
+                continue
+            c, nz = os.path.join(clean_dir, noisy_files[i]), os.path.join(noisy_dir, noisy_files[i])
+        elif validation:
+            c = os.path.join(clean_dir, "clean_fileid_{}.wav".format(i))
+            match = [f for f in noisy_files if f.split("_")[-1][0:-4] == str(i)]
+            if not match:
+                continue
+            nz = os.path.join(noisy_dir, match[0])
+        else:
+            c, nz = os.path.join(clean_dir, "fileid_{}.wav".format(i)), os.path.join(noisy_dir, "fileid_{}.wav".format(i))
+        if os.path.exists(c) and os.path.exists(nz):
+            out.append((c, nz))
+    return out
+
+
+def validate(net, testset_path, quantize_audio_input=False, network_processor=None, validation=True, VCTK_DEMAND=False,
+             metrics=("pesq_wb", "pesq_nb", "stoi", "DNSMOS"), test_factor=1.0, crop=None, batch_size=16):
+    """Denoise the test set with ``net`` and return the reference's dict of length-weighted sums ('Test/pesq_wb', ...,
+    'Test/llr_mean') plus 'Test/count', the total length; divide by 'Test/count' for the means."""
+    result = {"Test/" + k: 0 for k in KEYS}
+    device, half = torch.device("cuda"), False
+    for p in getattr(net, "parameters", lambda: iter(()))():
+        device, half = p.device, p.dtype is torch.float16
+        break
+
+    clips = []                                    # (rate, clean int16, noisy (1, L) float32)
+    for c, nz in _pairs(testset_path, validation, VCTK_DEMAND, test_factor):
+        rate, clean = wavfile.read(c)
+        _, noisy = _read_float(nz)
+        clips.append((rate, clean, noisy))
+
+    def prepare(x):
+        if network_processor is not None and hasattr(network_processor, "prepare_input"):
+            return network_processor.prepare_input(x)
+        return x
+
+    def finish(y):
+        if network_processor is not None and hasattr(network_processor, "finish_output"):
+            return network_processor.finish_output(y)
+        return y
+
+    denoised = [None] * len(clips)
+    by_len = {}
+    for i, (_, _, noisy) in enumerate(clips):
+        by_len.setdefault(tuple(noisy.shape), []).append(i)
+    with torch.no_grad():
+        for idx in by_len.values():
+            for s in range(0, len(idx), batch_size):
+                part = idx[s:s + batch_size]
+                x = torch.stack([prepare(clips[i][2]) for i in part]).to(device)
+                if half:
+                    x = x.half()
+                y = finish(net(x)).float()
+                q = (y * 32767).clamp(-32768, 32767).to(torch.int16).cpu().numpy()
+                for j, i in enumerate(part):
+                    denoised[i] = q[j].squeeze()
+
+    cleans, targets, rates = [], [], []
+    for (rate, clean, _), d in zip(clips, denoised):
+        if crop is not None:
+            clean, d = clean[:crop * rate], d[:crop * rate]
+        cleans.append(clean)
+        targets.append(d)
+        rates.append(rate)
+    if not cleans:
+        return result
+    for rate in sorted(set(rates)):
+        sel = [i for i, r in enumerate(rates) if r == rate]
+        for r in eval_waveforms([cleans[i] for i in sel], [targets[i] for i in sel], rate):
+            for k in r:
+                result["Test/" + k] += r[k]
+    return result

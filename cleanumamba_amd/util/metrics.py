@@ -1,0 +1,261 @@
+"""Speech-quality metrics of a ragged batch of clips on the GPU (csrc/metrics.hip).
+
+``speech_metrics(clean, processed)`` scores any number of clips of any lengths in one launch sequence: the per-clip
+``wss_dist``, ``llr_mean`` and ``segSNR`` of the reference's ``python_eval.eval_waveform`` and STOI (``pystoi.stoi``,
+Taal et al. 2011).  Samples are int16 values, as the reference scores them; float inputs must hold integers in the int16
+range.  Nothing here runs a metric on the CPU: the kernels are the only implementation.
+
+The constant tables are built here on the host:
+  * the 25 critical bands of Klatt's weighted spectral slope measure, as published with the composite measures of Hu &
+    Loizou, "Evaluation of objective quality measures for speech enhancement", IEEE TASLP 16(1), 2008: centre
+    frequencies and bandwidths in Hz, Gaussian filters of 1024-point FFT bins truncated at -30 dB, kept sparse;
+  * the 15 one-third-octave bands of STOI from 150 Hz over a 512-point FFT at 10 kHz, and the 16 k -> 10 k polyphase
+    filter (Kaiser-windowed sinc, 60 dB rejection) of STOI's Octave-compatible resampler.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from .. import hip
+
+FRAME_RATE = 16000
+WIN, HOP = 480, 120                  # 30 ms frames, 75 % overlap
+STOI_RATES = (16000, 10000)
+ALPHA = 0.95                         # fraction of the lowest frame values kept by the WSS / LLR means
+
+# Klatt's critical bands (Hu & Loizou 2008): centre frequency and bandwidth, Hz
+CRIT_CENTRE = (50.0000, 120.000, 190.000, 260.000, 330.000, 400.000, 470.000, 540.000, 617.372, 703.378, 798.717,
+               904.128, 1020.38, 1148.30, 1288.72, 1442.54, 1610.70, 1794.16, 1993.93, 2211.08, 2446.71, 2701.97,
+               2978.04, 3276.17, 3597.63)
+CRIT_BANDWIDTH = (70.0000, 70.0000, 70.0000, 70.0000, 70.0000, 70.0000, 70.0000, 77.3724, 86.0056, 95.3398, 105.411,
+                  116.256, 127.914, 140.423, 153.823, 168.154, 183.457, 199.776, 217.153, 235.631, 255.255, 276.072,
+                  298.126, 321.465, 346.136)
+
+
+def frame_window():
+    """The 480-point Hann-type window of the frame metrics: 0.5 (1 - cos(2 pi n / 481)), n = 1..480."""
+    return 0.5 * (1 - np.cos(2 * math.pi * np.arange(1, WIN + 1) / (WIN + 1)))
+
+
+def crit_band_table(rate=FRAME_RATE):
+    """Sparse critical-band filters over bins 0..511 of the 1024-point FFT: ``(tab, weights)`` with tab[b] = (first bin,
+    bin count, offset into weights).  Each band is exp(-11 ((j - floor(f0)) / bw)^2) scaled by bw_min / bw, its values
+    at or below the -30 dB point dropped; the support is one run of bins."""
+    n_fft = int(2 ** math.ceil(math.log2(2 * WIN)))
+    half, nyq = n_fft // 2, rate // 2
+    min_factor = math.exp(-30.0 / (2.0 * 2.303))
+    j = np.arange(half)
+    tab, weights = [], []
+    for cf, bwh in zip(CRIT_CENTRE, CRIT_BANDWIDTH):
+        f0, bw = cf / nyq * half, bwh / nyq * half
+        w = np.exp(-11 * np.square((j - np.floor(f0)) / bw) + (np.log(CRIT_BANDWIDTH[0]) - np.log(bwh)))
+        keep = np.nonzero(w > min_factor)[0]
+        lo, hi = int(keep[0]), int(keep[-1]) + 1
+        assert hi - lo == keep.size
+        tab.append((lo, hi - lo, sum(len(x) for x in weights)))
+        weights.append(w[lo:hi])
+    return np.array(tab, np.int32), np.concatenate(weights)
+
+
+def third_octave_table(fs=10000, nfft=512, num_bands=15, min_freq=150):
+    """[first, end) FFT bin of each one-third-octave band: the bins nearest to min_freq 2^((2k -+ 1) / 6)."""
+    f = np.linspace(0, fs, nfft + 1)[: nfft // 2 + 1]
+    k = np.arange(num_bands, dtype=float)
+    lo = min_freq * np.power(2.0, (2 * k - 1) / 6)
+    hi = min_freq * np.power(2.0, (2 * k + 1) / 6)
+    return np.array([(int(np.argmin(np.square(f - a))), int(np.argmin(np.square(f - b)))) for a, b in zip(lo, hi)],
+                    np.int32)
+
+
+def resample_taps(p=10000, q=16000):
+    """STOI's anti-aliasing filter for p / q resampling (Kaiser-windowed sinc, 60 dB rejection, transition a tenth of
+    the cut-off), normalised to unit sum and scaled by the reduced up factor, as the polyphase resampler applies it."""
+    g = math.gcd(p, q)
+    up, down = p // g, q // g
+    stop = 1.0 / (2 * max(up, down))
+    rej = 60.0
+    L = math.ceil((rej - 8) / (28.714 * stop / 10))
+    t = np.arange(-L, L + 1)
+    ideal = 2 * up * stop * np.sinc(2 * stop * t)
+    beta = 0.1102 * (rej - 8.7)
+    h = np.kaiser(2 * L + 1, beta) * ideal
+    return h / np.sum(h) * up
+
+
+def stoi_window():
+    """hanning(258)[1:-1]: the 256-point window of STOI's frames."""
+    return np.hanning(258)[1:-1]
+
+
+def _twiddle(n_fft):
+    k = np.arange(n_fft // 2 + 1, dtype=np.float64)
+    ang = -2.0 * math.pi * k / n_fft
+    return np.stack([np.cos(ang), np.sin(ang)], 1)
+
+
+_TABLES = {}
+
+
+def _tables(device):
+    if device not in _TABLES:
+        tab, w = crit_band_table()
+        put = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(device)
+        _TABLES[device] = dict(window=put(frame_window()), band_tab=put(tab), band_w=put(w), tw1024=put(_twiddle(1024)),
+                               taps=put(resample_taps()), stoi_win=put(stoi_window()), tw512=put(_twiddle(512)),
+                               bands=put(third_octave_table()))
+    return _TABLES[device]
+
+
+def _as_int16(x, what):
+    """One clip as a 1-D int16 tensor (same device); floats must hold integers in [-32768, 32767]."""
+    t = x.detach() if isinstance(x, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(np.asarray(x)))
+    t = t.reshape(-1)
+    if t.dtype == torch.int16:
+        return t
+    if t.dtype.is_floating_point:
+        bad = ~torch.isfinite(t) | (t != torch.round(t))
+    else:
+        bad = torch.zeros_like(t, dtype=torch.bool)
+    bad |= (t < -32768) | (t > 32767)
+    if bool(bad.any()):
+        raise ValueError(f"{what}: samples must be int16 values")
+    return t.to(torch.int16)
+
+
+class Batch:
+    """A checked ragged batch: flat int16 buffers of both signals on the GPU and host offsets / lengths."""
+
+    def __init__(self, clean, processed, rate, min_len=WIN):
+        if isinstance(clean, (np.ndarray, torch.Tensor)) and clean.ndim == 1:
+            clean, processed = [clean], [processed]
+        clean, processed = list(clean), list(processed)
+        if len(clean) == 0:
+            raise ValueError("speech metrics: empty batch")
+        if len(clean) != len(processed):
+            raise ValueError("speech metrics: %d clean clips but %d processed" % (len(clean), len(processed)))
+        cs = [_as_int16(c, "clean") for c in clean]
+        ps = [_as_int16(p, "processed") for p in processed]
+        lengths = []
+        for i, (c, p) in enumerate(zip(cs, ps)):
+            if c.numel() != p.numel():
+                raise ValueError("speech metrics: clip %d: clean has %d samples, processed %d" % (i, c.numel(), p.numel()))
+            if c.numel() < min_len:
+                raise ValueError("speech metrics: clip %d has %d samples, fewer than one %d-sample window"
+                                 % (i, c.numel(), min_len))
+            lengths.append(c.numel())
+        if len(cs) > 65535:
+            raise ValueError("speech metrics: at most 65535 clips per batch")
+        self.rate = rate
+        self.lengths = np.array(lengths, np.int64)
+        self.offsets = np.concatenate([[0], np.cumsum(self.lengths)[:-1]]).astype(np.int64)
+        self.n_clips = len(cs)
+        self._cs, self._ps = cs, ps
+
+    def upload(self):
+        if not torch.cuda.is_available():
+            raise RuntimeError("speech metrics run only on a ROCm GPU; there is no CPU fallback")
+        dev = torch.device("cuda", torch.cuda.current_device())
+        self.device = dev
+        self.clean = torch.cat([c.to(dev) for c in self._cs])
+        self.processed = torch.cat([p.to(dev) for p in self._ps])
+        return self
+
+    @staticmethod
+    def hp(a):
+        """a host int64 array as a pointer argument"""
+        return a.ctypes.data_as(ctypes.c_void_p)
+
+
+def frame_counts(lengths):
+    return np.maximum((np.asarray(lengths, np.int64) - WIN) // HOP, 0)
+
+
+def _check_rate(rate, want):
+    if rate not in want:
+        raise ValueError("speech metrics: rate %r Hz is not supported (%s)" % (rate, ", ".join(map(str, want))))
+
+
+def _frames(b):
+    """Per-frame segSNR, LLR and WSS of an uploaded batch (f64, clip i at frame_off[i]) and the frame offsets."""
+    L = hip.lib()
+    t = _tables(b.device)
+    nf = frame_counts(b.lengths)
+    total = int(nf.sum())
+    out = torch.empty((3, max(total, 1)), dtype=torch.float64, device=b.device)
+    ws = torch.empty(L.cum_metrics_workspace_bytes(b.n_clips, total), dtype=torch.uint8, device=b.device)
+    hip.check(L.cum_metrics_frames(hip.ptr(b.clean), hip.ptr(b.processed), b.clean.numel(), b.hp(b.offsets),
+                                   b.hp(b.lengths), b.n_clips, b.rate, hip.ptr(t["window"]), hip.ptr(t["band_tab"]),
+                                   hip.ptr(t["band_w"]), hip.ptr(t["tw1024"]), hip.ptr(ws), ws.numel(),
+                                   hip.ptr(out[0]), hip.ptr(out[1]), hip.ptr(out[2]), total, hip.stream_ptr()))
+    return out[:, :total], np.concatenate([[0], np.cumsum(nf)]), ws
+
+
+def _reduce(b, values, mode, ws):
+    out = torch.empty(b.n_clips, dtype=torch.float64, device=b.device)
+    hip.check(hip.lib().cum_metrics_clip_reduce(hip.ptr(values), b.hp(b.lengths), b.n_clips, mode, hip.ptr(ws),
+                                                ws.numel(), hip.ptr(out), hip.stream_ptr()))
+    return out
+
+
+def _stoi(b):
+    L = hip.lib()
+    t = _tables(b.device)
+    nbytes = L.cum_metrics_stoi_workspace_bytes(b.hp(b.lengths), b.n_clips, b.rate)
+    ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
+    out = torch.empty(b.n_clips, dtype=torch.float64, device=b.device)
+    hip.check(L.cum_metrics_stoi(hip.ptr(b.clean), hip.ptr(b.processed), b.clean.numel(), b.hp(b.offsets),
+                                 b.hp(b.lengths), b.n_clips, b.rate, hip.ptr(t["taps"]), t["taps"].numel(),
+                                 hip.ptr(t["stoi_win"]), hip.ptr(t["tw512"]), hip.ptr(t["bands"]), hip.ptr(ws),
+                                 ws.numel(), hip.ptr(out), hip.stream_ptr()))
+    return out
+
+
+METRICS = ("wss_dist", "llr_mean", "segSNR", "stoi")
+
+
+def frame_metrics(clean, processed, rate=FRAME_RATE):
+    """Per-frame ``segSNR``, ``llr`` and ``wss`` of every clip: a dict of lists of f64 tensors, one per clip."""
+    _check_rate(rate, (FRAME_RATE,))
+    b = Batch(clean, processed, rate).upload()
+    out, off, _ = _frames(b)
+    split = lambda v: [v[off[i]:off[i + 1]] for i in range(b.n_clips)]
+    return {"segSNR": split(out[0]), "llr": split(out[1]), "wss": split(out[2])}
+
+
+def speech_metrics(clean, processed, rate=FRAME_RATE, metrics=METRICS):
+    """Per-clip metrics of a ragged batch: a dict name -> f64 tensor of one value per clip, for each name in ``metrics``
+    (``wss_dist``, ``llr_mean``, ``segSNR``: eval_waveform's recipe at 16 kHz; ``stoi`` at 16 or 10 kHz).
+
+    ``clean`` / ``processed``: lists of 1-D arrays or tensors of int16 values, pairwise of equal length, each at least
+    480 samples.  Raises ValueError before any launch for an empty batch, unequal lengths, a short clip or a rate the
+    requested metrics do not support."""
+    metrics = tuple(metrics)
+    for m in metrics:
+        if m not in METRICS:
+            raise ValueError("speech metrics: unknown metric %r (have %s)" % (m, ", ".join(METRICS)))
+    frame_names = [m for m in metrics if m != "stoi"]
+    _check_rate(rate, (FRAME_RATE,) if frame_names else STOI_RATES)
+    b = Batch(clean, processed, rate).upload()
+    res = {}
+    if frame_names:
+        vals, _, ws = _frames(b)
+        if "segSNR" in metrics:
+            res["segSNR"] = _reduce(b, vals[0], 0, ws)
+        if "llr_mean" in metrics:
+            res["llr_mean"] = _reduce(b, vals[1], 2, ws)
+        if "wss_dist" in metrics:
+            res["wss_dist"] = _reduce(b, vals[2], 1, ws)
+    if "stoi" in metrics:
+        res["stoi"] = _stoi(b)
+    return {m: res[m] for m in metrics}
+
+
+def stoi(clean, processed, fs, extended=False):
+    """STOI of one clip, ``pystoi.stoi(x, y, fs_sig, extended=False)``'s signature; fs 16000 or 10000."""
+    if extended:
+        raise NotImplementedError("extended STOI is not implemented")
+    _check_rate(fs, STOI_RATES)
+    b = Batch([clean], [processed], fs, min_len=1).upload()
+    return float(_stoi(b)[0])

@@ -1,0 +1,114 @@
+"""The reference's evaluation functions (src/util/python_eval.py) with its signatures, numpy in and numpy out, computed
+on the GPU by cleanumamba_amd.util.metrics.
+
+Deviations, by design:
+  * ``snr`` returns the overall SNR computed in float.  The reference squares the int16 arrays in int16 arithmetic,
+    which wraps; ``eval_waveform`` never reports that value.
+  * PESQ is not reimplemented.  When the ``pesq`` package imports, it is called on the CPU as the reference calls it;
+    otherwise ``pesq_wb``, ``pesq_nb`` and the composites built on PESQ (CSIG, CBAK, COVL) are NaN, with one warning.
+  * The frame metrics exist at 16 kHz only (the reference's eval_waveform calls them at 16 kHz whatever the rate).
+"""
+import math
+import warnings
+from collections import defaultdict
+
+import numpy as np
+
+from . import metrics as M
+
+_PESQ_WARNED = False
+
+
+def _pesq_fn():
+    global _PESQ_WARNED
+    try:
+        from pesq import pesq
+        return pesq
+    except ImportError:
+        if not _PESQ_WARNED:
+            warnings.warn("pesq is not installed: pesq_wb, pesq_nb, CSIG, CBAK and COVL are NaN")
+            _PESQ_WARNED = True
+        return None
+
+
+def _same_length(a, b, msg):
+    if np.size(a) != np.size(b):
+        raise ValueError(msg)
+
+
+def _frames(clean_speech, processed_speech, sample_rate, name):
+    if sample_rate != M.FRAME_RATE:
+        raise ValueError("%s: only 16 kHz is supported (got %r)" % (name, sample_rate))
+    return M.frame_metrics([np.asarray(clean_speech)], [np.asarray(processed_speech)], sample_rate)
+
+
+def wss(clean_speech, processed_speech, sample_rate):
+    """Per-frame weighted spectral slope distortion (python_eval.py:139)."""
+    _same_length(clean_speech, processed_speech, "Files must have same length.")
+    return _frames(clean_speech, processed_speech, sample_rate, "wss")["wss"][0].cpu().numpy()
+
+
+def llr(clean_speech, processed_speech, sample_rate):
+    """Per-frame log-likelihood ratio of order-16 LPC (python_eval.py:336); NaN where a frame is all zeros."""
+    _same_length(clean_speech, processed_speech, "Both Speech Files must be same length.")
+    return _frames(clean_speech, processed_speech, sample_rate, "llr")["llr"][0].cpu().numpy()
+
+
+def snr(clean_speech, processed_speech, sample_rate):
+    """(overall SNR, per-frame segmental SNR clamped to [-10, 35] dB) (python_eval.py:409).  The overall SNR is computed
+    in float (the reference's int16 arithmetic wraps)."""
+    _same_length(clean_speech, processed_speech, "Both Speech Files must be same length.")
+    c = np.asarray(clean_speech, np.float64)
+    p = np.asarray(processed_speech, np.float64)
+    overall = 10 * np.log10(np.sum(np.square(c)) / np.sum(np.square(c - p)))
+    seg = _frames(clean_speech, processed_speech, sample_rate, "snr")["segSNR"][0].cpu().numpy()
+    return overall, seg
+
+
+def composites(pesq_mos, llr_mean, wss_dist, seg_snr):
+    """CSIG, CBAK, COVL (Hu & Loizou 2008) limited to [1, 5]; NaN when PESQ is NaN."""
+    if math.isnan(pesq_mos):
+        return float("nan"), float("nan"), float("nan")
+    lim = lambda v: min(5, max(1, v))
+    csig = lim(3.093 - 1.029 * llr_mean + 0.603 * pesq_mos - 0.009 * wss_dist)
+    cbak = lim(1.634 + 0.478 * pesq_mos - 0.007 * wss_dist + 0.063 * seg_snr)
+    covl = lim(1.594 + 0.805 * pesq_mos - 0.512 * llr_mean - 0.007 * wss_dist)
+    return csig, cbak, covl
+
+
+def eval_waveforms(cleans, targets, rate):
+    """eval_waveform of every (clean, target) pair, with all clips scored in one batched call: a list of result dicts."""
+    m = M.speech_metrics(cleans, targets, M.FRAME_RATE, metrics=("wss_dist", "llr_mean", "segSNR"))
+    st = M.speech_metrics(cleans, targets, rate, metrics=("stoi",))["stoi"]
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    st = st.cpu().numpy()
+    pesq = _pesq_fn()
+    out = []
+    for i, (clean, target) in enumerate(zip(cleans, targets)):
+        clean, target = np.asarray(clean), np.asarray(target)
+        length = target.shape[-1]
+        wss_dist, llr_mean, seg = float(m["wss_dist"][i]), float(m["llr_mean"][i]), float(m["segSNR"][i])
+        if pesq is not None:
+            pesq_wb, pesq_nb = pesq(16000, clean, target, "wb"), pesq(16000, clean, target, "nb")
+        else:
+            pesq_wb = pesq_nb = float("nan")
+        csig, cbak, covl = composites(pesq_wb, llr_mean, wss_dist, seg)
+        result = defaultdict(int)
+        result["pesq_wb"] += pesq_wb * length
+        result["pesq_nb"] += pesq_nb * length
+        result["stoi"] += float(st[i]) * length
+        result["CSIG"] += csig * length
+        result["CBAK"] += cbak * length
+        result["COVL"] += covl * length
+        result["wss_dist"] += wss_dist * length
+        result["segSNR"] += seg * length
+        result["llr_mean"] += llr_mean * length
+        result["count"] += 1 * length
+        out.append(result)
+    return out
+
+
+def eval_waveform(clean, target_wav, rate):
+    """Length-weighted metrics of one clip (python_eval.py:81): pesq_wb, pesq_nb, stoi, CSIG, CBAK, COVL, wss_dist,
+    segSNR, llr_mean and count.  The frame metrics run at 16 kHz, STOI at ``rate``, as in the reference."""
+    return eval_waveforms([clean], [target_wav], rate)[0]

@@ -678,6 +678,44 @@ int cum_ssd_step(int32_t streams, int32_t d_ssm, int32_t nheads, int32_t dstate,
                  const float *dt_bias, const float *A_log, const float *D, const float *norm_w, float *ssm_state,
                  float *out, int64_t out_ld, void *stream);
 
+/* ---- speech-quality metrics of a ragged batch of int16 clips (src/util/python_eval.py, pystoi.stoi) ----------------
+ * clean / processed: flat int16 buffers of n_samples, 16-byte aligned; clip i is [offsets[i], offsets[i] + lengths[i])
+ * of both.  offsets and lengths are HOST arrays: every entry checks them before any launch (a clip outside the buffer, a
+ * clip shorter than one window, an unsupported rate, an empty batch -> CUM_EINVAL) and uploads the clip table to the
+ * head of `workspace` on `stream`, waiting for that copy (one stream synchronise per call).  All sums run in a fixed order within a clip's own workgroups: bit-reproducible, and
+ * a clip's result does not depend on the rest of its batch. */
+/* frames per clip of the 16 kHz frame metrics: (len - 480) / 120, the reference's int(len / 120 - 480 / 120); -1 below 480 */
+int64_t cum_metrics_frame_count(int64_t len);
+/* frames kept by the trimmed mean: Python's round(0.95 * n_frames), half to even (python_eval.py:88, :93) */
+int64_t cum_metrics_reduce_keep(int64_t n_frames);
+/* workspace of cum_metrics_frames and cum_metrics_clip_reduce */
+int64_t cum_metrics_workspace_bytes(int64_t n_clips, int64_t n_frames_total);
+/* cum_metrics_frames <- python_eval.py:409 snr (segmental part), :336 llr + :380 lpcoeff, :139 wss at 16 kHz.
+ * Frame f of clip i goes to index frame_off(i) + f of seg_snr / llr / wss (f64), frame_off the running sum of
+ * cum_metrics_frame_count; n_frames_total is their sum.  Tables (device): window[480] = 0.5 (1 - cos(2 pi n / 481)),
+ * n = 1..480; band_tab[25][3] = (first bin, bin count, offset into band_w) of each critical band's truncated Gaussian;
+ * tw[513] = e^{-2 pi i m / 1024} as (re, im) f64. */
+int cum_metrics_frames(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                       const int64_t *lengths, int64_t n_clips, int32_t rate, const double *window,
+                       const int32_t *band_tab, const double *band_w, const double *tw, void *workspace,
+                       int64_t workspace_bytes, double *seg_snr, double *llr, double *wss, int64_t n_frames_total,
+                       void *stream);
+/* cum_metrics_clip_reduce <- eval_waveform's per-clip reduces (python_eval.py:86-104): out[i] over clip i's frame values
+ * (laid out as cum_metrics_frames writes them).  mode 0: mean (segSNR); 1: mean of the round(0.95 n) lowest, NaN
+ * sorting last (wss_dist); 2: as 1 with the NaNs of that slice dropped (llr_mean).  An empty selection gives NaN. */
+int cum_metrics_clip_reduce(const double *values, const int64_t *lengths, int64_t n_clips, int32_t mode, void *workspace,
+                            int64_t workspace_bytes, double *out, void *stream);
+/* workspace of cum_metrics_stoi (bytes); -1 for bad arguments */
+int64_t cum_metrics_stoi_workspace_bytes(const int64_t *lengths, int64_t n_clips, int32_t rate);
+/* cum_metrics_stoi <- pystoi.stoi(x, y, rate, extended=False) as python_eval.py:123 calls it; rate 16000 or 10000.
+ * taps[n_taps]: the 16 k -> 10 k polyphase filter of pystoi's resample_oct, normalised and scaled by up = 5 (ignored at
+ * 10 kHz); window[256] = hanning(258)[1:-1]; tw[257] = e^{-2 pi i m / 512} (f64 re, im); bands[15][2] = [first, end) bin
+ * of each one-third-octave band.  out[i]: STOI of clip i (1e-5 below 30 STFT frames, as pystoi). */
+int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                     const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
+                     const double *window, const double *tw, const int32_t *bands, void *workspace,
+                     int64_t workspace_bytes, double *out, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
