@@ -254,12 +254,17 @@ __global__ __launch_bounds__(NW * 64) void scan_bwd_kernel(const ScanParams p) {
   };
   // checkpoint of this wave's slice, straight into slot order: slot k = row k ^ hm of the (b, c, h, w, g) block, column
   // pi(lane) (scan_common.h, wide layout) -- eight 4-byte loads, each 8 whole 32-byte sectors per wave; a wave-uniform
-  // base + one 32-bit offset per lane, the row selected by ONE xor (row and column bits do not overlap)
+  // base + one 32-bit offset per lane, the row selected by ONE xor (row and column bits do not overlap).  The forward
+  // writes no checkpoint for the pad lanes of the last group (d >= dim): what is there is whatever the buffer held, and
+  // it is selected away, not multiplied away -- dC sums dy * x over the group's lanes, and 0 * NaN is NaN
   const int ck_o = hm * 64 + ckpt_pi(lane);
   auto ckpt_load_slots = [&](int c, int h, f2 (&x)[NP2]) {
     const float *q = p.ckpt_in + ckpt_wide_block(b, nchunks, c, h, NW, w, Dm, g);
 #pragma unroll
-    for (int k = 0; k < NS; ++k) x[k / 2][k % 2] = q[ck_o ^ (k * 64)];
+    for (int k = 0; k < NS; ++k) {
+      const float v = q[ck_o ^ (k * 64)];
+      x[k / 2][k % 2] = dok ? v : 0.f;
+    }
   };
   load_rows(nchunks - 1);
 #ifdef CUM_SCAN_PROBE
