@@ -17,7 +17,7 @@ namespace cum {
 
 // state vector (f32), shared by the three kernels and read by the host side only for logging
 enum { ST_NORM = 0, ST_MULT = 1, ST_FOUND_INF = 2, ST_SCALE = 3, ST_TRACKER = 4, ST_STEP = 5, ST_BC1 = 6,
-       ST_BC2_SQRT = 7, ST_LR = 8, ST_SKIPPED = 9 };
+       ST_BC2_SQRT = 7, ST_LR = 8, ST_SKIPPED = 9, ST_GRAD_SCALE = 10 };
 
 __global__ __launch_bounds__(256) void optim_sumsq_kernel(const float *__restrict__ g, int64_t n, float *__restrict__ partials) {
   __shared__ float red[4];
@@ -80,6 +80,7 @@ __global__ __launch_bounds__(256) void optim_prepare_kernel(const PrepareArgs a)
   }
   st[ST_NORM] = norm;
   st[ST_MULT] = coef / scale;
+  st[ST_GRAD_SCALE] = scale;                       // what the step's gradients carry (the update below may change [3])
   st[ST_FOUND_INF] = bad ? 1.f : 0.f;
   if (bad) {
     st[ST_SKIPPED] += 1.f;

@@ -61,6 +61,19 @@ class GemmDesc(ctypes.Structure):
                 ("gate_only", c_i32), ("ldy", c_i64), ("mask_bits", c_i32), ("allow_split_k", c_i32)]
 
 
+class PruneImpDesc(ctypes.Structure):
+    """cum_prune_imp_desc (include/cleanumamba_hip.h): one module's channels for cum_prune_importance."""
+    _fields_ = [("w", ctypes.c_void_p), ("g", ctypes.c_void_p), ("numel", c_i64), ("off", c_i64), ("ch_stride", c_i64),
+                ("head_stride", c_i64), ("s0", c_i64), ("s1", c_i64), ("channels", c_i32), ("heads", c_i32),
+                ("n0", c_i32), ("n1", c_i32), ("out", c_i64), ("lanes_on_channels", c_i32), ("pad_", c_i32)]
+
+
+class PruneGatherDesc(ctypes.Structure):
+    """cum_prune_gather_desc (include/cleanumamba_hip.h): one parameter's move from the old flat layout to the new."""
+    _fields_ = [("src", c_i64), ("dst", c_i64), ("n_new", c_i64), ("ndim", c_i32), ("old_dims", c_i32 * 3),
+                ("new_dims", c_i32 * 3), ("pad_", c_i32), ("keep", c_i64 * 3)]
+
+
 CUM_F32, CUM_BF16, CUM_F16 = 0, 1, 2
 HALF_TYPES = (torch.bfloat16, torch.float16)          # 16-bit element types the kernels read / write directly
 IO_TYPES = (torch.float32,) + HALF_TYPES
@@ -171,6 +184,11 @@ SIGNATURES = {
     "cum_metrics_clip_reduce": (c_i32, [_P, _P, c_i64, c_i32, _P, c_i64, _P, _P]),
     "cum_metrics_stoi_workspace_bytes": (c_i64, [_P, c_i64, c_i32]),
     "cum_metrics_stoi": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, c_i32, _P, c_i32] + [_P] * 4 + [c_i64, _P, _P]),
+    "cum_prune_importance_workspace_bytes": (c_i64, [ctypes.POINTER(PruneImpDesc), c_i32]),
+    "cum_prune_importance": (c_i32, [ctypes.POINTER(PruneImpDesc), c_i32, _P, _P, c_i64, _P, c_i64, _P]),
+    "cum_prune_gather_workspace_bytes": (c_i64, [c_i32, c_i64]),
+    "cum_prune_gather": (c_i32, [ctypes.POINTER(PruneGatherDesc), c_i32, _P, c_i64] + [_P] * 4 + [c_i64] + [_P] * 4
+                         + [c_i64, _P, c_i64, _P]),
 }
 
 _lib = None

@@ -114,6 +114,23 @@ class StreamPool:
         self._pend[:] = 0
         self._frames[:] = 0
 
+    def relayout(self):
+        """The model's widths changed (pruning) while no slot is open: take the new plan and size the state blocks to it.
+        A model the one-launch hop no longer runs leaves the pool stale (its next call raises)."""
+        if self._open.any():
+            raise RuntimeError("stream pool: close the slots before the model's widths change")
+        try:
+            plan = hopplan.HopPlan(self.model)
+        except ValueError:
+            self._stale = True
+            return
+        self.plan, self._wv, self._stale = plan, self.model._weights_version(), False
+        self.hop, self.frame_len = plan.hop, plan.frame_len
+        self.state = torch.zeros(self.capacity, plan.state_stride, dtype=torch.float32, device=self.device)
+        self.hist = torch.zeros(self.capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32,
+                                device=self.device)
+        self.reset()
+
     def invalidate_packed_weights(self):
         """Re-pack the weight blob on the next call (``CleanUMamba.invalidate_packed_weights`` calls this)."""
         self._stale = True

@@ -13,6 +13,7 @@ second one, so that
 The host only writes the learning rate into the device-side state vector before each step.
 """
 import ctypes
+import math
 import weakref
 
 import torch
@@ -20,7 +21,7 @@ import torch
 from .. import hip
 
 # layout of the device-side state vector (csrc/optim.hip)
-ST_NORM, ST_MULT, ST_FOUND_INF, ST_SCALE, ST_TRACKER, ST_STEP, ST_BC1, ST_BC2_SQRT, ST_LR, ST_SKIPPED = range(10)
+ST_NORM, ST_MULT, ST_FOUND_INF, ST_SCALE, ST_TRACKER, ST_STEP, ST_BC1, ST_BC2_SQRT, ST_LR, ST_SKIPPED, ST_GRAD_SCALE = range(11)
 
 
 _SINKS = {}          # parameter data_ptr -> weakref(FlatParams) that owns it
@@ -89,6 +90,49 @@ class FlatParams:
         ref = weakref.ref(self)
         for i, p in enumerate(self.params):
             p.register_hook(self._pre_accumulate(ref, i))
+        ptrs = [p.data_ptr() for p in self.params]
+        for ptr in ptrs:
+            _SINKS[ptr] = ref
+        weakref.finalize(self, _forget, ptrs, ref)
+
+    # weak references set by the FlatAdam whose moments and the GradBuckets whose slices follow this storage (pruning,
+    # pruning/device.py, rebuilds them with it)
+    optimizer = None
+    buckets = None
+
+    def __getstate__(self):
+        # (the weak back-references cannot be pickled: a saved model -- torch.save(net) with net.grad_buckets -- drops them)
+        state = self.__dict__.copy()
+        state.pop("optimizer", None)
+        state.pop("buckets", None)
+        return state
+
+    def replace_storage(self, data, grad, shapes):
+        """Take over new flat buffers that already hold every parameter and gradient in the FlatParams layout (same
+        order, 16-byte aligned starts, zero padding) with the new ``shapes`` (pruning, pruning/device.py): every
+        ``p.data`` / ``p.grad`` becomes a view of them; the Parameter objects, their hooks and the lazy-zeroing state
+        stay."""
+        offsets, off = [], 0
+        for s in shapes:
+            offsets.append(off)
+            off += (math.prod(s) + self.ALIGN - 1) // self.ALIGN * self.ALIGN
+        if off != data.numel() or off != grad.numel():
+            raise ValueError("replace_storage: buffer size does not match the layout")
+        ref = weakref.ref(self)
+        for p in self.params:
+            if _SINKS.get(p.data_ptr()) is ref:
+                del _SINKS[p.data_ptr()]
+        self.data, self.grad, self.offsets, self.numel = data, grad, offsets, off
+        self.grad_views = []
+        with torch.no_grad():
+            for p, o, s in zip(self.params, offsets, shapes):
+                n = math.prod(s)
+                p.grad = None
+                p.data = data[o:o + n].view(s)
+                gview = grad[o:o + n].view(s)
+                p.grad = gview
+                self.grad_views.append(gview)
+        self.by_ptr = {p.data_ptr(): i for i, p in enumerate(self.params)}
         ptrs = [p.data_ptr() for p in self.params]
         for ptr in ptrs:
             _SINKS[ptr] = ref
@@ -238,10 +282,17 @@ class FlatAdam:
         self.partials = torch.zeros(self.nparts, dtype=torch.float32, device=dev)
         self._lr_written = lr
         self._listeners = []
+        flat.optimizer = weakref.ref(self)
 
     # ---- loss scaling (device scalars: no host sync)
     def scale_loss(self, loss):
+        self.grads_scale_slot = ST_SCALE
         return loss * self.state_vec[ST_SCALE] if self.loss_scaling else loss
+
+    # Slot of state_vec holding the scale the gradients in the flat buffer carry: the current scale while they are being
+    # accumulated (scale_loss), the one the last step used once a step has run (its update may have changed the current
+    # one; cum_optim_prepare writes ST_GRAD_SCALE).  Read by the pruning importances (pruning/device.py).
+    grads_scale_slot = ST_SCALE
 
     @property
     def loss_scale(self):
@@ -279,6 +330,7 @@ class FlatAdam:
                                          hip.ptr(self.exp_avg_sq), f.numel, hip.ptr(self.state_vec), g["betas"][0],
                                          g["betas"][1], g["eps"], g["weight_decay"], st))
         f.bump_versions()
+        self.grads_scale_slot = ST_GRAD_SCALE
 
     # ---- checkpoint format of torch.optim.Adam (src/training/train.py:183-186, 367: optimizer_state_dict)
     def state_dict(self):

@@ -19,6 +19,7 @@ collective large enough to be link-bandwidth bound rather than latency bound whi
 still giving ~5 overlappable pieces for the 165 MB of E8 gradients.
 """
 import os
+import weakref
 
 import torch
 import torch.distributed as dist
@@ -63,17 +64,13 @@ class GradBuckets:
         # backward, whole-buffer all-reduce between the two captured graphs) against the real backend on a one-GPU box
         self.exchanging = self.world > 1 or (self.distributed and os.environ.get("CUM_EXCHANGE_ALONE") == "1")
         self.flat = flat if flat is not None else FlatParams(module)
+        self.flat.buckets = weakref.ref(self)
         self.params = self.flat.params
         self.require_sync = True
-        self.buckets = []          # [flat gradient slice, [params], pending count]
-        self.where = {}            # id(param) -> (bucket index, gradient view)
+        self.bucket_bytes = bucket_bytes
         self.handles = []
         self._armed = False
-        for start, end, members in self.flat.slices(bucket_bytes):
-            plist = [self.params[i] for i in members]
-            for i in members:
-                self.where[id(self.params[i])] = (len(self.buckets), self.flat.grad_views[i])
-            self.buckets.append([self.flat.grad[start:end], plist, len(plist)])
+        self.rebuild()
         for p in self.params:
             p.register_post_accumulate_grad_hook(self._hook)
         self.flat.on_write = self._written
@@ -81,6 +78,16 @@ class GradBuckets:
         # an exchange to overlap with (network/convstack.py EncoderStack.backward)
         self.flat.early_announce = self.exchanging
         self.flat.exchange_reads_buffer = self.exchanging        # (no lazy zero_grad under an exchange: flat_optim.py)
+
+    def rebuild(self):
+        """(Re)cut the buckets from the flat layout: at construction and after pruning replaced the flat buffers."""
+        self.buckets = []          # [flat gradient slice, [params], pending count]
+        self.where = {}            # id(param) -> (bucket index, gradient view)
+        for start, end, members in self.flat.slices(self.bucket_bytes):
+            plist = [self.params[i] for i in members]
+            for i in members:
+                self.where[id(self.params[i])] = (len(self.buckets), self.flat.grad_views[i])
+            self.buckets.append([self.flat.grad[start:end], plist, len(plist)])
 
     def _written(self, params):
         """Gradients a kernel wrote straight into the flat buffer (FlatParams.wrote): same bookkeeping as the hook."""

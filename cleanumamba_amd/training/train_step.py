@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from ..util.stft_loss import MultiResolutionSTFTLoss
+from .flat_optim import ST_GRAD_SCALE
 from ..util.util import LinearWarmupCosineDecay, loss_fn
 
 DEFAULT_OPTIM = {"n_iters": 1600000, "learning_rate": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8,
@@ -316,6 +317,7 @@ class TrainStep:
                 self.buckets.exchange_all()
                 g["optim_graph"].replay()
             self.buckets.flat.bump_versions()             # the replay moved the parameters behind autograd's back
+            self.optimizer.grads_scale_slot = ST_GRAD_SCALE   # the replay's step may have grown the scale its gradients carry
             loss, grad_norm = g["loss"].clone(), g["norm"].clone()
         else:
             loss, grad_norm = self._body(clean_audio, noisy_audio)

@@ -617,7 +617,8 @@ int cum_unframe_rows(int32_t dtype, const void *rows, int32_t batch, int64_t len
  * the caller before every step):
  *   [0] total gradient norm (unscaled)  [1] multiplier applied to g (clip coefficient / loss scale)  [2] found inf/nan
  *   [3] loss scale  [4] growth tracker  [5] Adam step count  [6] 1 - beta1^t  [7] sqrt(1 - beta2^t)  [8] learning rate
- *   [9] skipped steps
+ *   [9] skipped steps  [10] the loss scale the gradients of the last step carried (written by cum_optim_prepare
+ *   before it updates [3]: what a reader of those gradients divides by after the step)
  * Sequence per optimizer step: cum_optim_sumsq (partials: cum_optim_sumsq_parts(n) f32) -> cum_optim_prepare ->
  * cum_optim_adam.  Nothing returns to the host; with found inf/nan the Adam launch leaves p, m, v untouched and the
  * loss scale backs off (torch.amp.GradScaler semantics: growth x `growth` after `growth_interval` clean steps).
@@ -715,6 +716,51 @@ int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, int64_t n_s
                      const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
                      const double *window, const double *tw, const int32_t *bands, void *workspace,
                      int64_t workspace_bytes, double *out, void *stream);
+
+/* ---- structured channel pruning (cleanumamba_amd/pruning/; reference src/pruning/pruninggroup.py, util.py:328-349) --
+ * Both entries take HOST descriptor tables, check every descriptor before any launch (CUM_EINVAL, nothing launched),
+ * upload the tables to the head of `workspace` on `stream` and wait for that copy (one stream synchronise per call).
+ *
+ * cum_prune_importance <- PruningModule.channel_importances for every descriptor in one launch.  Channel c of
+ * descriptor d covers the elements
+ *   off + c ch_stride + h head_stride + i0 s0 + i1 s1,   h < heads, i0 < n0, i1 < n1
+ * of w and g (both laid out alike, numel elements; g NULL: no gradient, its sums are 0).  out: n_out rows of 5 f32,
+ * row d.out + c = [sum w^2, sum g'^2, sum |w g'|, sum (w g')^2, |sum w g'|] with g' = g / scale[0] (scale: NULL = 1, else
+ * one f32 in device memory: the loss scale the gradients carry).  Sums in f64, one wave per channel
+ * (lanes_on_channels = 0: lanes over the channel's elements) or per 64 channels (1: lane = channel) in a fixed order:
+ * bitwise reproducible.  A non-finite gradient gives non-finite sums (the caller checks). */
+typedef struct {
+  const float *w, *g;
+  int64_t numel;
+  int64_t off, ch_stride, head_stride, s0, s1;
+  int32_t channels, heads, n0, n1;
+  int64_t out;
+  int32_t lanes_on_channels, pad_;
+} cum_prune_imp_desc;
+int64_t cum_prune_importance_workspace_bytes(const cum_prune_imp_desc *descs, int32_t n_desc);
+int cum_prune_importance(const cum_prune_imp_desc *descs, int32_t n_desc, const float *scale, float *out, int64_t n_out,
+                         void *workspace, int64_t workspace_bytes, void *stream);
+/* cum_prune_gather <- prune_parameter_and_grad on flat buffers: for every parameter d, the row-major (ndim <= 3) tensor
+ * of old_dims at element d.src of the four old buffers (parameters, gradients, exp_avg, exp_avg_sq; src_numel each)
+ * -> its kept part, new_dims, at element d.dst of the four new buffers (dst_numel each):
+ *   new[i0][i1][i2] = old[K0(i0)][K1(i1)][K2(i2)],  Kk = keep[d.keep[k] ...] (strictly increasing), or the identity
+ *   when d.keep[k] < 0 (new_dims[k] == old_dims[k]).
+ * d.dst multiple of 4 (16-byte aligned starts), destinations in increasing order and disjoint; the alignment padding
+ * after each new parameter (up to the next multiple of 4) is written as zeros.  n_new = product of new_dims.  The four
+ * moment pointers (src_m, src_v, dst_m, dst_v) are all NULL when there are no Adam moments to move: then only parameters
+ * and gradients are gathered.  Plain copies: bit-exact. */
+typedef struct {
+  int64_t src, dst, n_new;
+  int32_t ndim;
+  int32_t old_dims[3], new_dims[3];
+  int32_t pad_;
+  int64_t keep[3];
+} cum_prune_gather_desc;
+int64_t cum_prune_gather_workspace_bytes(int32_t n_desc, int64_t n_keep);
+int cum_prune_gather(const cum_prune_gather_desc *descs, int32_t n_desc, const int32_t *keep, int64_t n_keep,
+                     const float *src_p, const float *src_g, const float *src_m, const float *src_v, int64_t src_numel,
+                     float *dst_p, float *dst_g, float *dst_m, float *dst_v, int64_t dst_numel, void *workspace,
+                     int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
