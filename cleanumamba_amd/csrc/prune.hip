@@ -11,10 +11,17 @@
 //                            (training/flat_optim.py): one launch moves the kept elements of every parameter from the old
 //                            layout into the new one, in all four buffers, bit-exact.  Kept indices come as one list per
 //                            dimension of a parameter, not as a per-element table.
-// Both are memory-bound.
+//   cum_prune_mask        <- the trial prune of the reference's layer-wise calibration
+//                            (src/pruning/layerwise_calibration.py:120-135: deepcopy + group.prune + forward) done in
+//                            place: the elements a prune would remove are saved to a compact buffer and zeroed, and
+//                            written back bit-exact after the trial forward.  Selected rows come as a device list of
+//                            indices per descriptor, so any channel set works.
+// All are memory-bound.
 #include <stdio.h>
 #include <string.h>
 
+#include <algorithm>
+#include <utility>
 #include <vector>
 
 #include "common.h"
@@ -203,6 +210,58 @@ __global__ __launch_bounds__(kGatherThreads) void prune_gather_kernel(const Gath
   }
 }
 
+constexpr int kMaskThreads = 256;
+constexpr int kMaskPer = 4;         // elements per thread: 1024 per workgroup
+
+struct MaskArgs {
+  const cum_prune_mask_desc *descs;
+  const int64_t *block_start;       // n_desc + 1 prefix sums of the workgroups per descriptor
+  const int64_t *save_start;        // n_desc prefix sums of the saved elements per descriptor
+  const int32_t *idx;
+  int32_t n_desc;
+  float *save;
+  int32_t restore;
+};
+
+// Element e of descriptor d (row j of its list, element (i0, i1) of that row; rows_fastest: consecutive e on
+// consecutive selected rows, for column selections) -> its offset in d.w.  save[save_start + e] holds its value.
+__global__ __launch_bounds__(kMaskThreads) void prune_mask_kernel(const MaskArgs a) {
+  int lo = 0, hi = a.n_desc - 1;
+  const int64_t b = blockIdx.x;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (a.block_start[mid] <= b) lo = mid;
+    else hi = mid - 1;
+  }
+  const cum_prune_mask_desc d = a.descs[lo];
+  const int64_t inner = (int64_t)d.n0 * d.n1;
+  const int64_t count = (int64_t)d.n_rows * inner;
+  const int64_t first = (b - a.block_start[lo]) * (int64_t)(kMaskThreads * kMaskPer);
+  float *__restrict__ save = a.save + a.save_start[lo];
+  const int32_t *__restrict__ rows = a.idx + d.first;
+#pragma unroll
+  for (int k = 0; k < kMaskPer; ++k) {
+    const int64_t e = first + (int64_t)k * kMaskThreads + threadIdx.x;
+    if (e >= count) break;
+    int64_t j, r;
+    if (d.rows_fastest) {
+      r = e / d.n_rows;
+      j = e - r * d.n_rows;
+    } else {
+      j = e / inner;
+      r = e - j * inner;
+    }
+    const int64_t i0 = r / d.n1, i1 = r - i0 * d.n1;
+    const int64_t off = (int64_t)rows[j] * d.row_stride + i0 * d.s0 + i1 * d.s1;
+    if (a.restore) {
+      d.w[off] = save[e];
+    } else {
+      save[e] = d.w[off];
+      d.w[off] = 0.f;
+    }
+  }
+}
+
 }  // namespace cum
 
 using namespace cum;
@@ -356,6 +415,79 @@ extern "C" int cum_prune_gather(const cum_prune_gather_desc *descs, int32_t n_de
     hipLaunchKernelGGL(prune_gather_kernel<4>, dim3((unsigned)start[n_desc]), dim3(kGatherThreads), 0, st, a);
   else
     hipLaunchKernelGGL(prune_gather_kernel<2>, dim3((unsigned)start[n_desc]), dim3(kGatherThreads), 0, st, a);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+static int64_t mask_count(const cum_prune_mask_desc &d) { return (int64_t)d.n_rows * d.n0 * d.n1; }
+
+extern "C" int64_t cum_prune_mask_save_elems(const cum_prune_mask_desc *descs, int32_t n_desc) {
+  if (!descs || n_desc <= 0) return -1;
+  int64_t n = 0;
+  for (int32_t i = 0; i < n_desc; ++i) {
+    if (descs[i].n_rows < 0 || descs[i].n0 <= 0 || descs[i].n1 <= 0) return -1;
+    n += mask_count(descs[i]);
+  }
+  return n;
+}
+
+extern "C" int64_t cum_prune_mask_workspace_bytes(int32_t n_desc, int64_t n_idx) {
+  if (n_desc <= 0 || n_idx < 0) return -1;
+  return align256((int64_t)n_desc * (int64_t)sizeof(cum_prune_mask_desc)) + 2 * align256((int64_t)(n_desc + 1) * 8) +
+         align256(n_idx * 4);
+}
+
+extern "C" int cum_prune_mask(const cum_prune_mask_desc *descs, int32_t n_desc, const int32_t *idx, int64_t n_idx,
+                              float *save, int64_t n_save, int32_t restore, void *workspace, int64_t workspace_bytes,
+                              void *stream) {
+  CUM_REQUIRE(descs && n_desc > 0, "prune_mask: empty descriptor table");
+  CUM_REQUIRE(n_idx >= 0 && (n_idx == 0 || idx), "prune_mask: null index list");
+  CUM_REQUIRE(restore == 0 || restore == 1, "prune_mask: restore must be 0 or 1");
+  std::vector<int64_t> start(n_desc + 1, 0), save_start(n_desc + 1, 0);
+  std::vector<std::pair<uintptr_t, uintptr_t>> spans;
+  for (int32_t i = 0; i < n_desc; ++i) {
+    const cum_prune_mask_desc &d = descs[i];
+    if (!d.w) return prune_fail("prune_mask: descriptor %lld has a null tensor pointer", i);
+    if (d.n0 <= 0 || d.n1 <= 0 || d.rows <= 0 || d.n_rows < 0)
+      return prune_fail("prune_mask: descriptor %lld has an empty or negative extent", i);
+    if (d.numel <= 0 || d.row_stride < 0 || d.s0 < 0 || d.s1 < 0)
+      return prune_fail("prune_mask: descriptor %lld has a bad size or a negative stride", i);
+    const int64_t last = (int64_t)(d.rows - 1) * d.row_stride + (int64_t)(d.n0 - 1) * d.s0 + (int64_t)(d.n1 - 1) * d.s1;
+    if (last >= d.numel) return prune_fail("prune_mask: descriptor %lld reaches past its tensor (element %lld)", i, last);
+    if (d.first < 0 || d.first + d.n_rows > n_idx)
+      return prune_fail("prune_mask: descriptor %lld: row list outside the index list (%lld indices)", i, n_idx);
+    for (int32_t j = 0; j < d.n_rows; ++j) {
+      const int32_t r = idx[d.first + j];
+      if (r < 0 || r >= d.rows || (j > 0 && r <= idx[d.first + j - 1]))
+        return prune_fail("prune_mask: descriptor %lld: row list not increasing within [0, rows) at position %lld", i, j);
+    }
+    spans.emplace_back((uintptr_t)d.w, (uintptr_t)(d.w + d.numel));
+    save_start[i + 1] = save_start[i] + mask_count(d);
+    start[i + 1] = start[i] + cdiv64(mask_count(d), kMaskThreads * kMaskPer);
+  }
+  // a saved value must be the original one: no element may belong to two descriptors
+  std::sort(spans.begin(), spans.end());
+  for (size_t i = 1; i < spans.size(); ++i)
+    if (spans[i].first < spans[i - 1].second)
+      return prune_fail("prune_mask: two descriptors cover overlapping memory (%lld tensors)", (long long)spans.size());
+  CUM_REQUIRE(save_start[n_desc] <= n_save, "prune_mask: save buffer too small");
+  CUM_REQUIRE(start[n_desc] < INT32_MAX, "prune_mask: too many elements");
+  if (start[n_desc] == 0) return CUM_OK;           // nothing selected
+  CUM_REQUIRE(save, "prune_mask: null save buffer");
+  CUM_REQUIRE(workspace && workspace_bytes >= cum_prune_mask_workspace_bytes(n_desc, n_idx),
+              "prune_mask: workspace too small");
+  char *ws = (char *)workspace;
+  const int64_t dbytes = align256((int64_t)n_desc * (int64_t)sizeof(cum_prune_mask_desc));
+  const int64_t sbytes = align256((int64_t)(n_desc + 1) * 8);
+  hipStream_t st = (hipStream_t)stream;
+  int rc = prune_upload("prune_mask", ws, descs, (size_t)n_desc * sizeof(cum_prune_mask_desc), st);
+  if (rc == CUM_OK) rc = prune_upload("prune_mask", ws + dbytes, start.data(), (size_t)(n_desc + 1) * 8, st);
+  if (rc == CUM_OK) rc = prune_upload("prune_mask", ws + dbytes + sbytes, save_start.data(), (size_t)(n_desc + 1) * 8, st);
+  if (rc == CUM_OK) rc = prune_upload("prune_mask", ws + dbytes + 2 * sbytes, idx, (size_t)n_idx * 4, st);
+  if (rc != CUM_OK) return rc;
+  MaskArgs a{(const cum_prune_mask_desc *)ws, (const int64_t *)(ws + dbytes), (const int64_t *)(ws + dbytes + sbytes),
+             (const int32_t *)(ws + dbytes + 2 * sbytes), n_desc, save, restore};
+  hipLaunchKernelGGL(prune_mask_kernel, dim3((unsigned)start[n_desc]), dim3(kMaskThreads), 0, st, a);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

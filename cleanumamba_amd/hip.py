@@ -74,6 +74,13 @@ class PruneGatherDesc(ctypes.Structure):
                 ("new_dims", c_i32 * 3), ("pad_", c_i32), ("keep", c_i64 * 3)]
 
 
+class PruneMaskDesc(ctypes.Structure):
+    """cum_prune_mask_desc (include/cleanumamba_hip.h): the rows of one tensor a trial prune zeroes."""
+    _fields_ = [("w", ctypes.c_void_p), ("numel", c_i64), ("row_stride", c_i64), ("s0", c_i64), ("s1", c_i64),
+                ("n0", c_i32), ("n1", c_i32), ("rows", c_i32), ("n_rows", c_i32), ("first", c_i64),
+                ("rows_fastest", c_i32), ("pad_", c_i32)]
+
+
 CUM_F32, CUM_BF16, CUM_F16 = 0, 1, 2
 HALF_TYPES = (torch.bfloat16, torch.float16)          # 16-bit element types the kernels read / write directly
 IO_TYPES = (torch.float32,) + HALF_TYPES
@@ -189,6 +196,9 @@ SIGNATURES = {
     "cum_prune_gather_workspace_bytes": (c_i64, [c_i32, c_i64]),
     "cum_prune_gather": (c_i32, [ctypes.POINTER(PruneGatherDesc), c_i32, _P, c_i64] + [_P] * 4 + [c_i64] + [_P] * 4
                          + [c_i64, _P, c_i64, _P]),
+    "cum_prune_mask_save_elems": (c_i64, [ctypes.POINTER(PruneMaskDesc), c_i32]),
+    "cum_prune_mask_workspace_bytes": (c_i64, [c_i32, c_i64]),
+    "cum_prune_mask": (c_i32, [ctypes.POINTER(PruneMaskDesc), c_i32, _P, c_i64, _P, c_i64, c_i32, _P, c_i64, _P]),
 }
 
 _lib = None

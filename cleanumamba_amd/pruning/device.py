@@ -308,14 +308,7 @@ def prune_modules(removals, optimizer=None, model=None, models=None, _after=None
         raise ValueError("prune: a FlatAdam was given but the parameters are not flat-managed by it")
     elif optimizer is not None and not isinstance(optimizer, torch.optim.Optimizer):
         raise TypeError(f"prune: unsupported optimizer {type(optimizer).__name__}")
-    for m in models:
-        if m.__dict__.get("_hop_state") is not None or m.encoder_decoder_state or m.pending.numel() > 0:
-            raise RuntimeError("prune: the model has a live stream whose state has the old widths; flush() or "
-                               "reset_stream() before pruning")
-        for pool in m.__dict__.get("_stream_pools", ()):
-            if pool.live:
-                raise RuntimeError(f"prune: a stream pool of the model has open slots {pool.live} whose state has the old "
-                                   "widths; close() them before pruning")
+    refuse_live_streams(models, "prune", "pruning")
 
     # ---- mutate
     if flat is not None:
@@ -329,6 +322,21 @@ def prune_modules(removals, optimizer=None, model=None, models=None, _after=None
     if _after is not None:
         _after()
     _drop_caches(models, _modules_touched(removals), adam)
+
+
+def refuse_live_streams(models, who, doing):
+    """Raise if a model has a live ``feed`` stream or a stream pool with open slots: their state has the current widths
+    and weights, which pruning (or a calibration trial) changes."""
+    for m in models:
+        pending = getattr(m, "pending", None)
+        if m.__dict__.get("_hop_state") is not None or getattr(m, "encoder_decoder_state", None) or \
+                (pending is not None and pending.numel() > 0):
+            raise RuntimeError(f"{who}: the model has a live stream whose state has the old widths; flush() or "
+                               f"reset_stream() before {doing}")
+        for pool in m.__dict__.get("_stream_pools", ()):
+            if pool.live:
+                raise RuntimeError(f"{who}: a stream pool of the model has open slots {pool.live} whose state has the old "
+                                   f"widths; close() them before {doing}")
 
 
 def _select(t, kd):
@@ -455,3 +463,83 @@ def _drop_caches(models, modules, adam):
     if adam is not None:
         adam.hyper_changed()                               # the TrainStep's captured graph (drop_graph)
 
+
+
+# ------------------------------------------------------------------------------------------------- in-place trial masks
+class TrialMask:
+    """The elements ``group.prune(idxs)`` would remove, zeroed in place and restored bit-exact (csrc/prune.hip
+    cum_prune_mask): one descriptor per weight / bias and pruned dimension, the removed rows as a device index list.
+    ``mask()`` saves and zeroes, ``restore()`` writes the saved values back; both bump the version counters of the
+    touched parameters, so that caches keyed on them (the pack plan's ``packed_version``, ``-exp(A_log)``) refresh.
+    The rows are ``PruningModule.removed_rows`` -- offset + h * n_channels + c -- not the rows the importance sums read
+    (offset + c * n_heads + h)."""
+
+    def __init__(self, group, idxs):
+        from .pruninggroup import _as_index_list
+        idxs = sorted(_as_index_list(idxs))
+        if len(set(idxs)) != len(idxs) or any(i < 0 or i >= group.n_channels for i in idxs):
+            raise IndexError(f"trial mask: group {group.name}: indices must be distinct and in [0, {group.n_channels})")
+        rows = {}                               # id(tensor) -> [tensor, parameter, dim, set(rows)]
+        for pm in group.modules:
+            removed = pm.removed_rows(idxs, group.n_channels)
+            for t, dim in ((pm.param(), pm.dim), (pm.bias(), 0)):
+                if t is None:
+                    continue
+                ent = rows.setdefault((id(t), dim), [t, dim, set()])
+                ent[2].update(removed)
+        self.params = []
+        descs, index = [], []
+        for t, dim, rs in rows.values():
+            rs = sorted(rs)
+            w = t.data
+            if not w.is_contiguous() or w.dtype != torch.float32:
+                raise ValueError(f"trial mask: group {group.name} needs contiguous f32 parameters")
+            d = hip.PruneMaskDesc()
+            d.w, d.numel = w.data_ptr(), w.numel()
+            d.rows = w.shape[dim] if w.dim() else 1
+            if w.dim() <= 1:
+                d.row_stride, d.n0, d.s0, d.n1, d.s1 = 1, 1, 0, 1, 0
+            elif dim == 0:
+                d.row_stride, d.n0, d.s0, d.n1, d.s1 = w.stride(0), w[0].numel(), 1, 1, 0
+            elif w.dim() == 2:
+                d.row_stride, d.n0, d.s0, d.n1, d.s1 = w.stride(1), w.shape[0], w.stride(0), 1, 0
+            else:
+                d.row_stride, d.n0, d.s0, d.n1, d.s1 = w.stride(1), w.shape[0], w.stride(0), w[0, 0].numel(), 1
+            d.first, d.n_rows = len(index), len(rs)
+            d.rows_fastest = int(dim != 0)
+            index.extend(rs)
+            descs.append(d)
+            if all(t is not p for p in self.params):
+                self.params.append(t)
+        self.device = hip.require_gpu(*[t.data for t in self.params])
+        self.n_desc = len(descs)
+        self.descs = (hip.PruneMaskDesc * self.n_desc)(*descs)
+        self.index = (ctypes.c_int32 * max(1, len(index)))(*index)
+        self.n_index = len(index)
+        lib = hip.lib()
+        self.n_save = int(lib.cum_prune_mask_save_elems(self.descs, self.n_desc))
+        wsb = int(lib.cum_prune_mask_workspace_bytes(self.n_desc, self.n_index))
+        if self.n_save < 0 or wsb < 0:
+            raise ValueError(f"trial mask: group {group.name}: bad descriptors")
+        self.save = torch.empty(max(1, self.n_save), dtype=torch.float32, device=self.device)
+        self.ws = torch.empty(max(1, wsb), dtype=torch.uint8, device=self.device)
+        self.masked = False
+
+    def _launch(self, restore):
+        lib = hip.lib()
+        with torch.cuda.device(self.device):
+            hip.check(lib.cum_prune_mask(self.descs, self.n_desc, self.index, self.n_index, hip.ptr(self.save),
+                                         self.n_save, int(restore), hip.ptr(self.ws), self.ws.numel(), hip.stream_ptr()))
+        torch._C._increment_version(self.params)
+
+    def mask(self):
+        if self.masked:
+            raise RuntimeError("trial mask: already masked")
+        self._launch(False)
+        self.masked = True
+
+    def restore(self):
+        if not self.masked:
+            raise RuntimeError("trial mask: nothing to restore")
+        self._launch(True)
+        self.masked = False

@@ -761,6 +761,26 @@ int cum_prune_gather(const cum_prune_gather_desc *descs, int32_t n_desc, const i
                      const float *src_p, const float *src_g, const float *src_m, const float *src_v, int64_t src_numel,
                      float *dst_p, float *dst_g, float *dst_m, float *dst_v, int64_t dst_numel, void *workspace,
                      int64_t workspace_bytes, void *stream);
+/* cum_prune_mask <- the trial prune of layer-wise calibration (src/pruning/layerwise_calibration.py:120-135) in place.
+ * Descriptor d covers, for every listed row r = idx[d.first + j] (j < n_rows, strictly increasing, r < rows), the
+ * elements  r row_stride + i0 s0 + i1 s1  (i0 < n0, i1 < n1)  of w (numel elements).  Saved values sit in `save`
+ * descriptor after descriptor, n_rows n0 n1 each (cum_prune_mask_save_elems in all); rows_fastest only orders them
+ * (1: consecutive values on consecutive listed rows).  restore = 0: save every covered element, then zero it;
+ * restore = 1: write the saved values back (plain copies: bit-exact).  The same descriptors and indices go to both
+ * calls.  No element may belong to two descriptors (checked: the tensors' [w, w + numel) ranges must be disjoint). */
+typedef struct {
+  float *w;
+  int64_t numel;
+  int64_t row_stride, s0, s1;
+  int32_t n0, n1;
+  int32_t rows, n_rows;
+  int64_t first;
+  int32_t rows_fastest, pad_;
+} cum_prune_mask_desc;
+int64_t cum_prune_mask_save_elems(const cum_prune_mask_desc *descs, int32_t n_desc);
+int64_t cum_prune_mask_workspace_bytes(int32_t n_desc, int64_t n_idx);
+int cum_prune_mask(const cum_prune_mask_desc *descs, int32_t n_desc, const int32_t *idx, int64_t n_idx, float *save,
+                   int64_t n_save, int32_t restore, void *workspace, int64_t workspace_bytes, void *stream);
 
 #ifdef __cplusplus
 }
