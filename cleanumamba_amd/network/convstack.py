@@ -18,6 +18,7 @@ transposed conv single GEMMs over the flat buffer:
 import ctypes
 import os
 
+import numpy as np
 import torch
 
 from .. import hip
@@ -106,23 +107,14 @@ class small_m_gemms:
         _SPLIT_K_OK = self.prev
 
 
-def wgrad(dZ, z_off, ldz, N, X, x_off, ldx, K, M, want_bias=True, out=None, out_w=None, out_b=None, scatter=None):
+def wgrad(dZ, z_off, ldz, N, X, x_off, ldx, K, M, want_bias=True, out=None, out_w=None, out_b=None):
     """dW [N, K] f32 = dZ^T X (X rows may overlap), db [N] f32 = column sums of dZ.  csrc/gemm_tn.hip.
     ``out = (flat f32 buffer, offset)`` places dW then db at that offset (N*K + N elements) instead of allocating;
     ``out_w`` / ``out_b``: contiguous f32 tensors of N*K / N elements that receive dW / db (gradient views of the
-    flat buffer, see grad_sink); ``scatter``: a ctypes array of hip.TnScatter -- the result goes straight to the
-    parameters' own layouts (cum_gemm_tn_scatter; _ScatterPlan below) and nothing is returned."""
+    flat buffer, see grad_sink)."""
     lib = hip.lib()
     dc = hip.dtype_code(dZ.dtype)
     dev = dZ.device
-    if scatter is not None:
-        ws = torch.empty(max(lib.cum_gemm_tn_workspace_elems(dc, M, N, K), 1), dtype=torch.float32, device=dev)
-        esz = dZ.element_size()
-        with torch.cuda.device(dev):
-            hip.check(lib.cum_gemm_tn_scatter(dc, M, N, K, ctypes.c_void_p(dZ.data_ptr() + z_off * esz), ldz,
-                                              ctypes.c_void_p(X.data_ptr() + x_off * esz), ldx, scatter, len(scatter),
-                                              hip.ptr(ws), hip.stream_ptr()))
-        return None, None
     if out_w is not None:
         dW = out_w.view(N, K)
         db = (out_b if out_b is not None else torch.empty(N, dtype=torch.float32, device=dev)) if want_bias else None
@@ -224,6 +216,24 @@ def _runs8(ro, co, base=0):
     return 2 if aligned else 1
 
 
+def _pack2d_jobs(mats, dev):
+    """cum_pack2d's device operands for separable layouts.  mats: [(destination offset, rows, cols, rowoff, coloff,
+    transpose)] (the last three as _separable returns them) -> (job records, 64 x 64 tile list, row / column tables,
+    number of tiles), or None if there is nothing to do."""
+    if not mats:
+        return None
+    jb = np.zeros(len(mats), dtype=[("off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("rt", "<i4"), ("ct", "<i4"),
+                                    ("tr", "<i4"), ("runs8", "<i4")])
+    tiles, tables, tab_pos = [], [], 0
+    for i, (off, rows, cols, ro, co, tr) in enumerate(mats):
+        jb[i] = (off, rows, cols, tab_pos, tab_pos + rows, int(tr), 0 if tr else _runs8(ro, co))
+        tables += [ro, co]
+        tab_pos += rows + cols
+        tiles += [(i, tr_, tc_) for tr_ in range((rows + 63) // 64) for tc_ in range((cols + 63) // 64)]
+    return (torch.from_numpy(jb.view(np.uint8)).to(dev), torch.tensor(tiles, dtype=torch.int32).to(dev),
+            torch.cat(tables).to(dev), len(tiles))
+
+
 class PackPlan:
     """Batches every weight / bias pack of one model into two gathers per forward.
 
@@ -250,7 +260,6 @@ class PackPlan:
         self.gidx = {}                        # (dtype, late) -> (device index tensor, [(reqkey, start, numel, shape)])
         self.current = {}
         self.big = {}                         # (dtype, late) -> the flat buffer all packed operands of that group are views of
-        self.late_event = None                # side-stream gather of the backward-only operands still to be joined
 
     @staticmethod
     def _shared_buffer(params):
@@ -277,11 +286,6 @@ class PackPlan:
 
     # layouts only the backward reads (data-gradient operands): skipped without autograd
     LATE = ("conv_dgrad", "convt_dgrad", "glu_dgrad", "plain_dgrad", "proj_t")
-    # "1": gather them on a side stream beside the forward's GEMMs.  Measured on the E8 train step (same box, two runs
-    # each): 21.44 / 21.48 ms with the side stream against 21.23 / 21.25 ms without -- the gather's scattered reads slow
-    # the concurrent GEMMs by more than the 0.3 ms it takes when run alone (as the round-2 attempt to run weight-gradient
-    # GEMMs on a second stream: every launch already fills the chip).  Off.
-    SIDE_STREAM = os.environ.get("CUM_PACK_SIDE_STREAM", "0") == "1"
 
     def refresh(self):
         """Recompute every recorded pack from the current parameter values.  While the set of recorded packs is
@@ -289,7 +293,7 @@ class PackPlan:
         kernels that hold their addresses.
 
         The operands of the data-gradient GEMMs (``LATE`` keys, about half of the packed bytes) are not needed before the
-        backward: with autograd off they are not gathered at all (``SIDE_STREAM``: see above)."""
+        backward: with autograd off they are not gathered at all."""
         grad_on = torch.is_grad_enabled()
         if not self.reqs:
             self.current = {}
@@ -306,8 +310,7 @@ class PackPlan:
                 # separable 2-D layouts first (index-free cum_pack2d: two small tables per operand), the rest (bias
                 # vectors, anything irregular) behind them through the per-element index of cum_gather
                 metas, start = [], 0
-                jobs, tiles, tables, tab_pos = [], [], [], 0
-                rest = []
+                mats, rest = [], []
                 for rk, g, shape in items:
                     sep = None
                     if _PACK2D and len(shape) == 2 and shape[1] % 8 == 0 and self.source is not None:
@@ -315,13 +318,7 @@ class PackPlan:
                     if sep is None:
                         rest.append((rk, g, shape))
                         continue
-                    ro, co, tr = sep
-                    jobs.append((start, shape[0], shape[1], tab_pos, tab_pos + shape[0], int(tr), 0 if tr else _runs8(ro, co)))
-                    tables += [ro, co]
-                    tab_pos += shape[0] + shape[1]
-                    for tr_ in range((shape[0] + 63) // 64):
-                        for tc_ in range((shape[1] + 63) // 64):
-                            tiles.append((len(jobs) - 1, tr_, tc_))
+                    mats.append((start, shape[0], shape[1], *sep))
                     metas.append((rk, start, g.numel(), shape))
                     start += (g.numel() + 7) // 8 * 8
                 rest_start, parts = start, []
@@ -329,22 +326,12 @@ class PackPlan:
                     metas.append((rk, start, g.numel(), shape))
                     parts.append(g)
                     start += g.numel()
-                pack2d = None
-                if jobs:
-                    import numpy as np
-                    jb = np.zeros(len(jobs), dtype=[("off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("rt", "<i4"), ("ct", "<i4"),
-                                                    ("tr", "<i4"), ("runs8", "<i4")])
-                    for i, (off, r, c, rt, ct, tr, r8) in enumerate(jobs):
-                        jb[i] = (off, r, c, rt, ct, tr, r8)
-                    pack2d = (torch.from_numpy(jb.view(np.uint8)).to(dev), torch.tensor(tiles, dtype=torch.int32).to(dev),
-                              torch.cat(tables).to(dev), len(tiles))
                 gi = torch.cat(parts).to(dev) if parts else None
-                self.gidx[gk] = (gi, metas, pack2d, rest_start, start)
+                self.gidx[gk] = (gi, metas, _pack2d_jobs(mats, dev), rest_start, start)
             self.dirty = False
-        self.late_event = None
         with torch.no_grad():
             flat = self.source if self.source is not None else torch.cat([p.detach().reshape(-1) for p in self.params])
-            cast, side = {}, None
+            cast = {}
             for gk, (gi, metas, pack2d, rest_start, total) in self.gidx.items():
                 dt, late = gk
                 if late and not grad_on:
@@ -363,38 +350,17 @@ class PackPlan:
                 fresh = big is None
                 if fresh:
                     big = torch.zeros(max(total, 8), dtype=dt, device=dev)
-
-                def run():
-                    if pack2d is not None:
-                        jb, tl, tb, ntiles = pack2d
-                        with torch.cuda.device(dev):
-                            hip.check(hip.lib().cum_pack2d(hip.ptr(flat), hip.ptr(jb), hip.ptr(tl), ntiles, hip.ptr(tb),
-                                                           hip.dtype_code(dt), hip.ptr(big), hip.stream_ptr()))
-                    if gi is not None:
-                        gather(flat_dt, gi, dt, out=big[rest_start:rest_start + gi.numel()])
-                if late and self.SIDE_STREAM:
-                    if side is None:
-                        side = self.__dict__.get("_side")
-                        if side is None:
-                            side = self.__dict__["_side"] = torch.cuda.Stream(device=dev)
-                        side.wait_stream(torch.cuda.current_stream(dev))
-                    with torch.cuda.stream(side):
-                        run()
-                else:
-                    run()
+                if pack2d is not None:
+                    jb, tl, tb, ntiles = pack2d
+                    with torch.cuda.device(dev):
+                        hip.check(hip.lib().cum_pack2d(hip.ptr(flat), hip.ptr(jb), hip.ptr(tl), ntiles, hip.ptr(tb),
+                                                       hip.dtype_code(dt), hip.ptr(big), hip.stream_ptr()))
+                if gi is not None:
+                    gather(flat_dt, gi, dt, out=big[rest_start:rest_start + gi.numel()])
                 if fresh:
                     self.big[gk] = big
                     for rk, start, n, shape in metas:
                         self.current[rk] = big[start:start + n].view(shape)
-            if side is not None:
-                self.late_event = side.record_event()
-
-    def join(self):
-        """First backward-side use of a late operand: the current stream waits for the side-stream gather."""
-        ev = self.late_event
-        if ev is not None:
-            torch.cuda.current_stream().wait_event(ev)
-            self.late_event = None
 
 
 _PACK2D = os.environ.get("CUM_PACK2D", "1") != "0"      # "0": every packed operand through the per-element index (A/B)
@@ -412,8 +378,6 @@ def take(src, key, build, dtype=None):
     if plan is not None and src.data_ptr() in plan.offset:
         hit = plan.current.get((key, src.data_ptr(), dtype if dtype is not None else src.dtype))
         if hit is not None:
-            if plan.late_event is not None and key[0] in plan.LATE:
-                plan.join()
             return hit
     ent = _INDEX_CACHE.get((key, src.device))
     if ent is None:
@@ -446,9 +410,8 @@ def _zeros(rows, cols):
 
 
 # Weight gradients of a whole stack: every cum_gemm_tn of the stack's backward writes (dW, db) in GEMM layout into one
-# flat f32 arena, and ONE gather (index built once per stack signature) brings all of them into the parameters'
-# layouts -- instead of two or three gathers per layer (~50 launches per step).
-_ARENA_BATCH = os.environ.get("CUM_WGRAD_ARENA", "1") != "0"      # "0": one gather per parameter (A/B timing)
+# flat f32 arena (_WgradArena), and ONE un-pack launch (jobs built once per stack signature) brings all of them into the
+# parameters' layouts -- instead of two or three gathers per layer (~50 launches per step).
 _ARENA_INDEX = {}
 
 
@@ -515,30 +478,15 @@ class _WgradArena:
             # them over with two small tables per parameter instead of a 4-byte index per element.  What does not
             # separate (or is narrower than 8 columns) keeps the per-element gather.
             parts = build_parts()
-            jobs, tiles, tables, tab_pos, rest = [], [], [], 0, []
+            mats, rest = [], []
             for k, (part, o, sh) in enumerate(zip(parts, offs, shapes)):
                 rows, cols = (sh[0], _numel(sh) // sh[0]) if len(sh) > 1 else (1, _numel(sh))
                 sep = _separable(part.reshape(rows, cols).to(torch.int64)) if (_PACK2D and cols % 8 == 0 and o % 4 == 0) else None
                 if sep is None or bool((part.reshape(-1) < 0).any()):
                     rest.append(k)
                     continue
-                ro, co, tr = sep
-                jobs.append((o - lo, rows, cols, tab_pos, tab_pos + rows, int(tr), 0 if tr else _runs8(ro, co)))
-                tables += [ro, co]
-                tab_pos += rows + cols
-                for tr_ in range((rows + 63) // 64):
-                    for tc_ in range((cols + 63) // 64):
-                        tiles.append((len(jobs) - 1, tr_, tc_))
-            pack2d = None
-            if jobs:
-                import numpy as np
-                jb = np.zeros(len(jobs), dtype=[("off", "<i8"), ("rows", "<i4"), ("cols", "<i4"), ("rt", "<i4"), ("ct", "<i4"),
-                                                ("tr", "<i4"), ("runs8", "<i4")])
-                for i, (off, r, c, rt, ct, tr, r8) in enumerate(jobs):
-                    jb[i] = (off, r, c, rt, ct, tr, r8)
-                dev = self.buf.device
-                pack2d = (torch.from_numpy(jb.view(np.uint8)).to(dev), torch.tensor(tiles, dtype=torch.int32).to(dev),
-                          torch.cat(tables).to(dev), len(tiles))
+                mats.append((o - lo, rows, cols, *sep))
+            pack2d = _pack2d_jobs(mats, self.buf.device)
             gidx = None
             if rest:
                 # (the leftovers need not be contiguous: one small gather each)
@@ -564,85 +512,39 @@ class _WgradArena:
         flat = gather(self.buf, ent, torch.float32)
         outs, off = [], 0
         for sh in shapes:
-            n = 1
-            for d in sh:
-                n *= d
-            outs.append(flat[off:off + n].view(sh))
-            off += n
+            outs.append(flat[off:off + _numel(sh)].view(sh))
+            off += _numel(sh)
         return outs
 
+    def deliver(self, key, params, shapes, build_parts):
+        """The arena's gradients to ``params`` (shapes[k] = params[k].shape; build_parts() -> per parameter the arena
+        position of every element).  Where the flat gradient buffer takes them (grad_sink) they are un-packed into it
+        and announced, and the result is [None] per parameter; otherwise the result is the gradients as tensors of the
+        parameters' dtypes, for autograd."""
+        sink = grad_sink(params)
+        if sink is None:
+            return [g.to(p.dtype) for g, p in zip(self.unpack(key, build_parts, shapes), params)]
+        flat, idx, offs = sink
+        # unpack_into takes one contiguous run of the flat buffer; parameters of others in between (the decoder's
+        # transposed-conv biases) must not be overwritten, so the un-pack runs once per run of these parameters
+        order = sorted(range(len(params)), key=lambda q: offs[q])
+        runs = [[order[0]]]
+        for prev, q in zip(order, order[1:]):
+            if offs[q] == offs[prev] + (_numel(shapes[prev]) + 3) // 4 * 4:
+                runs[-1].append(q)
+            else:
+                runs.append([q])
+        parts = []
 
-# "1": weight gradients straight from the slab reduce into the parameters' layouts (cum_gemm_tn_scatter), no arena and no
-# un-pack launch.  Built in round 6 and measured SLOWER on the E8 step (same box, A B A B: 19.12 / 19.14 ms against 18.89 /
-# 18.89 with the arena): the reduce then gathers its four sources per destination float4 with 4-byte loads through every
-# slab (2.1 GB per step) -- 256-byte runs per wave for a conv weight's taps, rows K apart for a transposed conv's -- where
-# the arena path reads the slabs as whole float4 rows and pays the permutation once, on 165 MB.  Off; kept for A/B.
-_SCATTER = os.environ.get("CUM_WGRAD_SCATTER", "0") == "1"
-_SCATTER_PLANS = {}
-
-
-class _ScatterPlan:
-    """Weight gradients straight into the parameters' layouts: per arena slot (= per weight-gradient GEMM) the row / column
-    tables of cum_gemm_tn_scatter for the parameters that slot feeds, derived once per stack signature from the same
-    index layouts the arena un-pack uses (``parts``: per parameter the arena position of every element).
-
-    slots[s] = [(q, rowoff, coloff, rows, cols, reads_bias, bias_fold)] with q the parameter's position in the stack's
-    parameter list, or None where a parameter of the slot does not separate (the arena path then serves that slot)."""
-
-    def __init__(self, arena, parts, shapes, slot_of, folds, dev):
-        per = {}
-        for q, (part, sh, sl) in enumerate(zip(parts, shapes, slot_of)):
-            if sl is None:
-                continue
-            rows, cols = (sh[0], _numel(sh) // sh[0]) if len(sh) > 1 else (1, _numel(sh))
-            rel = part.reshape(rows, cols).to(torch.int64) - arena.offs[sl]
-            N, K = arena.sizes[sl]
-            fold = folds.get(q, 0)
-            ok = cols % 4 == 0 and bool((part.reshape(-1) >= 0).all()) and int(rel.min()) >= 0 and \
-                int(rel.max()) < N * K + N
-            sep = _separable(rel) if ok else None
-            if sep is None:
-                per[sl] = None
-                continue
-            if per.get(sl, []) is None:
-                continue
-            ro, co, _ = sep
-            per.setdefault(sl, []).append((q, ro.to(dev), co.to(dev), rows, cols, int(bool((rel >= N * K).any())), int(fold)))
-        self.slots = {sl: (v if v is not None and len(v) <= 2 else None) for sl, v in per.items()}
-
-    def jobs(self, slot, grad, offs):
-        """ctypes array for one GEMM: destinations = the parameters' views of the flat gradient buffer."""
-        ent = self.slots.get(slot)
-        if not ent:
-            return None
-        arr = (hip.TnScatter * len(ent))()
-        for k, (q, ro, co, rows, cols, rb, fold) in enumerate(ent):
-            if offs[q] % 4:
-                return None
-            arr[k].dst = grad.data_ptr() + 4 * offs[q]
-            arr[k].rowoff, arr[k].coloff = ro.data_ptr(), co.data_ptr()
-            arr[k].rows, arr[k].cols, arr[k].reads_bias, arr[k].bias_fold = rows, cols, rb, fold
-        return arr
-
-    def params_of(self, slot):
-        return [e[0] for e in (self.slots.get(slot) or ())]
-
-
-def _scatter_plan(key, arena, parts_fn, shapes, slot_of, folds, dev):
-    if not _SCATTER:
-        return None
-    ck = (key, dev)
-    plan = _SCATTER_PLANS.get(ck)
-    if plan is None:
-        plan = _SCATTER_PLANS[ck] = _ScatterPlan(arena, parts_fn(), shapes, slot_of, folds, dev)
-    return plan
-
-
-def _contiguous_run(offs, shapes):
-    """True if the parameters (16-byte aligned, as FlatParams lays them out) fill [min offset, max end) without strangers."""
-    lo = min(offs)
-    hi = max(o + _numel(sh) for o, sh in zip(offs, shapes))
-    return sum((_numel(sh) + 3) // 4 * 4 for sh in shapes) >= hi - lo
+        def run_parts(run):
+            if not parts:
+                parts.extend(build_parts())
+            return [parts[q] for q in run]
+        for run in runs:
+            self.unpack_into((key, tuple(run)), lambda: run_parts(run), [shapes[q] for q in run], flat.grad,
+                             [offs[q] for q in run])
+        flat.wrote(idx)
+        return [None] * len(params)
 
 
 def _numel(shape):
@@ -1236,20 +1138,11 @@ def _glu_bwd(z, ybuf, dy, go):
     return dz
 
 
-def _glu_wgrad(dz, xbuf, w, gi, M, out=None, scatter=None):
-    """Weight / bias gradient of a 1x1+GLU layer from dZ [M, G*32] and its input row buffer.  With ``out`` (an arena
-    slot) the GEMM-layout results stay there for the stack's batched un-pack and nothing is returned; with ``scatter``
-    they go straight to the parameters' gradient views."""
+def _glu_wgrad(dz, xbuf, gi, M, out):
+    """Weight / bias gradient of a 1x1+GLU layer from dZ [M, G*32] and its input row buffer, in GEMM layout into the
+    arena slot ``out`` (the stack's un-pack brings them to the parameters)."""
     G32 = dz.shape[1]
-    H2 = w.shape[0]
-    sh = tuple(w.shape)
-    dwp, dbp = wgrad(dz, 0, G32, G32, xbuf, gi.Cp, gi.Cp, gi.Cp, M, out=None if scatter is not None else out,
-                     scatter=scatter)
-    if out is not None or scatter is not None:
-        return None, None
-    db = take(dbp, ("glu_vec_unpack", H2), lambda: _invert(lay_glu_vec(H2), (H2,)))
-    dw = take(dwp, ("glu_unpack", sh, G32, gi.Cp), lambda: _invert(lay_glu_fwd(sh, G32, gi.Cp), sh))
-    return dw.to(w.dtype), db.to(w.dtype)
+    wgrad(dz, 0, G32, G32, xbuf, gi.Cp, gi.Cp, gi.Cp, M, out=out)
 
 
 def _glu_dgrad_weights(w, gi, G32, dt):
@@ -1454,10 +1347,8 @@ class EncoderStack(torch.autograd.Function):
         grads = [None] * (4 * E)
         dz, dx0 = None, None
         # arena slots: 2 i = conv of layer i (N = Cp_mid, K = 4 Cp_in), 2 i + 1 = its 1x1+GLU (N = G*32, K = Cp_mid)
-        arena = None
-        if _ARENA_BATCH:
-            arena = _WgradArena([nk for i in range(E) for nk in ((geos[i][1].Cp, 4 * geos[i][0].Cp),
-                                                                 (2 * zs[i].shape[1], geos[i][1].Cp))], dev)
+        arena = _WgradArena([nk for i in range(E) for nk in ((geos[i][1].Cp, 4 * geos[i][0].Cp),
+                                                             (2 * zs[i].shape[1], geos[i][1].Cp))], dev)
         shapes = [tuple(p.shape) for p in params]
 
         def parts(lo, hi):                     # arena -> parameter index of layers [lo, hi)
@@ -1472,40 +1363,16 @@ class EncoderStack(torch.autograd.Function):
                 out.append(arena.db_index(2 * i + 1, _invert(lay_glu_vec(sh2[0]), (sh2[0],))))
             return out
         key = ("enc", tuple(shapes), tuple((g[0].Cp, g[1].Cp) for g in geos), tuple(z.shape[1] for z in zs))
-        sink = grad_sink(params) if arena is not None else None
-        if sink is not None and not _contiguous_run(sink[2], shapes):
-            sink = None
+
+        def deliver(lo, hi):                   # the gradients of layers [lo, hi): into the flat buffer or to autograd
+            grads[4 * lo:4 * hi] = arena.deliver((key, lo, hi), params[4 * lo:4 * hi], shapes[4 * lo:4 * hi],
+                                                 lambda: parts(lo, hi))
         # Data-parallel runs: the three deepest layers hold ~85 % of the stack's parameters and finish first, while the
         # (slow, HBM-bound) outer layers are still to come -- their gradients are unpacked and announced to the
         # exchange as soon as their GEMMs are enqueued instead of at the end of the stack.
         cut = E - 3 if E > 3 else 0
-        early = (sink is not None and cut > 0 and getattr(sink[0], "early_announce", False)
-                 and _contiguous_run(sink[2][4 * cut:], shapes[4 * cut:]) and _contiguous_run(sink[2][:4 * cut], shapes[:4 * cut]))
-
-        def flush(lo, hi):
-            flat, idx, offs = sink
-            arena.unpack_into((key, lo, hi), lambda: parts(lo, hi), shapes[4 * lo:4 * hi], flat.grad, offs[4 * lo:4 * hi])
-            flat.wrote(idx[4 * lo:4 * hi])
-        # Scatter form (cum_gemm_tn_scatter): every generic layer's two weight-gradient GEMMs write w, b of that layer
-        # straight into the flat gradient buffer and the layer is announced at once; the arena + un-pack launch remain
-        # for the fused first layer only (its own reduce kernels write arena slots).  All generic layers or none.
-        fused0 = y1s[0] is None and arena is not None and not ctx.needs_input_grad[0]
-        first = 1 if fused0 else 0
-        plan = None
-        if sink is not None:
-            plan = _scatter_plan(key, arena, lambda: parts(0, E), shapes, [2 * (q // 4) + (q % 4 >= 2) for q in range(4 * E)],
-                                 {}, dev)
-            if plan is not None and not all(len(plan.params_of(sl)) == 2 for i in range(first, E) for sl in (2 * i, 2 * i + 1)):
-                plan = None
-            if plan is not None and first and not _contiguous_run(sink[2][:4], shapes[:4]):
-                plan = None
-
-        def sc(slot):
-            if plan is None:
-                return None
-            jobs = plan.jobs(slot, sink[0].grad, sink[2])
-            assert jobs is not None
-            return jobs
+        sink = grad_sink(params) if cut > 0 else None
+        early = sink is not None and getattr(sink[0], "early_announce", False)
         for i in reversed(range(E)):
             gi, gm, go = geos[i]
             w1, b1, w2, b2 = params[4 * i:4 * i + 4]
@@ -1516,12 +1383,11 @@ class EncoderStack(torch.autograd.Function):
             G32 = dz.shape[1]
             y1 = y1s[i]
             if y1 is None:                     # fused first layer: y1 was never stored
-                if arena is not None and not ctx.needs_input_grad[0]:
+                if not ctx.needs_input_grad[0]:
                     _enc0_bwd(dz, bufs[0], w1, b1, w2, gm, go, arena.out(0), arena.out(1))
                     break
                 y1 = _conv_relu_fwd(bufs[0], w1, b1, gi, gm)      # generic route (input gradient wanted): rebuild it
-            grads[4 * i + 2], grads[4 * i + 3] = _glu_wgrad(dz, y1, w2, gm, go.M,
-                                                            out=arena.out(2 * i + 1) if arena else None, scatter=sc(2 * i + 1))
+            _glu_wgrad(dz, y1, gm, go.M, arena.out(2 * i + 1))
             # 1x1 data gradient, gated by the ReLU below it in the epilogue
             wt = _glu_dgrad_weights(w2, gm, G32, dt)
             dzc = gm.new(dt, dev)
@@ -1533,17 +1399,10 @@ class EncoderStack(torch.autograd.Function):
                      res=y1, r_off=gm.Cp, ldr=gm.Cp, geo=gm)
             # conv weight gradient: X row m = the 4*Cp contiguous inputs of output row m
             sh = tuple(w1.shape)
-            dwp, dbp = wgrad(dzc, gm.Cp, gm.Cp, gm.Cp, bufs[i], gi.Cp, 2 * gi.Cp, 4 * gi.Cp, gm.M,
-                             out=arena.out(2 * i) if (arena and plan is None) else None, scatter=sc(2 * i))
-            if arena is None:
-                grads[4 * i] = take(dwp, ("conv_unpack", sh, gi.Cp, gm.Cp),
-                                    lambda: _invert(lay_conv_fwd(sh, gi.Cp, gm.Cp, 4 * gi.Cp), sh)).to(w1.dtype)
-                grads[4 * i + 1] = dbp[:sh[0]].to(w1.dtype)
+            wgrad(dzc, gm.Cp, gm.Cp, gm.Cp, bufs[i], gi.Cp, 2 * gi.Cp, 4 * gi.Cp, gm.M, out=arena.out(2 * i))
             dz = None
-            if plan is not None:
-                sink[0].wrote(sink[1][4 * i:4 * i + 4])          # this layer's four gradients are in place
-            elif early and i == cut:
-                flush(cut, E)
+            if early and i == cut:
+                deliver(cut, E)
             if i == 0 and not ctx.needs_input_grad[0]:
                 break
             # conv data gradient = transposed conv: pair row t' reads dzc rows t'-1, t'
@@ -1563,16 +1422,7 @@ class EncoderStack(torch.autograd.Function):
                 dx0 = dx
             else:
                 dz = _glu_bwd(zs[i - 1], bufs[i], dx if ext is None else dx + ext, gi)
-        if arena is not None:
-            if plan is not None:           # every generic layer is in place already: the fused first layer's arena slots
-                if first:
-                    flush(0, 1)
-                grads = [None] * len(params)
-            elif sink is not None:         # straight into the flat gradient buffer: no AccumulateGrad adds
-                flush(0, cut if early else E)
-                grads = [None] * len(params)
-            else:
-                grads = [g.to(p.dtype) for g, p in zip(arena.unpack(key, lambda: parts(0, E), shapes), params)]
+        deliver(0, cut if early else E)
         return (dx0, None, None, *grads)
 
 
@@ -1606,7 +1456,7 @@ class DecoderStack(torch.autograd.Function):
             # last layer (64 -> 1): g and the gate are rebuilt from u where the backward needs them (csrc/dec7.hip); the
             # fused backward takes the ReLU of the layer below as sign bits and writes into the stack's arena
             if (j == E - 1 and skips[j] is None and _dec7_ok(w1, wt, gi, gg, go, ubuf.dtype)
-                    and (not save_z or (E >= 2 and skips[E - 2] is not None and _SIGN_MASK and _ARENA_BATCH))):
+                    and (not save_z or (E >= 2 and skips[E - 2] is not None and _SIGN_MASK))):
                 us.append(_dec7_fwd(us[-1], w1, b1, wt, bt, gi, go))
                 gs.append(None)
                 zs.append(None)
@@ -1654,10 +1504,8 @@ class DecoderStack(torch.autograd.Function):
         g32s = [32 * ((params[4 * j].shape[0] // 2 + 15) // 16) for j in range(E)]       # packed 1x1 rows (16 a | 16 b per 32)
         # arena slots: 2 j = 1x1+GLU of layer j (N = G*32, K = Cp_in), 2 j + 1 = its transposed conv (N = 2 Cp_out,
         # K = 2 Cp_glu)
-        arena = None
-        if _ARENA_BATCH:
-            arena = _WgradArena([nk for j in range(E) for nk in ((g32s[j], geos[j][0].Cp),
-                                                                 (2 * geos[j][2].Cp, 2 * geos[j][1].Cp))], dev)
+        arena = _WgradArena([nk for j in range(E) for nk in ((g32s[j], geos[j][0].Cp),
+                                                             (2 * geos[j][2].Cp, 2 * geos[j][1].Cp))], dev)
         shapes3 = [tuple(params[4 * j + k].shape) for j in range(E) for k in range(3)]
 
         def parts():
@@ -1671,35 +1519,6 @@ class DecoderStack(torch.autograd.Function):
                 out.append(arena.dw_index(2 * j + 1, _invert(lay_convt_fwd(sht, gg.Cp, go.Cp, 2 * go.Cp, 2 * gg.Cp), sht)))
             return out
         key = ("dec", tuple(shapes3), tuple((g[0].Cp, g[1].Cp, g[2].Cp) for g in geos), tuple(g32s))
-        # Scatter form (cum_gemm_tn_scatter; see EncoderStack.backward): w1, b1 from the 1x1's GEMM, wt and bt from the
-        # transposed conv's -- bt as the fold of the two halves of the paired-row bias gradient, which cost an ATen add
-        # per layer on the arena path.  The fused last layer keeps the arena (its own reduce kernels write the slots).
-        last_generic = E - 1 if ctx.fused_last else E
-        plan, sink4 = None, None
-        if arena is not None:
-            sink4 = grad_sink(list(params))
-            if sink4 is not None and all(p.is_leaf and p.dtype == torch.float32 for p in params):
-                shapes4 = [tuple(p.shape) for p in params]
-
-                def parts4():                      # parts() + the transposed conv's bias: channel c <- db[c] (+ db[Cp + c])
-                    three, out = parts(), []
-                    for j in range(E):
-                        out += three[3 * j:3 * j + 3]
-                        out.append(arena.db_index(2 * j + 1, torch.arange(1, shapes4[4 * j + 3][0] + 1, dtype=torch.int64)))
-                    return out
-                plan = _scatter_plan(key + ("bt",), arena, parts4, shapes4,
-                                     [2 * (q // 4) + (q % 4 >= 2) for q in range(4 * E)],
-                                     {4 * j + 3: geos[j][2].Cp for j in range(E)}, dev)
-                if plan is not None and not all(len(plan.params_of(sl)) == 2 for j in range(last_generic)
-                                                for sl in (2 * j, 2 * j + 1)):
-                    plan = None
-
-        def sc(slot):
-            if plan is None:
-                return None
-            jobs = plan.jobs(slot, sink4[0].grad, sink4[2])
-            assert jobs is not None
-            return jobs
         for j in reversed(range(E)):
             gi, gg, go = geos[j]
             w1, b1, wt, bt = params[4 * j:4 * j + 4]
@@ -1712,13 +1531,8 @@ class DecoderStack(torch.autograd.Function):
                     dskips[j - 1] = du
                 continue
             # transposed-conv weight gradient: pair rows of dpre against the 2*Cp contiguous inputs (rows m-1, m)
-            dwp, dbp = wgrad(dpre, go.Cp, 2 * go.Cp, 2 * go.Cp, gs[j], 0, gg.Cp, 2 * gg.Cp, gg.M,
-                             out=arena.out(2 * j + 1) if (arena and plan is None) else None, scatter=sc(2 * j + 1))
-            if plan is None:
-                grads[4 * j + 3] = _convt_bias_grad(bt, dbp, go.Cp, sht[1], wt.dtype)
-            if arena is None:
-                grads[4 * j + 2] = take(dwp, ("convt_unpack", sht, gg.Cp, go.Cp),
-                                        lambda: _invert(lay_convt_fwd(sht, gg.Cp, go.Cp, 2 * go.Cp, 2 * gg.Cp), sht)).to(wt.dtype)
+            _, dbp = wgrad(dpre, go.Cp, 2 * go.Cp, 2 * go.Cp, gs[j], 0, gg.Cp, 2 * gg.Cp, gg.M, out=arena.out(2 * j + 1))
+            grads[4 * j + 3] = _convt_bias_grad(bt, dbp, go.Cp, sht[1], wt.dtype)
             # its data gradient = strided conv of dpre (row t reads rows 2t..2t+3), through the GLU in the epilogue
             Nd, Kd = rup(gg.Cp, 16), rup(4 * go.Cp, bk_of(dt))
             wc = take(wt, ("convt_dgrad", sht, go.Cp, Nd, Kd), lambda: lay_convt_dgrad(sht, go.Cp, Nd, Kd), dt)
@@ -1732,10 +1546,7 @@ class DecoderStack(torch.autograd.Function):
                 dg = gg.new(dt, dev)
                 gemm(dpre, go.Cp, 2 * go.Cp, wc, None, dg, gg.Cp, gg.Cp, gg.M, gg.P, gg.T, hip.EPI_BIAS, gg.Cp, geo=gg)
                 dz = _glu_bwd(z, gs[j], dg, gg)
-            grads[4 * j], grads[4 * j + 1] = _glu_wgrad(dz, us[j], w1, gi, gg.M, out=arena.out(2 * j) if arena else None,
-                                                        scatter=sc(2 * j))
-            if plan is not None:
-                sink4[0].wrote(sink4[1][4 * j:4 * j + 4])        # this layer's four gradients are in place
+            _glu_wgrad(dz, us[j], gi, gg.M, arena.out(2 * j))
             # 1x1 data gradient: ungated it is the gradient of u_j (and of the skip added into it); gated by the ReLU
             # of layer j-1 it is that layer's dpre -- both written by one epilogue
             w1t = _glu_dgrad_weights(w1, gi, G32, dt)
@@ -1751,42 +1562,9 @@ class DecoderStack(torch.autograd.Function):
                 dpre = du
             if j > 0 and j - 1 < ctx.n_skips:
                 dskips[j - 1] = du
-        if arena is not None:
-            # w1, b1, wt per layer from one gather (bt is the sum of two halves of its slab: set above); in scatter form
-            # only the fused last layer's three are left to it
-            shapes = shapes3
-            lo3 = 3 * last_generic if plan is not None else 0
-            three = [params[4 * j + k] for j in range(E) for k in range(3)]
-            sink = grad_sink(three[lo3:]) if lo3 < len(three) else None
-            if plan is not None and lo3 == len(three):
-                pass                       # nothing left for the arena
-            elif sink is not None:         # w1, b1, wt straight into the flat gradient buffer (bt keeps the autograd path)
-                flat, idx, offs = sink
-                offs = [None] * lo3 + list(offs)
-                # the transposed-conv biases sit between the gathered parameters: they must not be overwritten with
-                # zeros by the gap fill, so the gather runs per contiguous run of gathered parameters
-                order = sorted(range(lo3, len(three)), key=lambda q: offs[q])
-                runs, cur = [], [order[0]]
-                for q_prev, q in zip(order, order[1:]):
-                    end_prev = offs[q_prev] + (_numel(shapes[q_prev]) + 3) // 4 * 4
-                    if offs[q] == end_prev:
-                        cur.append(q)
-                    else:
-                        runs.append(cur)
-                        cur = [q]
-                runs.append(cur)
-                all_parts = None
-                for r, run in enumerate(runs):
-                    def run_parts(run=run):
-                        nonlocal all_parts
-                        if all_parts is None:
-                            all_parts = parts()
-                        return [all_parts[q] for q in run]
-                    arena.unpack_into((key, r, lo3), run_parts, [shapes[q] for q in run], flat.grad, [offs[q] for q in run])
-                flat.wrote(idx)
-            else:
-                un = arena.unpack(key, parts, shapes)
-                for j in range(E):
-                    for k in range(3):
-                        grads[4 * j + k] = un[3 * j + k].to(params[4 * j + k].dtype)
+        # w1, b1, wt per layer from the arena (bt is the sum of two halves of its slab: set above)
+        three = [params[4 * j + k] for j in range(E) for k in range(3)]
+        un = arena.deliver(key, three, shapes3, parts)
+        for j in range(E):
+            grads[4 * j:4 * j + 3] = un[3 * j:3 * j + 3]
         return (du, None, None, None, *dskips, *grads)
