@@ -1,6 +1,7 @@
 """bench.py -- CleanUMamba-E8 train-step throughput on MI355X (BASELINE.json metric).
 
   python bench.py --gpus N --steps K --warmup W            (any N: for N > 1 the process spawns its own N ranks)
+  python bench.py --gpus N --steps K --warmup W --full     (the same, then every other measurement described below)
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...   (N > 1, ranks from the env)
 
 A step = one full optimisation step of the reference's hot loop (src/training/train.py:255-312):
@@ -11,6 +12,8 @@ N > 1), clip_grad_norm_(10), fused Adam, LR schedule -- on synthetic 10 s @ 16 k
 value = global_batch * 160000 * K / (max-over-ranks time of K steps); ms_per_step = that time / K.
 --dump-outputs DIR: after the timed steps rank 0 writes what the last one computed as DIR/<name>.npy (step_outputs);
 the inputs and the initial weights are seeded, so two builds run with the same arguments compare output for output.
+A plain run sets up, warms up, times the K steps, writes --dump-outputs and prints the line; everything below this
+paragraph is measured after the timed steps and only with --full (it leaves the headline fields as they are).
 roofline: the kernel VERDICT names (rocprofv3 --stats: gemm_tn9_kernel + gemm_tn_kernel, the conv-stack weight
 gradients), timed live with HIP events over the 16 encoder launch shapes of the step; each shape is priced against the
 roof that binds it, the headline is the MFMA-bound group (enc3-enc7) against the dense 16-bit MFMA peak.  `kernels` lists the other heavy kernels the same way
@@ -20,6 +23,7 @@ layer summed, against the FUSED layer's algorithmic bytes (HBM roof) and flops (
 selective scan at d_state 64 / 16 / 8 (where HBM, not v_exp_f32 issue, is the binding roof).
 cpu_baseline: the CPU oracle (oracle/cleanumamba_ref.py, kind "port") doing forward + loss + backward
 on a bounded sample (2 clips of 10 s), rank 0, N = 1 only.
+N > 1: `modes.no_exchange`, a third timed loop on the same GPUs without gradient exchange.
 """
 import argparse
 import json
@@ -57,10 +61,15 @@ def parse():
                          "--no-graph)")
     ap.add_argument("--rank-timeout", type=float, default=1500.0, help="seconds the launcher waits for its ranks")
     ap.add_argument("--no-pin", action="store_true", help="N > 1: do not pin the ranks to their GPUs' NUMA nodes")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure everything that is not the headline figure: the roofline, "
+                         "kernel, scan and layer tables, the E6 forward and the streaming configuration, the CPU baseline "
+                         "(one GPU) and the no-exchange loop (N > 1).  Off by default: a plain run sets up, warms up, times "
+                         "the steps, writes --dump-outputs and prints the result line")
     ap.add_argument("--no-baseline-mode", action="store_true",
-                    help="N > 1: skip the third timed loop (the same GPUs without gradient exchange)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-roofline", action="store_true")
+                    help="with --full, N > 1: skip the third timed loop (the same GPUs without gradient exchange)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-roofline", action="store_true", help="with --full: skip the roofline and per-kernel tables")
     ap.add_argument("--cpu-clip", type=int, default=CLIP, help="samples in the CPU-baseline clip")
     ap.add_argument("--dump-outputs", metavar="DIR", default=None,
                     help="rank 0 writes what the last timed step computed to DIR/<name>.npy (see step_outputs)")
@@ -798,7 +807,7 @@ def main():
     else:
         # several ranks: BOTH step forms in one invocation (the first multi-GPU run must not measure half of what
         # matters): the eager step with the per-bucket exchange overlapped, then the three-graph form; the headline is the
-        # faster one.  Then the same GPUs without any exchange: what the data-parallel step adds on this node.
+        # faster one.  With --full then the same GPUs without any exchange: what the data-parallel step adds on this node.
         eager = run_mode(True, False)
         eager.pop("net")
         torch.cuda.empty_cache()
@@ -809,7 +818,7 @@ def main():
         if best is not graph:
             graph.pop("net", None)
         torch.cuda.empty_cache()
-        if not args.no_baseline_mode:
+        if args.full and not args.no_baseline_mode:
             solo = run_mode(False, None)
             solo.pop("net")
             torch.cuda.empty_cache()
@@ -849,7 +858,7 @@ def main():
                             "three graphs: all-reduce (AVG) of the decoder + bottleneck gradients (106 MB) beside the captured "
                             "encoder backward, all-reduce of the encoder's (59 MB) after it, then the captured optimizer section"
                             if graph_status == "captured" else "per-bucket all-reduce overlapped with the eager backward")}
-        if not args.no_roofline:
+        if args.full and not args.no_roofline:
             torch.cuda.empty_cache()
             kdt = ac if ac is not None else torch.bfloat16
             out["roofline"] = tn_roofline(dev, kdt)
@@ -864,7 +873,7 @@ def main():
                 # the other single-GPU configurations of BASELINE.json, so that the driver's record carries them
                 out["c2_e6_forward"] = c2_e6_forward(dev, kdt)
                 out["c5_streaming"] = c5_streaming(dev)
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(args.cpu_clip)
         line = json.dumps(out)
     # The JSON line is the LAST line this job writes: libraries loaded by the ranks (RCCL prints its "Librccl path" line

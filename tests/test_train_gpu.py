@@ -656,14 +656,14 @@ def test_bench_two_ranks_from_a_plain_invocation(cuda, tmp_path, mode):
     """`python bench.py --gpus 2 ...` with no rank environment must start its own two ranks (fresh processes, here both on
     the one GPU with gradients over gloo), and print ONE JSON line for n_gpus = 2 -- the shape of the driver's command.
     Default for several ranks: BOTH step forms are timed in the one invocation (the eager step with the per-bucket
-    exchange overlapped with backward, then the three-graph form, then the same GPUs without exchange) and the faster
-    form is the headline; `--graph` / `--no-graph` time one form only."""
+    exchange overlapped with backward, then the three-graph form; with `--full`, as here, then the same GPUs without
+    exchange) and the faster form is the headline; `--graph` / `--no-graph` time one form only."""
     import json
     torch.cuda.empty_cache()
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     env.update(CUM_DIST_BACKEND="gloo", HSA_ENABLE_IPC_MODE_LEGACY="0")
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--no-roofline",
-           "--batch-per-gpu", "2", "--rank-timeout", "600"] + {"both": [], "graph": ["--graph"], "eager": ["--no-graph"]}[mode]
+           "--batch-per-gpu", "2", "--rank-timeout", "600"] + {"both": ["--full"], "graph": ["--graph"], "eager": ["--no-graph"]}[mode]
     res = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=700)
     assert res.returncode == 0, res.stderr[-4000:]
     lines = [ln for ln in res.stdout.splitlines() if ln.startswith("{")]

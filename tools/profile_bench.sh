@@ -1,5 +1,6 @@
 #!/bin/bash
 # Kernel trace of the default bench.py run + a short run for per-step sums (GPU box).  Outputs under gpurun_out/prof_round/.
+ROOT=$(cd "$(dirname "$0")/.." && pwd)
 cd /tmp && export TMPDIR=/tmp PYTHONPATH=$GRAFT_REPO_ROOT
 OUT=$GRAFT_REPO_ROOT/gpurun_out/prof_round
 rm -rf $OUT && mkdir -p $OUT
@@ -36,10 +37,10 @@ if len(idx) >= 12:
     for k, (n, t) in sorted(per.items(), key=lambda kv: -kv[1][1])[:45]:
         print("  %7.3f  %5.1f  %s" % (t / 10, n / 10, k))
 PY
-# (2) the default run, csv stats for profiles/
-rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/full -o bench -- python3 $GRAFT_REPO_ROOT/bench.py > $OUT/bench_under_rocprof.json 2> $OUT/full.err
+# (2) the default-length run with every table (--full), csv stats for profiles/
+rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/full -o bench -- python3 $ROOT/bench.py --full > $OUT/bench_under_rocprof.json 2> $OUT/full.err
 cp /tmp/full/bench_kernel_stats.csv $OUT/ 2>/dev/null || find /tmp/full -name "*kernel_stats.csv" -exec cp {} $OUT/bench_kernel_stats.csv \;
-# (3) agreement of roofline.launch_ms with the trace: the roofline loop is the last thing bench.py runs at N = 1
+# (3) agreement of roofline.launch_ms with the trace: the roofline loop is the last thing bench.py --full runs at N = 1
 #     before the cpu baseline (16 shapes x (3 warm-up + 10 timed) cum_gemm_tn calls; roofline.launch_ms covers the last 10)
 python3 - /tmp/full $OUT/bench_under_rocprof.json <<'PY' > $OUT/tn_agreement.txt
 import csv, glob, json, sys
