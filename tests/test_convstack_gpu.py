@@ -3,6 +3,7 @@ F.conv1d / F.conv_transpose1d restatement, forward and backward, fp32 and bf16 (
 import pytest
 import torch
 
+import gemm_bounds as gb
 from conftest import record, rel_l2
 from oracle import cleanumamba_ref as R
 
@@ -144,7 +145,8 @@ def test_gemm_backward_epilogues_against_torch(cuda, M, N, K, dtype, tol):
     128 x 128 kernel (f32: the 256 x 128 one on the largest; asserted below -- the 256 x 256 ping-pong kernel's epilogues
     are pinned by test_dispatch_map_gpu.py on shapes the library reports as taking it):
     3 = ReLU gate from a full activation and from sign nibbles (+ ungated second output);
-    4 = GLU backward from the packed (a | b) pre-activation and from the gate-only form (+ residual)."""
+    4 = GLU backward from the packed (a | b) pre-activation and from the gate-only form (+ residual).
+    Every output is held to the whole-tensor bound and, element by element, to tests/gemm_bounds.py."""
     from cleanumamba_amd import hip
     from cleanumamba_amd.network import convstack as cs
     g = torch.Generator().manual_seed(M + N + K)
@@ -157,6 +159,13 @@ def test_gemm_backward_epilogues_against_torch(cuda, M, N, K, dtype, tol):
     desc.dtype, desc.M, desc.N, desc.K = hip.dtype_code(dtype), M, N, K
     tile = hip.lib().cum_gemm_nt_tile(ctypes.byref(desc))
     assert tile == 128 or (dtype == torch.float32 and tile == 256)      # f32: 256 x 128 from 1 024 tiles on
+    tag = f"gemm_bwd_epi[{M}x{N}x{K}-{dtype}]"
+    S = gb.abs_sum(A.cpu(), W.cpu())                                    # sum_k |a||w| of every accumulator element
+
+    def elements(name, got, want, eps_l, cols=None):
+        want = want.to(cuda)                                            # (the element-wise passes run on the GPU)
+        bound = gb.element_bound(want, eps_l.to(cuda), dtype)
+        assert record(f"{tag}.{name}.elem", gb.check_elements(got, want, bound, f"{tag}.{name}", acc_cols=cols)) <= 1
 
     # ---- epilogue 3
     Y = rn(M, N).to(cuda).to(dtype)                                     # activation whose sign gates
@@ -165,6 +174,8 @@ def test_gemm_backward_epilogues_against_torch(cuda, M, N, K, dtype, tol):
     cs.gemm(A, 0, K, W, None, out, 0, N, M, 1 << 30, 1 << 30, hip.EPI_MASK, N, res=Y, r_off=0, ldr=N, aux=ung, x_off=0, ldz=N)
     want = torch.where(Y.cpu().double() > 0, acc, torch.zeros_like(acc))
     assert rel_l2(out.float(), want) < tol and rel_l2(ung.float(), acc) < tol
+    elements("out", out, want, torch.where(Y.cpu().double() > 0, gb.acc_error(S, K), torch.zeros_like(S)))   # gated off: exact zero
+    elements("ung", ung, acc, gb.acc_error(S, K))
     bits = torch.zeros(M * N // 4, dtype=torch.uint8, device=cuda)
     yq = (Y.float().cpu() > 0).view(M, N // 4, 4).to(torch.uint8)
     bits.copy_((yq[..., 0] | yq[..., 1] << 1 | yq[..., 2] << 2 | yq[..., 3] << 3).reshape(-1).to(cuda))
@@ -179,6 +190,7 @@ def test_gemm_backward_epilogues_against_torch(cuda, M, N, K, dtype, tol):
     cs.gemm(A, 0, K, W, bias, relu_out, 0, N, M, 1 << 30, 1 << 30, hip.EPI_RELU, N, aux=nib, x_off=0, ldz=N, mask_bits=True)
     rq = (relu_out.float().cpu() > 0).view(M, N // 4, 4).to(torch.uint8)
     assert torch.equal(nib.cpu(), (rq[..., 0] | rq[..., 1] << 1 | rq[..., 2] << 2 | rq[..., 3] << 3).reshape(-1))
+    elements("relu_out", relu_out, (acc + bias.cpu().double()).clamp_min(0), gb.acc_error(S + bias.cpu().abs().double(), K))
 
     # ---- epilogue 4: d = acc + ext is the gradient of y = a * sig(b)
     ext = rn(M, N).to(cuda).to(dtype)
@@ -189,12 +201,15 @@ def test_gemm_backward_epilogues_against_torch(cuda, M, N, K, dtype, tol):
     Z = Z.to(cuda).to(dtype)
     ar, br = Z.float().cpu().view(M, N // 16, 2, 16)[:, :, 0].reshape(M, N).double(), Z.float().cpu().view(M, N // 16, 2, 16)[:, :, 1].reshape(M, N).double()
     d = acc + ext.float().cpu().double()
+    eps_d = gb.acc_error(S + ext.float().cpu().abs().double(), K)
+    pack = lambda da, db: torch.stack((da.view(M, N // 16, 16), db.view(M, N // 16, 16)), 2).reshape(M, 2 * N)
     sg = torch.sigmoid(br)
     want_dz = torch.empty(M, N // 16, 2, 16, dtype=torch.float64)
     want_dz[:, :, 0], want_dz[:, :, 1] = (d * sg).view(M, N // 16, 16), (d * ar * sg * (1 - sg)).view(M, N // 16, 16)
     dz = torch.full((M, 2 * N), float("nan"), device=cuda, dtype=dtype)
     cs.gemm(A, 0, K, W, None, dz, 0, 2 * N, M, 1 << 30, 1 << 30, hip.EPI_GLU_BWD, N, res=ext, r_off=0, ldr=N, aux=Z, x_off=0, ldz=2 * N)
     assert rel_l2(dz.float(), want_dz.view(M, 2 * N)) < tol
+    elements("dz", dz, want_dz.view(M, 2 * N), pack(*gb.glu_bwd_error(eps_d, br, a=ar)), gb.glu_bwd_acc_cols(2 * N))
     # gate-only form: b [M][N] and the saved output y
     bg = br.to(dtype).to(cuda)
     y = (ar * sg).to(dtype).to(cuda)
@@ -205,6 +220,8 @@ def test_gemm_backward_epilogues_against_torch(cuda, M, N, K, dtype, tol):
     cs.gemm(A, 0, K, W, None, dz2, 0, 2 * N, M, 1 << 30, 1 << 30, hip.EPI_GLU_BWD, N, res=ext, r_off=0, ldr=N, aux=bg, x_off=0, ldz=N,
             aux2=y, y_off=0, ldy=N, gate_only=True)
     assert rel_l2(dz2.float(), want2.view(M, 2 * N)) < tol
+    elements("dz2", dz2, want2.view(M, 2 * N), pack(*gb.glu_bwd_error(eps_d, bg.float().cpu().double(), y=y.float().cpu().double())),
+             gb.glu_bwd_acc_cols(2 * N))
 
 
 @pytest.mark.parametrize("dtype,tol", [(torch.float32, 2e-6), (torch.bfloat16, 2e-6), (torch.float16, 2e-6)])   # f32 accumulation of exact products

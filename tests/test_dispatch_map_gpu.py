@@ -14,6 +14,7 @@ import os
 import pytest
 import torch
 
+import gemm_bounds as gb
 from conftest import record, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -22,7 +23,7 @@ E8 = dict(channels_input=1, channels_output=1, channels_H=64, max_H=768, encoder
           stride=2, tsfm_n_layers=3, tsfm_n_head=8, tsfm_d_model=512, tsfm_d_inner=2048)
 B, CLIP = 16, 160000
 # output rounding of one GEMM whose f32 accumulator is exact up to summation order (as test_convstack_gpu.py)
-NT_TOL = {torch.float16: 8e-4, torch.bfloat16: 6e-3}
+NT_TOL = {torch.float16: 8e-4, torch.bfloat16: 6e-3, torch.float32: 1e-5}
 TN_TOL = 2e-6
 
 
@@ -80,8 +81,16 @@ def _nibbles(pos):
     return q[..., 0] | q[..., 1] << 1 | q[..., 2] << 2 | q[..., 3] << 3
 
 
+def _pack16(a, b):
+    """(a, b) [rows, n] -> [rows, 2 n] in the packed layout of Z and dZ: 16 a then 16 b per 32 columns."""
+    out = torch.empty(a.shape[0], a.shape[1] // 16, 2, 16, dtype=a.dtype, device=a.device)
+    out[:, :, 0], out[:, :, 1] = a.view(a.shape[0], -1, 16), b.view(b.shape[0], -1, 16)
+    return out.view(a.shape[0], -1)
+
+
 def _check_nt(cuda, dtype, key, tag):
-    """Re-issue one recorded cum_gemm_nt descriptor on seeded operands; compare out (and aux) with f64."""
+    """Re-issue one recorded cum_gemm_nt descriptor on seeded operands; compare out (and aux) with f64: the whole tensor
+    in rel-L2 and every element against its own bound (tests/gemm_bounds.py)."""
     from cleanumamba_amd import hip
     from cleanumamba_amd.network import convstack as cs
     (epi, M, N, K, lda, ldc, pitch, valid, n_store, has_res, ldr, has_aux, ldz, has_aux2, ldy, gate_only, mask_bits,
@@ -128,15 +137,31 @@ def _check_nt(cuda, dtype, key, tag):
     # ---- f64 reference, row chunks
     got_out = _rows(out, o_off, M, ldc, n_out).double()
     want_out = torch.empty(M, n_out, dtype=torch.float64, device=cuda)
-    want_aux = None
+    want_aux = got_aux = None
+    if has_aux and epi != hip.EPI_GLU_BWD and not (mask_bits and epi == hip.EPI_RELU):
+        got_aux = _rows(aux, x_off, M, ldz, N // 2 if epi == hip.EPI_GLU else n_store)
+    worst = {"out": 0.0, "aux": 0.0}
+    p_msg = pitch if pitch < (1 << 30) else None
+
+    def elements(which, got, want, eps_l, lo, live, cols=None):
+        # every element of this row chunk against its own bound; aux is compared on the rows inside a clip only, as below
+        if which == "aux":
+            want = torch.where(live[:, None], want, got.double())
+            live = None
+        bound = gb.element_bound(want, eps_l, dtype, live=live)
+        worst[which] = max(worst[which], gb.check_elements(got, want, bound, f"{tag}.{which} {key}", row0=lo, pitch=p_msg,
+                                                           acc_cols=cols))
     Wd = W.double()
     bd = bias.double() if bias is not None else torch.zeros(N, dtype=torch.float64, device=cuda)
     CH = 32768
     n16 = N // 16
     for lo in range(0, M, CH):
         hi = min(M, lo + CH)
-        acc = _rows(A, a_off + lo * lda, hi - lo, lda, K).double() @ Wd.t()
+        Ach = _rows(A, a_off + lo * lda, hi - lo, lda, K)
+        acc = Ach.double() @ Wd.t()
+        S = gb.abs_sum(Ach, W, bias if epi != hip.EPI_GLU_BWD else None)   # (GLU_BWD adds no bias)
         rl = real[lo:hi]
+        lv = rl[:, 0]
         if epi in (hip.EPI_BIAS, hip.EPI_RELU):
             v = acc + bd
             if epi == hip.EPI_RELU:
@@ -146,48 +171,71 @@ def _check_nt(cuda, dtype, key, tag):
                 if want_aux is None:
                     want_aux = torch.empty(M, n_store, dtype=torch.float64, device=cuda)
                 want_aux[lo:hi] = v[:, :n_store]
+                if got_aux is not None:
+                    elements("aux", got_aux[lo:hi], v[:, :n_store], gb.acc_error(S, K)[:, :n_store], lo, lv)
             if has_res:
-                v = torch.where(rl, v + _rows(res, r_off + lo * ldr, hi - lo, ldr, N).double(), torch.zeros_like(v))
+                rs = _rows(res, r_off + lo * ldr, hi - lo, ldr, N).double()
+                v = torch.where(rl, v + rs, torch.zeros_like(v))
+                S = S + rs.abs()
             want_out[lo:hi] = v[:, :n_store]
+            elements("out", got_out[lo:hi], v[:, :n_store], gb.acc_error(S, K)[:, :n_store], lo, lv)
         elif epi == hip.EPI_GLU:
             z = (acc + bd).view(hi - lo, N // 32, 2, 16)
             a, b = z[:, :, 0].reshape(hi - lo, N // 2), z[:, :, 1].reshape(hi - lo, N // 2)
             o = torch.where(rl, a * torch.sigmoid(b), torch.zeros_like(a))
+            eps = gb.acc_error(S, K).view(hi - lo, N // 32, 2, 16)
+            ea, eb = eps[:, :, 0].reshape(hi - lo, N // 2), eps[:, :, 1].reshape(hi - lo, N // 2)
+            eo = gb.glu_error(a, b, ea, eb)
             if has_aux:
                 assert gate_only, "the train step saves the gate-only form"
                 if want_aux is None:
                     want_aux = torch.empty(M, N // 2, dtype=torch.float64, device=cuda)
                 want_aux[lo:hi] = b
+                elements("aux", got_aux[lo:hi], b, eb, lo, lv)
             if has_res:
-                o = torch.where(rl, o + _rows(res, r_off + lo * ldr, hi - lo, ldr, N // 2).double(), torch.zeros_like(o))
+                rs = _rows(res, r_off + lo * ldr, hi - lo, ldr, N // 2).double()
+                o = torch.where(rl, o + rs, torch.zeros_like(o))
+                eo = eo + gb.acc_error(rs.abs(), K)                     # added after the activation: an addend with L = 1
             want_out[lo:hi] = o[:, :n_store]
+            elements("out", got_out[lo:hi], o[:, :n_store], eo[:, :n_store], lo, lv, gb.glu_acc_cols(n_store, cuda))
         elif epi == hip.EPI_MASK:
             v = torch.where(rl, acc + bd, torch.zeros_like(acc))
             if has_aux:
                 if want_aux is None:
                     want_aux = torch.empty(M, n_store, dtype=torch.float64, device=cuda)
                 want_aux[lo:hi] = v[:, :n_store]
+                elements("aux", got_aux[lo:hi], v[:, :n_store], gb.acc_error(S, K)[:, :n_store], lo, lv)
             gate = sign[lo:hi, :N] if sign is not None else _rows(res, r_off + lo * ldr, hi - lo, ldr, N) > 0
             want_out[lo:hi] = torch.where(gate, v, torch.zeros_like(v))[:, :n_store]
+            # a gated-off element is an exact zero: L = 0
+            elements("out", got_out[lo:hi], want_out[lo:hi], torch.where(gate, gb.acc_error(S, K), torch.zeros_like(S))[:, :n_store],
+                     lo, lv)
         else:                                                            # GLU_BWD
             d = acc[:, :n_store]
+            S = S[:, :n_store]
             if has_res:
-                d = d + _rows(res, r_off + lo * ldr, hi - lo, ldr, n_store).double()
+                rs = _rows(res, r_off + lo * ldr, hi - lo, ldr, n_store).double()
+                d, S = d + rs, S + rs.abs()
             d = torch.where(rl, d, torch.zeros_like(d))
             if gate_only:
                 bg = _rows(aux, lo * ldz, hi - lo, ldz, n_store).double()
                 y = _rows(aux2, lo * ldy, hi - lo, ldy, n_store).double()
                 sg = torch.sigmoid(bg)
                 da, db = d * sg, d * y * (1 - sg)
+                eda, edb = gb.glu_bwd_error(gb.acc_error(S, K), bg, y=y)
             else:
                 zz = _rows(aux, lo * ldz, hi - lo, ldz, 2 * n_store).double().view(hi - lo, n_store // 16, 2, 16)
                 a, bg = zz[:, :, 0].reshape(hi - lo, n_store), zz[:, :, 1].reshape(hi - lo, n_store)
                 sg = torch.sigmoid(bg)
                 da, db = d * sg, d * a * sg * (1 - sg)
-            w = want_out[lo:hi].view(hi - lo, n_store // 16, 2, 16)
-            w[:, :, 0], w[:, :, 1] = da.view(hi - lo, -1, 16), db.view(hi - lo, -1, 16)
+                eda, edb = gb.glu_bwd_error(gb.acc_error(S, K), bg, a=a)
+            want_out[lo:hi] = _pack16(da, db)
+            elements("out", got_out[lo:hi], want_out[lo:hi], _pack16(eda, edb), lo, lv, gb.glu_bwd_acc_cols(n_out, cuda))
         del acc
     assert n16 > 0
+    assert record(tag + ".out.elem", worst["out"]) <= 1
+    if got_aux is not None:
+        assert record(tag + ".aux.elem", worst["aux"]) <= 1
     err = rel_l2(got_out, want_out)
     assert record(tag + ".out", err) < tol, (tag, key, err)
     # rows outside a clip are written as zeros, never left untouched (the next GEMM reads them as padding)
@@ -208,7 +256,7 @@ def _check_nt(cuda, dtype, key, tag):
                 assert float(mag[bad].max()) < 1e-4 * float(want_aux.abs().mean()), tag + ": sign nibbles"
         else:
             live = real[:, 0]
-            got_aux = _rows(aux, x_off, M, ldz, want_aux.shape[1]).double()
+            got_aux = got_aux.double()
             assert record(tag + ".aux", rel_l2(got_aux[live], want_aux[live])) < tol, tag + ": aux"
 
 
@@ -282,18 +330,24 @@ def test_streaming_weight_gradient_kernel(cuda, dtype, shape):
     _check_tn(cuda, dtype, shape, f"tn_stream[{dtype}:{M}x{N}x{K}:ldx{shape[4]}]")
 
 
-@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
-@pytest.mark.parametrize("epi", [0, 1, 2, 3, 4])
-@pytest.mark.parametrize("kernel", ["nt9", "ring"])
-def test_ping_pong_kernel_ragged_rows_every_epilogue(cuda, dtype, epi, kernel):
-    """gemm_nt9_kernel (256 x 256 ping-pong; tile id 512) and gemm_nt_ring_kernel (128 x 256 through the three-stage ring; tile
-    id 384) on a row count that ends inside a tile (and inside a 64-row wave slab), every epilogue with its optional operands:
-    residual, pre-activation copies, sign nibbles both ways, gate-only GLU forms."""
+# kernel -> (tile id cum_gemm_nt_tile reports, (M, N, K), pitch, valid, split_k): for each kernel the smallest shape the
+# launcher gives it, M ending inside a tile and inside a 64-row wave slab, pitch / valid seams off every tile height
+RAGGED = {
+    "nt9": (512, (60000 + 77, 768, 1536), 5003, 5001, False),       # 256 x 256 ping-pong: from 224 tiles
+    "ring": (384, (10000 + 77, 768, 1536), 5003, 5001, False),      # 128 x 256 three-stage ring: from 40 tiles
+    "tile128": (128, (1000 + 77, 192, 512), 203, 201, False),       # 128 x 128
+    "splitk": (64, (1000 + 77, 96, 2048), 203, 201, True),          # 64 x 64, K split over the waves (asked for: K >= 256)
+    "f32tile256": (256, (262144 + 77, 128, 256), 5003, 5001, False),  # f32 256 x 128: K >= 256 and from 1024 tiles
+}
+
+
+def _ragged_rows_every_form(cuda, dtype, epi, kernel):
     from cleanumamba_amd import hip
-    M, N, K = (60000 + 77, 768, 1536) if kernel == "nt9" else (10000 + 77, 768, 1536)
+    tile, (M, N, K), pitch, valid, split_k = RAGGED[kernel]
     d = hip.GemmDesc()
-    d.dtype, d.M, d.N, d.K = hip.dtype_code(dtype), M, N, K
-    assert hip.lib().cum_gemm_nt_tile(ctypes.byref(d)) == (512 if kernel == "nt9" else 384)
+    d.dtype, d.M, d.N, d.K, d.allow_split_k = hip.dtype_code(dtype), M, N, K, 2 if split_k else 0
+    assert hip.lib().cum_gemm_nt_tile(ctypes.byref(d)) == tile
+    assert M % 64 % 16 and all(v % t for v in (pitch, valid) for t in (64, 128, 256)) and valid < pitch < M
     n_store = N // 2 if epi == hip.EPI_GLU else N
     cases = {
         0: [(True, N, False, 0, False, 0, False, False)],
@@ -304,9 +358,27 @@ def test_ping_pong_kernel_ragged_rows_every_epilogue(cuda, dtype, epi, kernel):
     }[epi]
     for ci, (has_res, ldr, has_aux, ldz, has_aux2, ldy, gate_only, mask_bits) in enumerate(cases):
         ldc = 2 * N if epi == hip.EPI_GLU_BWD else n_store
-        key = (epi, M, N, K, K, ldc, 5003, 5001, n_store, has_res, ldr, has_aux, ldz, has_aux2, ldy, gate_only, mask_bits,
-               False, epi != hip.EPI_GLU_BWD, None, 0, 0)
+        key = (epi, M, N, K, K, ldc, pitch, valid, n_store, has_res, ldr, has_aux, ldz, has_aux2, ldy, gate_only, mask_bits,
+               split_k, epi != hip.EPI_GLU_BWD, None, 0, 0)
         _check_nt(cuda, dtype, key, f"{kernel}.ragged[{dtype}:epi{epi}:{ci}]")
+
+
+@pytest.mark.parametrize("dtype", [torch.bfloat16, torch.float16])
+@pytest.mark.parametrize("epi", [0, 1, 2, 3, 4])
+@pytest.mark.parametrize("kernel", ["nt9", "ring", "tile128", "splitk"])
+def test_ping_pong_kernel_ragged_rows_every_epilogue(cuda, dtype, epi, kernel):
+    """gemm_nt9_kernel (256 x 256 ping-pong; tile id 512), gemm_nt_ring_kernel (128 x 256 through the three-stage ring; tile
+    id 384), gemm_nt_kernel (128 x 128; tile id 128) and gemm_nt_splitk_kernel (64 x 64; tile id 64) on a row count that
+    ends inside a tile (and inside a 64-row wave slab), every epilogue with its optional operands: residual,
+    pre-activation copies, sign nibbles both ways, gate-only GLU forms."""
+    _ragged_rows_every_form(cuda, dtype, epi, kernel)
+
+
+@pytest.mark.parametrize("epi", [0, 1, 2, 3, 4])
+def test_f32_tall_tile_kernel_ragged_rows_every_epilogue(cuda, epi):
+    """The same for the f32 instantiation of gemm_nt_kernel with 256 x 128 tiles (tile id 256); its own test because f32 is
+    no dtype of the 16-bit kernels above."""
+    _ragged_rows_every_form(cuda, torch.float32, epi, "f32tile256")
 
 
 def _e6_net(cuda):

@@ -6,6 +6,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
+import gemm_bounds as gb
 from conftest import load_ckpt, record, rel_l2
 
 pytestmark = pytest.mark.gpu
@@ -14,7 +15,8 @@ pytestmark = pytest.mark.gpu
 @pytest.mark.parametrize("dtype", [torch.float32, torch.float16])
 @pytest.mark.parametrize("shape", [(37, 114, 16), (50, 8, 114), (129, 48, 58), (64, 55, 60), (1, 114, 96)])
 def test_projection_of_any_width_forward_and_gradients(cuda, shape, dtype):
-    """_proj (cum_gemm_nt / cum_gemm_tn on padded operands) against an f64 matmul: y, dx, dW."""
+    """_proj (cum_gemm_nt / cum_gemm_tn on padded operands) against an f64 matmul: y, dx, dW; y and dx, each one
+    cum_gemm_nt call, element by element as well (tests/gemm_bounds.py; zero padding adds nothing to a sum)."""
     from cleanumamba_amd.mamba_ssm.modules.mamba_simple import _proj
     M, K, N = shape
     g = torch.Generator(device=cuda).manual_seed(M * 7 + K)
@@ -31,6 +33,12 @@ def test_projection_of_any_width_forward_and_gradients(cuda, shape, dtype):
     assert record(f"proj_any[{shape}-{dtype}].y", rel_l2(y, want)) < tol
     dyd = dy.to(y.dtype).double()
     assert rel_l2(x.grad, dyd @ wd) < tol
+    wq, dyq = w.detach().to(dtype), dy.to(y.dtype).reshape(-1, N)
+    for name, got, ref, eps in (("y", y.detach(), want, gb.acc_error(gb.abs_sum(x.detach().reshape(-1, K), wq), K)),
+                                ("dx", x.grad, dyd @ wd, gb.acc_error(gb.abs_sum(dyq, wq.t()), N))):
+        ref = ref.reshape(3 * M, -1)
+        ratio = gb.check_elements(got.reshape(3 * M, -1), ref, gb.element_bound(ref, eps, dtype), f"proj_any[{shape}-{dtype}].{name}")
+        assert record(f"proj_any[{shape}-{dtype}].{name}.elem", ratio) <= 1
     assert rel_l2(w.grad, (dyd.reshape(-1, N).t() @ x.detach().double().reshape(-1, K))) < tol
 
 
