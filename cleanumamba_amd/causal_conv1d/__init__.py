@@ -75,10 +75,42 @@ class CausalConv1dFn(torch.autograd.Function):
         return dx, dw, db, None
 
 
-def causal_conv1d_fn(x, weight, bias=None, activation=None):
+@torch.no_grad()
+def _conv_from(x, weight, bias, activation, state):
+    """Forward continuing from ``state`` (B, D, W) f32, which is left holding the last W inputs (cum_causal_conv1d_fwd_from;
+    the C entry takes distinct entering / leaving states: the leaving one is a temporary copied back)."""
+    if activation not in (None, "silu", "swish"):
+        raise NotImplementedError("activation must be None, silu, or swish")
+    hip.require_gpu(x, any_dtype=True)
+    hip.require_gpu(weight, bias, state)
+    if x.dim() != 3 or weight.dim() != 2 or weight.shape[0] != x.shape[1]:
+        raise RuntimeError("causal_conv1d: x must be (B, D, L) and weight (D, W)")
+    if tuple(state.shape) != (x.shape[0], x.shape[1], weight.shape[1]):
+        raise RuntimeError("causal_conv1d: state must be (B, D, W)")
+    weight = weight.contiguous()
+    bias = None if bias is None else bias.contiguous()
+    s_in = state.contiguous()
+    s_out = torch.empty_like(s_in)
+    y = _alloc_like(x)
+    s = _shape(x, y, weight.shape[1], activation is not None)
+    with torch.cuda.device(x.device):
+        hip.check(hip.lib().cum_causal_conv1d_fwd_from(ctypes.byref(s), hip.ptr(x), hip.ptr(weight), hip.ptr(bias),
+                                                       hip.ptr(y), hip.ptr(s_in), hip.ptr(s_out), hip.stream_ptr()))
+    state.copy_(s_out)
+    return y
+
+
+def causal_conv1d_fn(x, weight, bias=None, activation=None, *, state=None):
+    """``state`` (B, D, W) f32: the conv continues a sequence -- times before x read the state's newest W - 1 columns
+    instead of zero, and the state is updated in place to the last W inputs (the layout causal_conv1d_update keeps).
+    Inference only."""
     in_dtype = x.dtype
     if in_dtype not in hip.IO_TYPES:
         x = x.float()
+    if state is not None:
+        if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (x, weight, bias)):
+            raise RuntimeError("causal_conv1d_fn: state is inference only (run under torch.no_grad())")
+        return _conv_from(x, weight.float(), None if bias is None else bias.float(), activation, state).to(in_dtype)
     return CausalConv1dFn.apply(x, weight.float(), None if bias is None else bias.float(), activation).to(in_dtype)
 
 

@@ -277,6 +277,40 @@ __global__ __launch_bounds__(256) void dwconv_bwd_finalize_kernel(const float *w
   }
 }
 
+// cum_causal_conv1d_fwd_from, after the plain forward has run: the first W - 1 outputs again, with the times t < 0 read
+// from state_in's newest W - 1 columns instead of zero (same fma order as dwconv_fwd_kernel: a zero state gives the same
+// bits), and state_out[j] = the input at time L - W + j (from state_in where that is negative).  One thread per (b, d);
+// state layout (batch, dim, W) f32, what dwconv_update_kernel keeps.
+template <typename TIO>
+__global__ __launch_bounds__(256) void dwconv_enter_kernel(const ConvParams p, const float *__restrict__ state_in,
+                                                           float *__restrict__ state_out) {
+  const int64_t i = blockIdx.x * (int64_t)blockDim.x + threadIdx.x;
+  if (i >= (int64_t)p.s.batch * p.s.dim) return;
+  const int b = i / p.s.dim, d = i % p.s.dim;
+  const int W = p.s.width, L = p.s.len;
+  const TIO *xp = static_cast<const TIO *>(p.x) + b * p.s.x_sb + d * p.s.x_sd;
+  TIO *yp = static_cast<TIO *>(p.y) + b * p.s.y_sb + d * p.s.y_sd;
+  const float *si = state_in ? state_in + i * W : nullptr;
+  auto in = [&](int t) -> float {          // t in [-W, L)
+    if (t >= 0) return (float)xp[(int64_t)t * p.s.x_sl];
+    return si ? si[W + t] : 0.f;
+  };
+  if (si) {
+    const float bs = p.bias ? p.bias[d] : 0.f;
+    const int head = (W - 1) < L ? (W - 1) : L;
+    for (int t = 0; t < head; ++t) {
+      float acc = bs;
+      for (int k = 0; k < W; ++k) acc = fmaf(p.w[d * W + k], in(t - (W - 1) + k), acc);
+      if (p.s.silu) acc = acc * sigmoidf_(acc);
+      yp[(int64_t)t * p.s.y_sl] = (TIO)acc;
+    }
+  }
+  if (state_out) {
+    float *so = state_out + i * W;
+    for (int j = 0; j < W; ++j) so[j] = in(L - W + j);
+  }
+}
+
 __global__ void dwconv_update_kernel(int batch, int dim, int W, float *__restrict__ state, const float *__restrict__ x,
                                      const float *__restrict__ w, const float *__restrict__ bias, int silu,
                                      float *__restrict__ y) {
@@ -336,6 +370,34 @@ extern "C" int cum_causal_conv1d_fwd(const cum_conv_shape *s, const void *x, con
     default: CUM_DW_FWD(4); break;
   }
 #undef CUM_DW_FWD
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_causal_conv1d_fwd_from(const cum_conv_shape *s, const void *x, const float *weight, const float *bias,
+                                          void *y, const float *state_in, float *state_out, void *stream) {
+  if (int rc = conv_check(s)) return rc;
+  const size_t state_bytes = sizeof(float) * (size_t)s->batch * s->dim * s->width;
+  if (state_in && state_out && state_bytes) {
+    const char *a = reinterpret_cast<const char *>(state_in), *b = reinterpret_cast<const char *>(state_out);
+    CUM_REQUIRE(a + state_bytes <= b || b + state_bytes <= a, "conv_fwd_from: state_in and state_out must not overlap");
+  }
+  if (s->batch == 0) return CUM_OK;
+  hipStream_t st = (hipStream_t)stream;
+  if (s->len == 0) {                     // nothing entered: the state leaves as it came
+    if (state_out && state_in) (void)hipMemcpyAsync(state_out, state_in, state_bytes, hipMemcpyDeviceToDevice, st);
+    else if (state_out) (void)hipMemsetAsync(state_out, 0, state_bytes, st);
+    return CUM_OK;
+  }
+  if (int rc = cum_causal_conv1d_fwd(s, x, weight, bias, y, stream)) return rc;
+  if (!state_in && !state_out) return CUM_OK;
+  ConvParams p{};
+  p.s = *s; p.x = x; p.w = weight; p.bias = bias; p.y = y;
+  const int64_t total = (int64_t)s->batch * s->dim;
+  const dim3 grid((unsigned)((total + 255) / 256)), block(256);
+  if (s->io_dtype == CUM_BF16) hipLaunchKernelGGL((dwconv_enter_kernel<__bf16>), grid, block, 0, st, p, state_in, state_out);
+  else if (s->io_dtype == CUM_F16) hipLaunchKernelGGL((dwconv_enter_kernel<f16>), grid, block, 0, st, p, state_in, state_out);
+  else hipLaunchKernelGGL((dwconv_enter_kernel<float>), grid, block, 0, st, p, state_in, state_out);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

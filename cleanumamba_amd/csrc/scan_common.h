@@ -42,7 +42,27 @@ struct ScanParams {
   // segmented (time-parallel) forward, scan_seg.hip: nseg segments of seg_chunks chunks; carry = its workspace
   int nseg, seg_chunks;
   float *carry;
+  // forward, optional (cum_selective_scan_fwd_from): the state entering t = 0, last_state's layout; NULL = zero
+  const float *init_state;
 };
+
+// The entering state of the wave's slice [n0, n0 + nvalid) of channel dc (a valid channel for every lane) into the
+// registers the recurrence walks, where the kernels set x = 0.  Padding states stay 0.  Called only by the ENTER
+// instantiations of the forward kernels (launched when init_state is given): the ones the plain entries reach carry
+// no trace of it -- a run-time test of the pointer cost them a register and scalar spills (profiles/scan_fwd_resources.md).
+__device__ __forceinline__ void scan_enter(const ScanParams &p, int b, int dc, int n0, int nvalid, float (&x)[NS]) {
+  const float *is = p.init_state + ((int64_t)b * p.s.dim + dc) * p.s.dstate + n0;
+#pragma unroll
+  for (int j = 0; j < NS; ++j)
+    if (j < nvalid) x[j] = is[j];
+}
+template <int NP2>
+__device__ __forceinline__ void scan_enter(const ScanParams &p, int b, int dc, int n0, int nvalid, f2 (&x)[NP2]) {
+  const float *is = p.init_state + ((int64_t)b * p.s.dim + dc) * p.s.dstate + n0;
+#pragma unroll
+  for (int j = 0; j < 2 * NP2; ++j)
+    if (j < nvalid) x[j / 2][j % 2] = is[j];
+}
 
 // Checkpoint buffer, d_state <= 16 (one or two waves per workgroup): the NS states a lane (channel d) of wave w holds,
 // entering half h of chunk c of clip b, as 32 contiguous bytes -- [(b, c, h, w, d)][NS]: two 16-byte accesses per lane,

@@ -13,7 +13,7 @@
 
 namespace cum {
 
-template <int NW, bool FAST, typename TIO>
+template <int NW, bool FAST, typename TIO, bool ENTER = false>
 __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanParams p) {
   constexpr int K = (TB + NW - 1) / NW;  // (t, d) rows per thread in phases A / C
   __shared__ float s_dt[TB][64];
@@ -38,6 +38,7 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanParams p) {
     Ap[j] = (j < nvalid) ? a : 0.f;
     x[j] = 0.f;
   }
+  if constexpr (ENTER) scan_enter(p, b, dc, n0, nvalid, x);
   const float Dd = p.D ? p.D[dc] : 0.f;
   const float bias = p.bias ? p.bias[dc] : 0.f;
   const TIO *up = static_cast<const TIO *>(p.u) + b * p.s.u_sb + dc * p.s.u_sd;
@@ -163,7 +164,7 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_kernel(const ScanParams p) {
 // tiles with coalesced vector loads (any strides, padding masked to zero), phase B reads each wave's 8-float slice
 // with wave-uniform ds_read_b128 (LDS broadcast), one step ahead.  LDS returns in order, so waits are counted and
 // nothing in the step loop waits on the scalar cache.
-template <int NW, typename TIO>
+template <int NW, typename TIO, bool ENTER = false>
 __global__ __launch_bounds__(NW * 64) void scan_fwd_lds_kernel(const ScanParams p) {
   constexpr int K = (TB + NW - 1) / NW;
   constexpr int NT = NW * 64;
@@ -193,6 +194,7 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_lds_kernel(const ScanParams 
     Ap[j / 2][j % 2] = (j < nvalid) ? a : 0.f;
     x[j / 2][j % 2] = 0.f;
   }
+  if constexpr (ENTER) scan_enter(p, b, dc, n0, nvalid, x);
   const float Dd = p.D ? p.D[dc] : 0.f;
   const float bias = p.bias ? p.bias[dc] : 0.f;
   const TIO *up = static_cast<const TIO *>(p.u) + b * p.s.u_sb + dc * p.s.u_sd;
@@ -331,7 +333,7 @@ __global__ __launch_bounds__(NW * 64) void scan_fwd_lds_kernel(const ScanParams 
 // PB = 16: a whole chunk of rows in flight (the wave that runs alone on its SIMD); PB = 8: half a chunk -- 48 registers
 // fewer (164 -> <= 128 at d_state 8), i.e. FOUR waves per SIMD instead of three, for grids that bring more than three
 // waves per SIMD anyway (batch 128 at D = 2048: 4096 waves = one resident round instead of a 3 + 1 split).
-template <int NW, typename TIO, int PB>
+template <int NW, typename TIO, int PB, bool ENTER = false>
 __global__ __launch_bounds__(64) void scan_fwd_small_kernel(const ScanParams p) {
   constexpr int NPD = NW * NS;           // padded state count (8 or 16)
   constexpr int NP2 = NPD / 2;
@@ -356,6 +358,7 @@ __global__ __launch_bounds__(64) void scan_fwd_small_kernel(const ScanParams p) 
     Ap[j / 2][j % 2] = j < N ? a : 0.f;
     x[j / 2][j % 2] = 0.f;
   }
+  if constexpr (ENTER) scan_enter(p, b, dc, 0, N, x);
   const float Dd = p.D ? p.D[dc] : 0.f;
   const float bias = p.bias ? p.bias[dc] : 0.f;
   const TIO *up = static_cast<const TIO *>(p.u) + b * p.s.u_sb + dc * p.s.u_sd;
@@ -468,7 +471,7 @@ __global__ __launch_bounds__(64) void scan_fwd_small_kernel(const ScanParams p) 
 // the predicated form.  (Raw buffer loads -- resource + vector offset + scalar row offset, no vector address arithmetic at
 // all -- were tried: the compiler wraps them in waterfall loops wherever it cannot prove the row offset uniform, 183
 // registers.)
-template <int NW, typename TIO, int PB>
+template <int NW, typename TIO, int PB, bool ENTER = false>
 __global__ __launch_bounds__(64) void scan_fwd_small_fast_kernel(const ScanParams p) {
   constexpr int NPD = NW * NS;
   constexpr int NP2 = NPD / 2;
@@ -490,6 +493,7 @@ __global__ __launch_bounds__(64) void scan_fwd_small_fast_kernel(const ScanParam
     Ap[j / 2][j % 2] = j < N ? a : 0.f;
     x[j / 2][j % 2] = 0.f;
   }
+  if constexpr (ENTER) scan_enter(p, b, d, 0, N, x);
   const float Dd = p.D ? p.D[d] : 0.f;
   const float bias = p.bias ? p.bias[d] : 0.f;
   const TIO *up = static_cast<const TIO *>(p.u) + b * p.s.u_sb;
@@ -616,7 +620,7 @@ __global__ __launch_bounds__(64) void scan_fwd_small_fast_kernel(const ScanParam
 // rows already in flight in its registers, softplus / gate / skip term into an LDS slot, B_t / C_t tile staged --
 // while the consumers walk block p's recurrence and write the output themselves.  One workgroup barrier per 16-step
 // block; both roles cost about the same per step, so the step time roughly halves.
-template <int NW, typename TIO>
+template <int NW, typename TIO, bool ENTER = false>
 __global__ __launch_bounds__((NW + 1) * 64) void scan_fwd_ws_kernel(const ScanParams p) {
   constexpr int PB = TB;
   constexpr int NPD = NW * NS;
@@ -714,6 +718,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void scan_fwd_ws_kernel(const ScanPa
     Ap[j / 2][j % 2] = (j < nvalid) ? a : 0.f;
     x[j / 2][j % 2] = 0.f;
   }
+  if constexpr (ENTER) scan_enter(p, b, dc, n0, nvalid, x);
   TIO *ob = static_cast<TIO *>(p.out) + b * p.s.o_sb;
   const int o_lo = dc * (int)p.s.o_sd;
   const int o_sl = (int)p.s.o_sl;
@@ -812,7 +817,7 @@ __global__ __launch_bounds__((NW + 1) * 64) void scan_fwd_ws_kernel(const ScanPa
 // barrier per unit.  In interval i the loader writes operand slot (i + 1) & 1 / finisher-operand slot (i + 1) % 3, the
 // consumers read slot i & 1 and write partial-sum slot i & 1, the finisher reads partial sums (i - 1) & 1 and its
 // operands (i - 1) % 3.
-template <int NW, typename TIO>
+template <int NW, typename TIO, bool ENTER = false>
 __global__ __launch_bounds__((NW + 2) * 64) void scan_fwd_ws3_kernel(const ScanParams p) {
   constexpr int NP = NW * NS;                    // padded state count
   constexpr int BCE = SUB * 2 * NP / 64;         // B / C tile elements per loader lane and unit
@@ -931,6 +936,7 @@ __global__ __launch_bounds__((NW + 2) * 64) void scan_fwd_ws3_kernel(const ScanP
     Ap[j / 2][j % 2] = (j < nvalid) ? a : 0.f;
     x[j / 2][j % 2] = 0.f;
   }
+  if constexpr (ENTER) scan_enter(p, b, dc, n0, nvalid, x);
   for (int i = 0; i < nu + 1; ++i) {
     __syncthreads();
     if (i >= nu) break;                           // (the drain interval belongs to the finisher)
@@ -1009,7 +1015,8 @@ __global__ void state_update_kernel(int batch, int dim, int N, float *__restrict
   out[i] = y;
 }
 
-template <int NW, typename TIO>
+// ENTER: the instantiations that load ScanParams::init_state (cum_selective_scan_fwd_from)
+template <int NW, typename TIO, bool ENTER>
 static int launch_fwd_io(const ScanParams &p, hipStream_t st) {
   dim3 grid((p.s.dim + 63) / 64, p.s.batch), block(NW * 64);
   if constexpr (NW <= 2) {
@@ -1032,11 +1039,11 @@ static int launch_fwd_io(const ScanParams &p, hipStream_t st) {
                         ext * p.s.dt_sd < (1 << 30) && ext * p.s.z_sd < (1 << 30) && ext * p.s.o_sd < (1 << 30) &&
                         cum_knob("CUM_SCAN_SMALL_FAST", 1) != 0;
       if (waves > half_min) {
-        if (fast) hipLaunchKernelGGL((scan_fwd_small_fast_kernel<NW, TIO, SUB>), grid, dim3(64), 0, st, p);
-        else hipLaunchKernelGGL((scan_fwd_small_kernel<NW, TIO, SUB>), grid, dim3(64), 0, st, p);
+        if (fast) hipLaunchKernelGGL((scan_fwd_small_fast_kernel<NW, TIO, SUB, ENTER>), grid, dim3(64), 0, st, p);
+        else hipLaunchKernelGGL((scan_fwd_small_kernel<NW, TIO, SUB, ENTER>), grid, dim3(64), 0, st, p);
       } else {
-        if (fast && (NW == 2 || waves <= 2048)) hipLaunchKernelGGL((scan_fwd_small_fast_kernel<NW, TIO, TB>), grid, dim3(64), 0, st, p);
-        else hipLaunchKernelGGL((scan_fwd_small_kernel<NW, TIO, TB>), grid, dim3(64), 0, st, p);
+        if (fast && (NW == 2 || waves <= 2048)) hipLaunchKernelGGL((scan_fwd_small_fast_kernel<NW, TIO, TB, ENTER>), grid, dim3(64), 0, st, p);
+        else hipLaunchKernelGGL((scan_fwd_small_kernel<NW, TIO, TB, ENTER>), grid, dim3(64), 0, st, p);
       }
       CUM_CHECK_LAUNCH();
       return CUM_OK;
@@ -1045,7 +1052,7 @@ static int launch_fwd_io(const ScanParams &p, hipStream_t st) {
     if (v == 1)
 #endif
     {
-      hipLaunchKernelGGL((scan_fwd_ws_kernel<NW, TIO>), grid, dim3((NW + 1) * 64), 0, st, p);
+      hipLaunchKernelGGL((scan_fwd_ws_kernel<NW, TIO, ENTER>), grid, dim3((NW + 1) * 64), 0, st, p);
       CUM_CHECK_LAUNCH();
       return CUM_OK;
     }
@@ -1057,31 +1064,36 @@ static int launch_fwd_io(const ScanParams &p, hipStream_t st) {
 #ifdef CUM_AB   // CUM_SCAN_FWD_LDS=0: B_t / C_t through the constant address space (s_load) instead of the LDS tile
   if (cum_knob("CUM_SCAN_FWD_LDS", 1) == 0) {
     if (p.s.B_sn == 1 && p.s.C_sn == 1 && p.s.dstate == NS * NW)
-      hipLaunchKernelGGL((scan_fwd_kernel<NW, true, TIO>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((scan_fwd_kernel<NW, true, TIO, ENTER>), grid, block, 0, st, p);
     else
-      hipLaunchKernelGGL((scan_fwd_kernel<NW, false, TIO>), grid, block, 0, st, p);
+      hipLaunchKernelGGL((scan_fwd_kernel<NW, false, TIO, ENTER>), grid, block, 0, st, p);
     CUM_CHECK_LAUNCH();
     return CUM_OK;
   }
 #endif
 #ifdef CUM_AB   // CUM_SCAN_FWD_WS3=1: loader / consumer / finisher waves (scan_fwd_ws3_kernel: measured 49 % slower at N = 64)
     if (cum_knob("CUM_SCAN_FWD_WS3", 0) == 1) {
-      hipLaunchKernelGGL((scan_fwd_ws3_kernel<NW, TIO>), grid, dim3((NW + 2) * 64), 0, st, p);
+      hipLaunchKernelGGL((scan_fwd_ws3_kernel<NW, TIO, ENTER>), grid, dim3((NW + 2) * 64), 0, st, p);
       CUM_CHECK_LAUNCH();
       return CUM_OK;
     }
 #endif
-    hipLaunchKernelGGL((scan_fwd_lds_kernel<NW, TIO>), grid, block, 0, st, p);
+    hipLaunchKernelGGL((scan_fwd_lds_kernel<NW, TIO, ENTER>), grid, block, 0, st, p);
     CUM_CHECK_LAUNCH();
   }
   return CUM_OK;
 }
 
+template <int NW, bool ENTER>
+static int launch_fwd_enter(const ScanParams &p, hipStream_t st) {
+  if (p.s.io_dtype == CUM_BF16) return launch_fwd_io<NW, __bf16, ENTER>(p, st);
+  if (p.s.io_dtype == CUM_F16) return launch_fwd_io<NW, f16, ENTER>(p, st);
+  return launch_fwd_io<NW, float, ENTER>(p, st);
+}
+
 template <int NW>
 static int launch_fwd(const ScanParams &p, hipStream_t st) {
-  if (p.s.io_dtype == CUM_BF16) return launch_fwd_io<NW, __bf16>(p, st);
-  if (p.s.io_dtype == CUM_F16) return launch_fwd_io<NW, f16>(p, st);
-  return launch_fwd_io<NW, float>(p, st);
+  return p.init_state ? launch_fwd_enter<NW, true>(p, st) : launch_fwd_enter<NW, false>(p, st);
 }
 
 int scan_check_shape(const cum_scan_shape *s) {
@@ -1144,16 +1156,24 @@ extern "C" int32_t cum_scan_fwd_keeps_y(int32_t batch, int32_t dim, int32_t dsta
   return 1;
 }
 
-extern "C" int cum_selective_scan_fwd_ws(const cum_scan_shape *s, const void *u, const void *delta, const float *A,
-                                         const float *Bm, const float *Cm, const float *D, const void *z,
-                                         const float *delta_bias, void *out, void *y_pre, float *last_state, float *ckpt,
-                                         float *workspace, void *stream) {
+// Both forward entries.  init_state: the state entering t = 0 (cum_selective_scan_fwd_from), NULL = zero.
+static int scan_fwd_run(const cum_scan_shape *s, const void *u, const void *delta, const float *A, const float *Bm,
+                        const float *Cm, const float *D, const void *z, const float *delta_bias, void *out, void *y_pre,
+                        const float *init_state, float *last_state, float *ckpt, float *workspace, void *stream) {
   if (int rc = scan_check_shape(s)) return rc;
-  if (s->batch == 0) return CUM_OK;
   hipStream_t st = (hipStream_t)stream;
+  const size_t state_bytes = sizeof(float) * (size_t)s->batch * s->dim * s->dstate;
+  if (init_state && last_state && state_bytes) {
+    // later segments of the time-parallel form read the former while its last segment writes the latter
+    const char *a = reinterpret_cast<const char *>(init_state), *b = reinterpret_cast<const char *>(last_state);
+    CUM_REQUIRE(a + state_bytes <= b || b + state_bytes <= a, "scan_fwd_from: init_state and last_state must not overlap");
+  }
+  if (s->batch == 0) return CUM_OK;
   if (s->len == 0) {  // empty sequences carry null data pointers
-    if (last_state)
-      (void)hipMemsetAsync(last_state, 0, sizeof(float) * (size_t)s->batch * s->dim * s->dstate, st);
+    if (last_state && init_state)
+      (void)hipMemcpyAsync(last_state, init_state, state_bytes, hipMemcpyDeviceToDevice, st);
+    else if (last_state)
+      (void)hipMemsetAsync(last_state, 0, state_bytes, st);
     return CUM_OK;
   }
   CUM_REQUIRE(u && delta && A && Bm && Cm && out, "scan_fwd: null tensor");
@@ -1162,6 +1182,7 @@ extern "C" int cum_selective_scan_fwd_ws(const cum_scan_shape *s, const void *u,
   p.u = u; p.delta = delta; p.A = A; p.Bm = Bm; p.Cm = Cm; p.D = D; p.z = z; p.bias = delta_bias;
   p.out = out; p.last_state = last_state; p.ckpt = ckpt;
   p.ypre = y_pre;
+  p.init_state = init_state;
   CUM_REQUIRE(!y_pre || cum_scan_fwd_keeps_y(s->batch, s->dim, s->dstate, s->len, workspace != nullptr),
               "scan_fwd: y_pre is kept only where cum_scan_fwd_keeps_y says so");
   p.nchunks = (s->len + TB - 1) / TB;
@@ -1183,6 +1204,21 @@ extern "C" int cum_selective_scan_fwd_ws(const cum_scan_shape *s, const void *u,
     case 7: return launch_fwd<7>(p, st);
     default: return launch_fwd<8>(p, st);
   }
+}
+
+extern "C" int cum_selective_scan_fwd_ws(const cum_scan_shape *s, const void *u, const void *delta, const float *A,
+                                         const float *Bm, const float *Cm, const float *D, const void *z,
+                                         const float *delta_bias, void *out, void *y_pre, float *last_state, float *ckpt,
+                                         float *workspace, void *stream) {
+  return scan_fwd_run(s, u, delta, A, Bm, Cm, D, z, delta_bias, out, y_pre, nullptr, last_state, ckpt, workspace, stream);
+}
+
+extern "C" int cum_selective_scan_fwd_from(const cum_scan_shape *s, const void *u, const void *delta, const float *A,
+                                           const float *Bm, const float *Cm, const float *D, const void *z,
+                                           const float *delta_bias, void *out, const float *init_state,
+                                           float *last_state, float *workspace, void *stream) {
+  return scan_fwd_run(s, u, delta, A, Bm, Cm, D, z, delta_bias, out, nullptr, init_state, last_state, nullptr, workspace,
+                      stream);
 }
 
 extern "C" int cum_selective_state_update(int32_t batch, int32_t dim, int32_t dstate, float *state, const float *x,

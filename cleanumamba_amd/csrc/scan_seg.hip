@@ -11,7 +11,8 @@
 //   pass 1  (scan_seg_kernel<.., 1>, grid x S): every segment is walked from a ZERO state: x_end^0[d, n], and
 //           sum_t delta'_t[d].  The segment's decay needs no product over time: a_t = exp(delta'_t A), so
 //           prod_t a_t = exp(A sum_t delta'_t).
-//   carry   (prologue of pass 2): per (b, d, n), sequentially over the earlier segments: X_0 = 0,
+//   carry   (prologue of pass 2): per (b, d, n), sequentially over the earlier segments: X_0 = 0 (ENTER: the state
+//           entering the sequence, cum_selective_scan_fwd_from),
 //           X_{s+1} = exp2(A log2e * sum delta'_s) X_s + x_end^0_s  -- the true state entering every segment.
 //   pass 2  (scan_seg_kernel<.., 2>, grid x S): every segment re-walked from X_s with outputs, the z gate, the saved
 //           states of the backward (same checkpoint layout: scan_bwd*.hip are unchanged) and last_state.
@@ -24,7 +25,7 @@
 
 namespace cum {
 
-template <int NW, typename TIO, int PASS>
+template <int NW, typename TIO, int PASS, bool ENTER = false>
 __global__ __launch_bounds__(NW * 64) void scan_seg_kernel(const ScanParams p) {
   constexpr int K = (TB + NW - 1) / NW;
   constexpr int NT = NW * 64;
@@ -60,6 +61,9 @@ __global__ __launch_bounds__(NW * 64) void scan_seg_kernel(const ScanParams p) {
     x[j / 2][j % 2] = 0.f;
   }
   if constexpr (OUT) {
+    // X_0: the state entering the sequence (cum_selective_scan_fwd_from), else zero.  Pass 1 walks every segment from
+    // zero regardless: the recurrence is linear, so segment 0's effect on an entering state is its decay times it.
+    if constexpr (ENTER) scan_enter(p, b, dc, n0, nvalid, x);
     // The true entering state: compose the (decay, end state) pairs of all earlier segments, in order.  seg - 1 dependent
     // exp2 + fma per state on loads that do not depend on each other (a separate carry launch between the passes cost
     // more than these few L2 reads: its own prologue, a launch boundary, and a second trip of the states through memory).
@@ -289,7 +293,8 @@ static int launch_seg_io(const ScanParams &p, hipStream_t st) {
   dim3 grid(p.ngroups, p.s.batch, p.nseg), grid1(p.ngroups, p.s.batch, p.nseg - 1), block(NW * 64);
   hipLaunchKernelGGL((scan_seg_kernel<NW, TIO, 1>), grid1, block, 0, st, p);
   CUM_CHECK_LAUNCH();
-  hipLaunchKernelGGL((scan_seg_kernel<NW, TIO, 2>), grid, block, 0, st, p);
+  if (p.init_state) hipLaunchKernelGGL((scan_seg_kernel<NW, TIO, 2, true>), grid, block, 0, st, p);
+  else hipLaunchKernelGGL((scan_seg_kernel<NW, TIO, 2>), grid, block, 0, st, p);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

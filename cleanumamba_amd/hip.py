@@ -90,6 +90,7 @@ SIGNATURES = {
     "cum_selective_scan_fwd": (c_i32, [ctypes.POINTER(ScanShape)] + [_P] * 12),
     "cum_scan_fwd_workspace_elems": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "cum_selective_scan_fwd_ws": (c_i32, [ctypes.POINTER(ScanShape)] + [_P] * 14),
+    "cum_selective_scan_fwd_from": (c_i32, [ctypes.POINTER(ScanShape)] + [_P] * 13),
     "cum_scan_fwd_keeps_y": (c_i32, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "cum_scan_bwd_workspace_elems": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "cum_selective_scan_bwd": (c_i32, [ctypes.POINTER(ScanShape), ctypes.POINTER(ScanGradStrides)] + [_P] * 21),
@@ -98,6 +99,7 @@ SIGNATURES = {
     "cum_selective_state_update": (c_i32, [c_i32, c_i32, c_i32, _P, _P, _P, _P, _P, c_i64, _P, c_i64,
                                            _P, _P, _P, c_i32, _P, _P]),
     "cum_causal_conv1d_fwd": (c_i32, [ctypes.POINTER(ConvShape)] + [_P] * 5),
+    "cum_causal_conv1d_fwd_from": (c_i32, [ctypes.POINTER(ConvShape)] + [_P] * 7),
     "cum_conv_bwd_workspace_elems": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "cum_causal_conv1d_bwd": (c_i32, [ctypes.POINTER(ConvShape)] + [_P] * 5 + [c_i64] * 3 + [_P] * 4),
     "cum_causal_conv1d_update": (c_i32, [c_i32, c_i32, c_i32, _P, _P, _P, _P, c_i32, _P, _P]),

@@ -331,9 +331,15 @@ class Mamba(nn.Module):
         conv_state, ssm_state = None, None
         if inference_params is not None:
             conv_state, ssm_state = self._get_states_from_cache(inference_params, batch)
-            if inference_params.seqlen_offset > 0:
+            if inference_params.seqlen_offset > 0 and seqlen == 1:
                 out, _, _ = self.step(hidden_states, conv_state, ssm_state)
                 return out
+        # seqlen_offset > 0 with more than one token: the sequence continues from the cached states, which are left
+        # holding the state after these tokens (conv and scan with an entering state)
+        carry = inference_params is not None and inference_params.seqlen_offset > 0
+        if carry and causal_conv1d_fn is None:
+            raise RuntimeError("Mamba.forward: continuing from cached states needs causal_conv1d_fn (the nn.Conv1d path "
+                               "has no entering state)")
 
         d_inner = self.in_proj.weight.shape[0] // 2
         dt_rank = self.dt_proj.weight.shape[1]
@@ -353,9 +359,11 @@ class Mamba(nn.Module):
                 return _proj(y, self.out_proj.weight, self.out_proj.bias)
         x, z = _SplitXZ.apply(xz, d_inner)                                         # (B, d_inner, L) views, channel stride 1
         A = -torch.exp(self.A_log.float())
-        if conv_state is not None:
+        if conv_state is not None and not carry:
             conv_state.copy_(F.pad(x, (d_conv - x.shape[-1], 0)))
-        if causal_conv1d_fn is None:
+        if carry:
+            x = causal_conv1d_fn(x, self.conv1d.weight.squeeze(1), self.conv1d.bias, self.activation, state=conv_state)
+        elif causal_conv1d_fn is None:
             x = self.act(self.conv1d(x)[..., :seqlen])
             x = x.transpose(1, 2).contiguous().transpose(1, 2)
         else:
@@ -365,7 +373,7 @@ class Mamba(nn.Module):
         dt = _proj(dt, self.dt_proj.weight).transpose(1, 2)                       # (B, d_inner, L); bias goes in the scan
         y = selective_scan_fn(x, dt, A, Bm.transpose(1, 2), Cm.transpose(1, 2), self.D.float(), z=z,
                               delta_bias=self.dt_proj.bias.float(), delta_softplus=True,
-                              return_last_state=ssm_state is not None)
+                              return_last_state=ssm_state is not None, **({"initial_state": ssm_state} if carry else {}))
         if ssm_state is not None:
             y, last_state = y
             ssm_state.copy_(last_state)

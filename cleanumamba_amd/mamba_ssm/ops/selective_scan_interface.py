@@ -177,9 +177,43 @@ class SelectiveScanFn(torch.autograd.Function):
         return du, ddelta, dA, dB, dC, dD, dz, dbias, None, None, None
 
 
+def scan_forward_from(u, delta, A, B, C, D, z, delta_bias, delta_softplus, initial_state):
+    """Inference forward continuing from ``initial_state`` (B, D, N) f32 (cum_selective_scan_fwd_from): out and the
+    leaving state, a fresh tensor -- the C entry rejects overlapping entering / leaving states, so the leaving one is
+    never written over the caller's tensor; a caller that carries one tensor copies it back (double buffer)."""
+    Bm, Cm = _as3(B), _as3(C)
+    hip.require_gpu(u, delta, z, any_dtype=True)
+    hip.require_gpu(A, Bm, Cm, D, delta_bias, initial_state)
+    if delta.dtype != u.dtype or (z is not None and z.dtype != u.dtype):
+        raise RuntimeError("selective_scan: u, delta and z must share one element type")
+    bsz, dim, L = u.shape
+    N = A.shape[1]
+    if A.shape[0] != dim or Bm.shape != (bsz, N, L) or Cm.shape != (bsz, N, L) or delta.shape != u.shape:
+        raise RuntimeError("selective_scan: inconsistent shapes")
+    if tuple(initial_state.shape) != (bsz, dim, N):
+        raise RuntimeError(f"selective_scan: initial_state must be (B, D, N) = {(bsz, dim, N)}")
+    A = A.contiguous()
+    D = None if D is None else D.contiguous()
+    delta_bias = None if delta_bias is None else delta_bias.contiguous()
+    init = initial_state.contiguous()
+    lib = hip.lib()
+    out = _empty_like_layout(u)
+    last = torch.empty(bsz, dim, N, dtype=torch.float32, device=u.device)
+    s = _shape(u, delta, z, out, Bm, Cm, delta_softplus)
+    n = lib.cum_scan_fwd_workspace_elems(bsz, dim, N, L) if TIME_PARALLEL else 0
+    ws = torch.empty(n, dtype=torch.float32, device=u.device) if n > 0 else None
+    with torch.cuda.device(u.device):
+        hip.check(lib.cum_selective_scan_fwd_from(ctypes.byref(s), hip.ptr(u), hip.ptr(delta), hip.ptr(A), hip.ptr(Bm),
+                                                  hip.ptr(Cm), hip.ptr(D), hip.ptr(z), hip.ptr(delta_bias), hip.ptr(out),
+                                                  hip.ptr(init), hip.ptr(last), hip.ptr(ws), hip.stream_ptr()))
+    return out, last
+
+
 def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_softplus=False,
-                      return_last_state=False):
-    """out (and last_state (B, D, N) if requested); gate ``z`` is applied inside the kernel."""
+                      return_last_state=False, initial_state=None):
+    """out (and last_state (B, D, N) if requested); gate ``z`` is applied inside the kernel.  ``initial_state`` (B, D, N)
+    f32: the state entering t = 0 (inference only: no backward runs through a carried state); the returned last_state is
+    always a fresh tensor, so the tensor given as ``initial_state`` may be the one the caller then overwrites with it."""
     in_dtype = u.dtype
     io = in_dtype if in_dtype in hip.IO_TYPES else torch.float32
     u, delta = u.to(io), delta.to(io)
@@ -189,6 +223,13 @@ def selective_scan_fn(u, delta, A, B, C, D=None, z=None, delta_bias=None, delta_
     delta_bias = None if delta_bias is None else delta_bias.float()
     # chunk-boundary states are written only when a backward can follow
     save = torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (u, delta, A, B, C, D, z, delta_bias))
+    if initial_state is not None:
+        if save or (torch.is_grad_enabled() and initial_state.requires_grad):
+            raise RuntimeError("selective_scan_fn: initial_state is inference only -- an operand requires grad, and there "
+                               "is no backward through a carried state (run under torch.no_grad())")
+        with torch.no_grad():
+            out, last = scan_forward_from(u, delta, A, B, C, D, z, delta_bias, delta_softplus, initial_state.float())
+        return (out.to(in_dtype), last) if return_last_state else out.to(in_dtype)
     res = SelectiveScanFn.apply(u, delta, A, B, C, D, z, delta_bias, delta_softplus, return_last_state, save)
     if return_last_state:
         return res[0].to(in_dtype), res[1]

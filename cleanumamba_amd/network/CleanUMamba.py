@@ -297,10 +297,14 @@ class CleanUMamba(nn.Module):
             return dt
         return torch.float32
 
-    def _forward_fused(self, buf, B, T0, dt):
+    def _forward_fused(self, buf, B, T0, dt, carry=None):
         """Encoder, bottleneck and decoder on channels-last row buffers (network/convstack.py).
         buf: row buffer of the (B, 1, T0 = valid_length) input in element type dt.  Returns (row buffer of the output,
-        its Geo, skips deepest first as (B, C, T) views, tsfm_out)."""
+        its Geo, skips deepest first as (B, C, T) views, tsfm_out).
+        carry (network/blockdenoise.py, inference only): the input is one window of a longer signal -- its first
+        ``carry.context`` bottleneck columns were already seen by the previous window.  The Mamba blocks then run on the
+        new columns only, continuing from the states in ``carry.params``, and ``carry.join`` puts the previous window's
+        last norm_f outputs back in front for tsfm_conv2 and the decoder."""
         E = self.encoder_n_layers
         save = torch.is_grad_enabled()
         self._activate_pack_plan(dt)
@@ -336,14 +340,19 @@ class CleanUMamba(nn.Module):
         g_t = cs.Geo(B, geo.T, self.tsfm_conv1.weight.shape[0])
         hbuf = cs.Pointwise.apply(buf, self.tsfm_conv1.weight, self.tsfm_conv1.bias, None, geo, g_t)
         hidden_states = g_t.rows(hbuf)[:, :g_t.T, :g_t.C]
+        if carry is not None:
+            hidden_states = hidden_states[:, carry.context:]
         residual = None
         for layer in self.tsfm_Mamba_layers:
-            hidden_states, residual = layer(hidden_states, residual, inference_params=None)
+            hidden_states, residual = layer(hidden_states, residual,
+                                            inference_params=None if carry is None else carry.params)
         if _ln.supported(hidden_states, self.norm_f):
             hidden_states, _ = _ln.add_layer_norm(hidden_states, residual, self.norm_f)
         else:
             residual = hidden_states + residual
             hidden_states = self.norm_f(residual.to(dtype=self.norm_f.weight.dtype))
+        if carry is not None:
+            hidden_states = carry.join(hidden_states)
         tsfm_out = hidden_states.permute(0, 2, 1)
         tbuf = cs.to_rows(tsfm_out, g_t, dt)
         # tsfm_conv2 with the deepest skip added in its epilogue
@@ -368,6 +377,20 @@ class CleanUMamba(nn.Module):
                 buf = cs.ConvT4S2.apply(gbuf, dec[2].weight, dec[2].bias, dec_skips[j] if j < E - 1 else None, gg, go,
                                         j < E - 1)
         return buf, geo, [cs.from_rows(b, g) for b, g in skips], tsfm_out
+
+    # --------------------------------------------------------------- long recordings
+    def block_denoiser(self, streams, std=None, block_hops=None):
+        """A BlockDenoiser (network/blockdenoise.py): ``push(x)`` / ``finish()`` denoise a signal of any length in blocks
+        of ``block_hops`` bottleneck columns with the Mamba state carried across -- ``forward``'s result at one block's
+        memory.  std: (streams, 1) per-clip std + eps of the WHOLE signal (required when ``normalize_input``)."""
+        from .blockdenoise import BlockDenoiser
+        return BlockDenoiser(self, streams, std=std, block_hops=block_hops)
+
+    def denoise_long(self, noisy, block_size=160000, block_hops=None):
+        """``forward`` on a (B, L) / (B, 1, L) signal of any length, block by block (network/blockdenoise.py).  Host input
+        gives host output, and device memory does not depend on L."""
+        from .blockdenoise import denoise_long
+        return denoise_long(self, noisy, block_size=block_size, block_hops=block_hops)
 
     def _activate_pack_plan(self, dt):
         """One batched re-pack of all conv weights for this forward (and its backward); see cs.PackPlan.  Skipped

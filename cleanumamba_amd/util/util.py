@@ -2,6 +2,7 @@
 
 weight_scaling_init ........ src/util/util.py:174-181 (used by the model constructor)
 LinearWarmupCosineDecay .... src/util/util.py:69-161
+sampling ................... src/util/util.py:185-212 (blocks with carried state, not independent ones)
 loss_fn .................... src/util/util.py:215-327 (L1 + multi-resolution STFT; the
                              cross-entropy / distillation branches are out of scope)
 """
@@ -88,6 +89,18 @@ class _Combine(torch.autograd.Function):
     def backward(ctx, g):
         gv = (ctx.W * g[:, None].float()).sum(0)
         return (None,) + tuple(gv.unbind())
+
+
+def sampling(net, noisy_audio, split_sampling=False, block_size=1600):
+    """Denoise (the reference's src/util/util.py:185-212, same signature).  ``split_sampling=False``: ``net(noisy_audio)``
+    without grad.  ``split_sampling=True``: ``net.denoise_long(noisy_audio, block_size)`` -- deliberately NOT the
+    reference's independent blocks, which normalise every block on its own and restart the encoder, the Mamba state and
+    the decoder overlap at every block edge (a click per seam): here the blocks are windows of the whole-signal forward
+    with the Mamba state carried across, so the result is ``net(noisy_audio)`` to f32 rounding at one block's memory."""
+    if not split_sampling:
+        with torch.no_grad():
+            return net(noisy_audio)
+    return net.denoise_long(noisy_audio, block_size)
 
 
 def loss_fn(net, X, cross_entropy=None, ell_p=1, ell_p_lambda=1, stft_lambda=1, mrstftloss=None, kd_p=1,

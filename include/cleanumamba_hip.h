@@ -103,6 +103,18 @@ int cum_selective_scan_fwd_ws(const cum_scan_shape *s, const void *u, const void
  * cum_scan_fwd_keeps_y() returns 1 for the shape (the sequential kernel for d_state > 16: the E6 / E8 bottleneck). */
 int32_t cum_scan_fwd_keeps_y(int32_t batch, int32_t dim, int32_t dstate, int32_t len, int32_t with_workspace);
 
+/* Inference forward that CONTINUES a sequence: cum_selective_scan_fwd_ws without ckpt and y_pre, plus the state entering
+ * t = 0.  init_state: NULL (zero: the plain forward) or (batch, dim, dstate) contiguous f32 -- last_state's layout, so one
+ * call's last_state is the next call's init_state and a sequence cut anywhere gives the uncut outputs up to f32 rounding
+ * (the prefill of upstream's mamba_simple.py:356-371, which can hand a state out but not take one in).  Honoured by
+ * every forward kernel the dispatcher picks; in the time-parallel form it is X_0 of the carry prologue.  init_state and
+ * last_state must not overlap (later segments read the one while the last segment writes the other): CUM_EINVAL before
+ * any launch.  len == 0 copies init_state to last_state. */
+int cum_selective_scan_fwd_from(const cum_scan_shape *s, const void *u, const void *delta,
+                                const float *A, const float *Bm, const float *Cm, const float *D,
+                                const void *z, const float *delta_bias, void *out,
+                                const float *init_state, float *last_state, float *workspace, void *stream);
+
 /* Strides (batch, dim, len) of the three per-element gradient outputs. */
 typedef struct {
   int64_t du_sb, du_sd, du_sl;
@@ -167,6 +179,15 @@ typedef struct {
 
 int cum_causal_conv1d_fwd(const cum_conv_shape *s, const void *x, const float *weight,
                           const float *bias, void *y, void *stream);
+
+/* The forward continuing a sequence.  state_in, state_out: NULL or (batch, dim, width) contiguous f32, the layout
+ * cum_causal_conv1d_update keeps (column j of the state after `len` inputs = the input at time len - width + j), so a
+ * later update continues from state_out.  Times t < 0 read state_in's newest width - 1 columns instead of zero (NULL:
+ * zero); state_out takes its columns from state_in where len < width.  The two must not overlap: CUM_EINVAL before any
+ * launch. */
+int cum_causal_conv1d_fwd_from(const cum_conv_shape *s, const void *x, const float *weight,
+                               const float *bias, void *y, const float *state_in, float *state_out,
+                               void *stream);
 
 /* dy has y's strides; dx has strides (dx_sb, dx_sd, dx_sl).  dweight (dim, width),
  * dbias (dim): overwritten.  workspace: cum_conv_bwd_workspace_elems() fp32 elements. */
