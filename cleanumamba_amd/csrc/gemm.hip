@@ -27,7 +27,6 @@
 // the DMA is linear), single-buffered: 32 KB of LDS and ~110 VGPRs per workgroup let 4 workgroups
 // share a CU, and their interleaving hides the load latency (CDNA guide: the 128x128 "step-3"
 // structure).
-#include <stdlib.h>
 #include <type_traits>
 #include "common.h"
 
@@ -59,7 +58,9 @@ struct GemmParams {
   int pitch, valid;        // row m is real iff (m % pitch) < valid; other rows are stored as zeros
   int n_store;             // number of output columns to store (<= N, or N/2 for GLU); multiple of 4
   int64_t zero_head, zero_tail;
-  int rows_epilogue;       // gemm_nt8_kernel: GLU_BWD epilogue through LDS (CUM_NT8_ROWS=0 turns it off for A/B runs)
+  int rows_epilogue;       // always 1: the 16-bit kernels route their epilogues through LDS wherever nt_rows_ok() allows.
+                           // The field (and nt_rows_ok's first line) stays until a same-box timing covers its removal:
+                           // dropping it changes the argument block, and so the device code, of every NT kernel.
   int group_m;             // gemm_nt9_kernel: m-tiles an XCD walks side by side (launch_gemm_nt9)
 };
 
@@ -239,9 +240,8 @@ struct Raw4<f16> {
 // stores).  The
 // straightforward form -- load, wait, compute, store per 16x16 tile inside per-lane `continue`s -- serialised 16
 // (MASK) to 48 (GLU_BWD) memory round trips per tile.
-// NH: 64-row halves of the wave's sub-tile (1, or 2 for gemm_nt8_kernel's 128 x 64); PIPE: slabs whose loads are
-// issued ahead of the slab being finished (-1: the default of the 128-VGPR kernels, see the end of the function).
-template <typename T, int EPI, int NH = 1, int PIPE = -1>
+// NH: 64-row halves of the wave's sub-tile (1, or 2 for gemm_nt9_kernel's 128 x 64).
+template <typename T, int EPI, int NH = 1>
 __device__ __forceinline__ void nt_epilogue(const GemmParams &p, const f32x4 (*accp)[4][4], const float (&bv)[4][4],
                                             int m0, int n0, int wm0, int wn, int g, int r) {
   // lane holds D[n = nb + 4g + j][m = mb + r], j = 0..3 -> 4 consecutive channels of row m.
@@ -406,9 +406,10 @@ __device__ __forceinline__ void nt_epilogue(const GemmParams &p, const f32x4 (*a
     }
   };
   constexpr int NSL = 4 * NH;
-  // default depth: 12 loads per slab (GLU_BWD) or 16-byte f32 operands: two slabs in flight would spill at the 128-VGPR
-  // budget of 4 waves per SIMD (the f32 instantiations spilled 6-49 VGPRs with the pipelined form); else one ahead
-  constexpr int AHEAD = PIPE >= 0 ? PIPE : ((EPI == EPI_GLU_BWD || sizeof(T) == 4) ? 0 : 1);
+  // slabs whose loads are issued ahead of the slab being finished.  12 loads per slab (GLU_BWD) or 16-byte f32 operands:
+  // two slabs in flight would spill at the 128-VGPR budget of 4 waves per SIMD (the f32 instantiations spilled 6-49 VGPRs
+  // with the pipelined form); else one ahead
+  constexpr int AHEAD = (EPI == EPI_GLU_BWD || sizeof(T) == 4) ? 0 : 1;
   Slab ring[AHEAD + 1];
 #pragma unroll
   for (int sl = 0; sl < AHEAD && sl < NSL; ++sl) issue(sl, ring[sl]);
@@ -419,7 +420,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmParams &p, const f32x4 (*a
   }
 }
 
-// GLU-backward epilogue of gemm_nt8_kernel through LDS (gate-only form, full-width tiles, 16-byte aligned rows).
+// GLU-backward epilogue of the 16-bit kernels through LDS (gate-only form, full-width tiles, 16-byte aligned rows).
 //
 // In the MFMA result layout a lane touches 8 bytes of 16 different rows per instruction: 16 rows x 32 bytes.  One CU
 // sustains that pattern at 44 us per 256 x 256 tile of this epilogue however idle the rest of the chip is, against 19 us
@@ -430,7 +431,7 @@ __device__ __forceinline__ void nt_epilogue(const GemmParams &p, const f32x4 (*a
 // the MFMA layout (row stride 144 B: conflict-free 8-byte reads), and dZ leaves through a row-major staging slab (stride
 // 272 B) as 4 rows x 256 B per store instruction.  Wave-private LDS traffic needs no barrier: the LDS executes a wave's
 // instructions in order.
-// NH: 64-row halves of the wave's sub-tile (gemm_nt8_kernel: 2, gemm_nt_kernel: 1); AHEAD: slabs whose operand loads are
+// NH: 64-row halves of the wave's sub-tile (gemm_nt9_kernel: 2, gemm_nt_kernel and gemm_nt_ring_kernel: 1); AHEAD: slabs whose operand loads are
 // issued before the slab being finished (1 where registers allow, 0 in the 128-VGPR kernels).
 template <typename T, int NH, int AHEAD>
 __device__ __forceinline__ void nt_epilogue_glu_bwd_rows(const GemmParams &p, const f32x4 (*accp)[4][4], int mw0, int nw0,
@@ -506,10 +507,10 @@ __device__ __forceinline__ void nt_epilogue_glu_bwd_rows(const GemmParams &p, co
   }
 }
 
-// The same transposition for the bias / ReLU / ReLU-gate epilogues (EPI_BIAS, EPI_RELU, EPI_MASK) of gemm_nt8_kernel:
+// The same transposition for the bias / ReLU / ReLU-gate epilogues (EPI_BIAS, EPI_RELU, EPI_MASK):
 // residual or gating activation in (T, or sign nibbles: one byte per four channels), result out, optional second
 // output (the pre-residual / ungated value as T, or the sign nibbles of a ReLU).  Arithmetic and masking are those of
-// nt_epilogue; only the route of the bytes differs.  The launcher-side conditions are in nt8_rows_ok().
+// nt_epilogue; only the route of the bytes differs.  The conditions are in nt_rows_ok().
 template <typename T, int EPI, int NH, int AHEAD>
 __device__ __forceinline__ void nt_epilogue_rows(const GemmParams &p, const f32x4 (*accp)[4][4], const float (&bv)[4][4],
                                                  int mw0, int nw0, int lane, unsigned char *lw) {
@@ -728,12 +729,10 @@ __device__ __forceinline__ void nt_epilogue_any(const GemmParams &p, const f32x4
 }
 
 // Block tiles BM x BN, one wave per 64x64 sub-tile:
-//   128x128 (4 waves, 32 KB LDS, 4 workgroups/CU), 256x128 (8 waves, 48 KB, 2-3 workgroups/CU): single LDS
-//   buffer, the interleaving of the co-resident workgroups hides the load latency;
-//   256x256 (16 waves, one workgroup per CU): two LDS buffers (128 KB), the DMA of step k+1 runs under the
-//   MFMAs of step k, one barrier per step.
+//   128x128 (4 waves, 32 KB LDS, 4 workgroups/CU), 256x128 (8 waves, 48 KB, 2-3 workgroups/CU, f32 only): single LDS
+//   buffer, the interleaving of the co-resident workgroups hides the load latency.
 // The kernel is bound by L2 -> LDS bandwidth (a 128x128x64 tile moves 32 KB per 2.1 MFLOP = 64 flop/B; 256x128:
-// 85 flop/B; 256x256: 128 flop/B), so the largest tile that still fills the chip wins.
+// 85 flop/B), so the largest tile that still fills the chip wins.  (256x256 tiles of 16-bit types: gemm_nt9_kernel.)
 template <typename T, int EPI, int BM, int BN>
 // 16-bit element types: four waves per SIMD (128 VGPRs).  f32 (the parity path) carries 16-byte operand registers
 // through the epilogues and needs up to ~170: it is allowed down to two waves per SIMD instead of spilling.  So is the
@@ -748,13 +747,11 @@ __global__ __launch_bounds__(BM * BN / 64) __attribute__((amdgpu_waves_per_eu((s
   constexpr int WN = BN / 64;        // waves along n
   constexpr int ACH = BM * 8 / NT;   // activation chunks per thread
   constexpr int WCH = BN * 8 / NT;   // weight chunks per thread
-  constexpr bool DB = (BM == 256 && BN == 256);
-  constexpr int STAGE = (BM + BN) * 8;
-  // per stage [row * 8 + chunk]: activations, then weights; after the K loop the same memory is the waves' private
+  // [row * 8 + chunk]: activations, then weights; after the K loop the same memory is the waves' private
   // transposition space of the LDS-routed epilogues (16-bit types; the GLU-backward one needs 11 KB per wave)
-  constexpr int TILE_CHUNKS = (DB ? 2 : 1) * STAGE;
-  // LDS-routed epilogues: the 128 x 128 tile of the 16-bit types (the 16-wave tile is the A/B fallback of gemm_nt8_kernel
-  // and the 256 x 128 tile would drop to one or two workgroups per CU: both keep the generic epilogue)
+  constexpr int TILE_CHUNKS = (BM + BN) * 8;
+  // LDS-routed epilogues: the 128 x 128 tile of the 16-bit types (the 256 x 128 tile would drop to one or two workgroups
+  // per CU: it keeps the generic epilogue)
   constexpr bool ROWS = sizeof(T) == 2 && BM == 128 && BN == 128;
   constexpr int EPI_CHUNKS = ROWS ? (NT / 64) * nt_rows_lds(EPI) / 16 : 0;
   __shared__ uint4 lds_all[TILE_CHUNKS > EPI_CHUNKS ? TILE_CHUNKS : EPI_CHUNKS];
@@ -814,14 +811,13 @@ __global__ __launch_bounds__(BM * BN / 64) __attribute__((amdgpu_waves_per_eu((s
   typedef const __attribute__((address_space(1))) void *glb_ptr;
   const int wave_u = uniform(wave);
   // one wave-instruction fills 1 KiB = 8 LDS rows; lane L writes chunk position it*NT + wave*64 + L
-#define CUM_GLDS(k0, stage)                                                                                    \
+#define CUM_GLDS(k0)                                                                                           \
   do {                                                                                                         \
     _Pragma("unroll") for (int it = 0; it < ACH; ++it)                                                        \
-      __builtin_amdgcn_global_load_lds((glb_ptr)(ga[it] + (k0)),                                               \
-                                       (lds_ptr)(&lds_all[(stage) * STAGE + it * NT + wave_u * 64]), 16, 0, 0);  \
+      __builtin_amdgcn_global_load_lds((glb_ptr)(ga[it] + (k0)), (lds_ptr)(&lds_all[it * NT + wave_u * 64]), 16, 0, 0); \
     _Pragma("unroll") for (int it = 0; it < WCH; ++it)                                                        \
       __builtin_amdgcn_global_load_lds((glb_ptr)(gw[it] + (k0)),                                               \
-                                       (lds_ptr)(&lds_all[(stage) * STAGE + BM * 8 + it * NT + wave_u * 64]), 16, 0, 0); \
+                                       (lds_ptr)(&lds_all[BM * 8 + it * NT + wave_u * 64]), 16, 0, 0);         \
   } while (0)
 
   f32x4 acc[4][4];  // [ni][mi]
@@ -833,46 +829,58 @@ __global__ __launch_bounds__(BM * BN / 64) __attribute__((amdgpu_waves_per_eu((s
   float bv[4][4];
   nt_load_bias(p, n0, wn, g, bv);
   const int nk = p.K / BK;
-  if constexpr (DB) CUM_GLDS(0, 0);
   for (int kt = 0; kt < nk; ++kt) {
-    if constexpr (!DB) CUM_GLDS(kt * BK, 0);
+    CUM_GLDS(kt * BK);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();   // DB: stage kt has landed for every wave, and every wave is done reading stage kt-1
-    if constexpr (DB) {
-      if (kt + 1 < nk) CUM_GLDS((kt + 1) * BK, (kt + 1) & 1);
-    }
-    const uint4 *const ldsA = lds_all + (DB ? (kt & 1) * STAGE : 0), *const ldsW = ldsA + BM * 8;
-    nt_compute<T>(ldsA, ldsW, acc, wm, wn, g, r);
-    if constexpr (!DB) __syncthreads();  // every wave is done reading before the next tile overwrites the buffer
+    __syncthreads();   // the tile has landed for every wave
+    nt_compute<T>(lds_all, lds_all + BM * 8, acc, wm, wn, g, r);
+    __syncthreads();   // every wave is done reading before the next tile overwrites the buffer
   }
 #undef CUM_GLDS
 
-  if constexpr (ROWS)   // (the single-buffered loop ends with a barrier: the LDS is free; 128 VGPRs: no slab of loads ahead)
+  if constexpr (ROWS)   // (the loop ends with a barrier: the LDS is free; 128 VGPRs: no slab of loads ahead)
     nt_epilogue_any<T, EPI, 1, (EPI == EPI_GLU_BWD && sizeof(T) == 2) ? 1 : 0>(p, &acc, bv, m0, n0, wm, wn, lane,
                                   reinterpret_cast<unsigned char *>(lds_all) + wave * nt_rows_lds(EPI));
   else
     nt_epilogue<T, EPI>(p, &acc, bv, m0, n0, wm, wn, g, r);
 }
 
-#ifdef CUM_AB   // gemm_nt8_kernel: the predecessor of gemm_nt9_kernel, kept for same-box A/B runs (CUM_NT9=0)
-// ---------------------------------------------------------------- 256 x 256 tile, 8 waves, DMA in flight across barriers
-// The 16-wave 256x256 kernel above waits `vmcnt(0)` + `__syncthreads()` at the top of every K-step: one LDS-DMA stage in
-// flight, every wave stalled while it lands, 16 waves x 64x64 sub-tiles (0.5 fragment reads per MFMA).  This variant
-// follows the structure cdna_hip_programming.md section 5 measures at 1.3-1.45x such a loop (256^2 tile, 8 waves of
-// 128 x 64, K-step 64, raw s_barrier, counted vmcnt, never 0 in the loop), with its own unit schedule:
-//   * a K-tile is four 16 KB UNITS -- activation rows 0-127 / 128-255 (A0, A1), weight rows 0-127 / 128-255 (W0, W1);
-//     two K-tiles of units = 128 KB, ONE __shared__ array;
-//   * wave (wr, wc) owns rows [128 wr, +128) x channels [64 wc, +64): it reads unit A_wr whole at the start of the
-//     K-tile (16 fragment reads, kept in registers) and W_(wc >> 1) in two halves (phases 1 and 3);
-//   * so K-tile t's A units are free after phase 1 and its W units after phase 3, and the units of K-tile t + 2 are
-//     DMA'd into them one per phase (A0, A1, W0, W1) while K-tile t's 64 MFMAs per wave run: at the top of K-tile t + 1
-//     a counted `s_waitcnt vmcnt(8)` retires K-tile t + 1's units and leaves all eight DMAs of K-tile t + 2 in flight --
-//     every unit has one to two K-tiles (2-4 k cycles) of cover instead of at most one K-step;
-//   * three barriers per K-tile: B1 (K-tile landed, before the first read), B2 (A units read by every wave), B3 (W units
-//     read by every wave).  A DMA'd unit is read only after the wait that retires it AND a barrier; a unit is re-staged
-//     only after a barrier that follows every wave's lgkmcnt(0) on its reads.
+
+// ---------------------------------------------------------------- 256 x 256 tile, 8 waves, two wave groups in ping-pong
+// The structure cdna_hip_programming.md section 5 measures at 1.3-1.45x a loop that waits `vmcnt(0)` + `__syncthreads()`
+// at the top of every K-step (256^2 tile, 8 waves of 128 x 64, K-step 64, raw s_barrier, counted vmcnt, never 0 in the
+// loop), with its own unit schedule:
+//   * a K-tile is four 16 KB UNITS -- activation rows 0-127 / 128-255 (A0, A1), weight rows 0-127 / 128-255 (W0, W1),
+//     each [128 rows][8 chunks of 16 bytes], swizzled; two K-tiles of units = 128 KB, ONE __shared__ array;
+//   * wave (wr, wc) owns rows [128 wr, +128) x channels [64 wc, +64): it reads unit A_wr and half of unit W_(wc >> 1)
+//     (24 fragment reads per 64 MFMAs; 64 x 64 wave tiles need 32);
+//   * units are filled by LDS-DMA, thread `tid` writing linear chunks it * 512 + tid (it = 0, 1) of a unit, and the units
+//     of K-tile t + 2 are DMA'd into those of K-tile t as they fall free, while K-tile t's 64 MFMAs per wave run: every
+//     unit has one to two K-tiles (2-4 k cycles) of cover instead of at most one K-step;
+//   * a DMA'd unit is read only after the counted vmcnt that retires it AND a barrier; a unit is re-staged only after a
+//     barrier that follows every wave's lgkmcnt(0) on its reads of it.
+// A K-tile is eight SLOTS (one barrier each), alternately a LOAD slot (issue the fragment reads of the next 16 MFMAs and
+// this slot's share of the LDS-DMAs, then wait at the barrier) and a COMPUTE slot (16 MFMAs = one 64 x 32 quadrant over
+// the K-tile), and waves 4-7 run ONE SLOT BEHIND waves 0-3: on every SIMD one wave computes while its partner loads
+// (MI355X_MICROARCH.md "Two waves per SIMD", cdna_hip_programming.md 5 "8-phase").
+//   group 0 (rows 0-127):   L1 C1 L2 C2 L3 C3 L4 C4 | L1 ...        group 1 (rows 128-255): .. L1 C1 L2 C2 L3 C3 L4 C4 | ...
+//   L1: A rows 0-63 + W channels 0-31 (12 reads)   C1: (rows 0-63,  ch 0-31)
+//   L2: A rows 64-127 (8 reads)                    C2: (rows 64-127, ch 0-31)
+//   L3: W channels 32-63 (4 reads)                 C3: (rows 64-127, ch 32-63)
+//   L4: -                                          C4: (rows 0-63,  ch 32-63)
+// Unit lifetimes (K-tile t, slots counted in barriers 8 t + i of group 0): A0 is read by group 0 only, in L1 / L2 -> free
+// after barrier 8t+4; A1 by group 1 only -> free after 8t+5; W0 / W1 by both, last in group 1's L3 -> free after 8t+7.
+// LDS-DMA of K-tile t + 2 into the freed units: group 0 issues A0 in L3, A1 in L4, W0 + W1 in the next K-tile's L1;
+// group 1 issues A0 + A1 in L3, W0 + W1 in L4.  One counted wait per K-tile and wave (end of C4 / in L4): vmcnt(4) = K-tile
+// t + 1 has landed, the four A instructions of K-tile t + 2 stay in flight; the barrier behind it publishes K-tile t + 1.
+// (Spreading the DMA issue evenly over the load slots -- two instructions in each -- measured the same to +-2 %.)
+// History: against its predecessor, which ran all eight waves in the same phase (three barriers per K-tile, matrix pipe
+// 59 % busy), this schedule measured on MI355X (tools/bench_gemm.py, bf16) enc3-enc6 conv 0.84 / 1.01 / 1.09 / 1.08 ->
+// 0.90 / 1.09 / 1.20 / 1.17 PFLOP/s, plain 8192^3 1.14 -> 1.22-1.25, matrix pipe 68 % busy while the chip's clock under
+// this load fell 1.58 -> 1.51 GHz (power: part of every gain in MFMA density is given back as clock,
+// MI355X_MICROARCH.md "DVFS give-back").
 template <typename T, int EPI>
-__global__ __launch_bounds__(512) void gemm_nt8_kernel(const GemmParams p) {
+__global__ __launch_bounds__(512) void gemm_nt9_kernel(const GemmParams p) {
   static_assert(sizeof(T) == 2, "16-bit element types only");
   constexpr int EPC = 8, BK = 64;
   constexpr int UNIT = 128 * 8;                       // 16-byte chunks of one unit: [128 rows][8 chunks], swizzled
@@ -882,10 +890,17 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const GemmParams p) {
   const int wave = uniform(tid >> 6);
   const int wr = wave >> 2, wc = wave & 3;
   const int g = lane >> 4, r = lane & 15;
+  // Tile order: workgroup ids b, b + 8, ... run on one XCD (one L2).  An XCD walks `group_m` of its m-tiles side by side,
+  // n-tile after n-tile: its 32 resident workgroups then cover group_m x (32 / group_m) tiles and pull group_m A panels +
+  // 32 / group_m W panels per K-tile through its L2 instead of 1 + 32 (group_m = 1: one m-tile after the other, which is what
+  // the layers' N <= 1 536 = 6 n-tiles want; a square GEMM with 32 n-tiles streams all of W per m-tile that way).
   const int NB = (p.N + 255) / 256;
   const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int m_tile = (local / NB) * 8 + xcd;
-  const int n0 = (local % NB) * 256;
+  const int per = p.group_m * NB, grp = local / per, within = local - grp * per;
+  const int left = (int)gridDim.x / (8 * NB) - grp * p.group_m;
+  const int gm = left < p.group_m ? left : p.group_m;
+  const int m_tile = (grp * p.group_m + within % gm) * 8 + xcd;
+  const int n0 = (within / gm) * 256;
   const int m0 = m_tile * 256;
   if (m0 >= p.M) return;
   if (blockIdx.x == 0) {                              // framing rows of the output buffer (see gemm_nt_kernel)
@@ -948,12 +963,6 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const GemmParams p) {
 #pragma unroll
     for (int u = 0; u < 4; ++u) CUM_STAGE(u, 1, 1);
   }
-  // Fragment reads are inline asm: hipcc's wait insertion sees every ds_read of an array that LDS-DMAs are in flight
-  // into as a reason for `s_waitcnt vmcnt(0)` (it cannot tell the units apart), which would drain the pipeline twice
-  // per K-tile.  An asm read is not counted by the compiler: each group of reads is followed by one wait statement
-  // that names every destination "+v" (cdna_hip_programming.md 5.7, form ii), so no consumer is scheduled above it.
-  // Addresses: byte offset of (row, 16-byte chunk) inside a unit = row * 128 + ((chunk ^ (row & 7)) << 4); rows 16 apart
-  // share the swizzle term, so one base register per K half (ks) + immediate offsets serves all row tiles.
   const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)lds_all;
   unsigned aA[2], aW[2];
 #pragma unroll
@@ -963,229 +972,6 @@ __global__ __launch_bounds__(512) void gemm_nt8_kernel(const GemmParams p) {
     aW[ks] = lds0 + (unsigned)(((2 + (wc >> 1)) * UNIT + ((wc & 1) * 64 + r) * 8 + (cl ^ (r & 7))) * 16);
   }
 #define CUM_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
-  for (int kt = 0; kt < nk; ++kt) {
-    const int par = kt & 1;
-    const unsigned pb = (unsigned)par * (4 * UNIT * 16);
-    const unsigned a0 = aA[0] + pb, a1 = aA[1] + pb, w0 = aW[0] + pb, w1 = aW[1] + pb;
-    const bool more = kt + 2 < nk;
-    if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");   // K-tile kt landed; K-tile kt + 1 stays in flight
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");                              // B1
-    // ---- phase 1: W fragments of channels 0-31 and all A fragments of the K-tile, issued in the order the MFMAs
-    //      consume them (LDS returns in order): the first half-quadrant starts after 6 of the 20 reads, the rest land
-    //      under MFMAs
-    u32x4 af[2][8], wf[2][2];        // native vectors: an asm operand of the HIP uint4 struct would go through memory
-    CUM_DSR(wf[0][0], w0, 0);     CUM_DSR(wf[0][1], w0, 2048);
-    CUM_DSR(af[0][0], a0, 0);     CUM_DSR(af[0][1], a0, 2048);  CUM_DSR(af[0][2], a0, 4096);  CUM_DSR(af[0][3], a0, 6144);
-    CUM_DSR(wf[1][0], w1, 0);     CUM_DSR(wf[1][1], w1, 2048);
-    CUM_DSR(af[1][0], a1, 0);     CUM_DSR(af[1][1], a1, 2048);  CUM_DSR(af[1][2], a1, 4096);  CUM_DSR(af[1][3], a1, 6144);
-    CUM_DSR(af[0][4], a0, 8192);  CUM_DSR(af[0][5], a0, 10240); CUM_DSR(af[0][6], a0, 12288); CUM_DSR(af[0][7], a0, 14336);
-    CUM_DSR(af[1][4], a1, 8192);  CUM_DSR(af[1][5], a1, 10240); CUM_DSR(af[1][6], a1, 12288); CUM_DSR(af[1][7], a1, 14336);
-#define CUM_HALFQ(h, nlo, ks)                                                                                  \
-  do {                                                                                                         \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                           \
-      _Pragma("unroll") for (int mi = 0; mi < 4; ++mi) {                                                       \
-        if constexpr (__is_same(T, f16))                                                                       \
-          acc[h][(nlo) + ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_f16(                                     \
-              __builtin_bit_cast(f16x8, wf[ks][ni]), __builtin_bit_cast(f16x8, af[ks][4 * (h) + mi]),          \
-              acc[h][(nlo) + ni][mi], 0, 0, 0);                                                                \
-        else                                                                                                   \
-          acc[h][(nlo) + ni][mi] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(                                    \
-              __builtin_bit_cast(bf16x8, wf[ks][ni]), __builtin_bit_cast(bf16x8, af[ks][4 * (h) + mi]),        \
-              acc[h][(nlo) + ni][mi], 0, 0, 0);                                                                \
-      }                                                                                                        \
-  } while (0)
-#define CUM_QUAD(h, nlo)         \
-  do {                           \
-    CUM_HALFQ(h, nlo, 0);        \
-    CUM_HALFQ(h, nlo, 1);        \
-  } while (0)
-    asm volatile("s_waitcnt lgkmcnt(14)"
-                 : "+v"(wf[0][0]), "+v"(wf[0][1]), "+v"(af[0][0]), "+v"(af[0][1]), "+v"(af[0][2]), "+v"(af[0][3]) : : "memory");
-    __builtin_amdgcn_s_setprio(1);
-    CUM_HALFQ(0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);     // keep these 8 MFMAs in front of the next wait: they cover the reads it waits for
-    asm volatile("s_waitcnt lgkmcnt(8)"
-                 : "+v"(wf[1][0]), "+v"(wf[1][1]), "+v"(af[1][0]), "+v"(af[1][1]), "+v"(af[1][2]), "+v"(af[1][3]) : : "memory");
-    CUM_HALFQ(0, 0, 1);
-    __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(af[0][4]), "+v"(af[0][5]), "+v"(af[0][6]), "+v"(af[0][7]), "+v"(af[1][4]), "+v"(af[1][5]),
-                   "+v"(af[1][6]), "+v"(af[1][7]) : : "memory");
-    asm volatile("s_barrier" ::: "memory");                              // B2: the A units of this parity are free
-    // Waves w and w + 4 share a SIMD.  Issuing an LDS-DMA costs the issuing wave ~100 cycles apiece; if both partners
-    // issue theirs at the same point of the K-tile the SIMD's matrix pipe idles meanwhile.  So the two halves of the
-    // workgroup take the DMA issue at different points: waves 0-3 stage first and compute after, waves 4-7 compute
-    // first (same barriers, same DMA count between the counted waits).
-    // ---- phase 2
-    const bool early = more && wr == 0, late = more && wr != 0;
-    if (early) {
-      CUM_STAGE(0, kt + 2, par);
-      CUM_STAGE(1, kt + 2, par);
-    }
-    __builtin_amdgcn_s_setprio(1);
-    CUM_QUAD(1, 0);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (late) {
-      CUM_STAGE(0, kt + 2, par);
-      CUM_STAGE(1, kt + 2, par);
-    }
-    // ---- phase 3: W fragments of channels 32-63 (rows + 32 of the unit: + 4096 bytes)
-    CUM_DSR(wf[0][0], w0, 4096);  CUM_DSR(wf[0][1], w0, 6144);  CUM_DSR(wf[1][0], w1, 4096);  CUM_DSR(wf[1][1], w1, 6144);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(wf[0][0]), "+v"(wf[0][1]), "+v"(wf[1][0]), "+v"(wf[1][1]) : : "memory");
-    asm volatile("s_barrier" ::: "memory");                              // B3: the W units of this parity are free
-    if (early) {
-      CUM_STAGE(2, kt + 2, par);
-      CUM_STAGE(3, kt + 2, par);
-    }
-    __builtin_amdgcn_s_setprio(1);
-    CUM_QUAD(1, 2);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    if (late) {
-      CUM_STAGE(2, kt + 2, par);
-      CUM_STAGE(3, kt + 2, par);
-    }
-    // ---- phase 4
-    __builtin_amdgcn_s_setprio(1);
-    CUM_QUAD(0, 2);
-    __builtin_amdgcn_s_setprio(0);
-  }
-#undef CUM_HALFQ
-#undef CUM_DSR
-#undef CUM_QUAD
-#undef CUM_STAGE
-  // Epilogue: through wave-private LDS where the conditions hold (nt_epilogue_any); the fragment registers are dead here,
-  // so one slab of operand loads is issued ahead.  (Deeper pipelining of the generic epilogue measured neutral: it is
-  // bound by its access pattern, not by loads in flight.)
-  asm volatile("s_barrier" ::: "memory");          // every wave is done reading the K loop's LDS units
-  nt_epilogue_any<T, EPI, 2, 1>(p, acc, bv, m0, n0, 2 * wr, wc, lane,
-                                reinterpret_cast<unsigned char *>(lds_all) + wave * nt_rows_lds(EPI));
-}
-
-#endif  // CUM_AB
-
-// ---------------------------------------------------------------- 256 x 256 tile, 8 waves, two wave groups in ping-pong
-// Same tile, units, DMA scheme and epilogues as gemm_nt8_kernel; what changes is WHEN the two halves of the workgroup do
-// what.  In gemm_nt8_kernel all eight waves run the same phase at the same time: both waves of a SIMD issue their 20
-// fragment reads together, wait for them together, want the matrix pipe together and meet at the same three barriers --
-// the pipe measured 48 % busy.  Here a K-tile is eight SLOTS (one barrier each), alternately a LOAD slot (issue the
-// fragment reads of the next 16 MFMAs and this slot's share of the LDS-DMAs, then wait at the barrier) and a COMPUTE slot
-// (16 MFMAs = one 64 x 32 quadrant over the K-tile), and waves 4-7 run ONE SLOT BEHIND waves 0-3: on every SIMD one wave
-// computes while its partner loads (MI355X_MICROARCH.md "Two waves per SIMD", cdna_hip_programming.md 5 "8-phase").
-//   group 0 (rows 0-127):   L1 C1 L2 C2 L3 C3 L4 C4 | L1 ...        group 1 (rows 128-255): .. L1 C1 L2 C2 L3 C3 L4 C4 | ...
-//   L1: A rows 0-63 + W channels 0-31 (12 reads)   C1: (rows 0-63,  ch 0-31)
-//   L2: A rows 64-127 (8 reads)                    C2: (rows 64-127, ch 0-31)
-//   L3: W channels 32-63 (4 reads)                 C3: (rows 64-127, ch 32-63)
-//   L4: -                                          C4: (rows 0-63,  ch 32-63)
-// Unit lifetimes (K-tile t, slots counted in barriers 8 t + i of group 0): A0 is read by group 0 only, in L1 / L2 -> free
-// after barrier 8t+4; A1 by group 1 only -> free after 8t+5; W0 / W1 by both, last in group 1's L3 -> free after 8t+7.
-// LDS-DMA of K-tile t + 2 into the freed units: group 0 issues A0 in L3, A1 in L4, W0 + W1 in the next K-tile's L1;
-// group 1 issues A0 + A1 in L3, W0 + W1 in L4.  One counted wait per K-tile and wave (end of C4 / in L4): vmcnt(4) = K-tile
-// t + 1 has landed, the four A instructions of K-tile t + 2 stay in flight; the barrier behind it publishes K-tile t + 1.
-// (Spreading the DMA issue evenly over the load slots -- two instructions in each -- measured the same to +-2 %.)
-// Measured on MI355X (tools/bench_gemm.py, bf16): enc3-enc6 conv 0.84 / 1.01 / 1.09 / 1.08 -> 0.90 / 1.09 / 1.20 / 1.17
-// PFLOP/s, plain 8192^3 1.14 -> 1.22-1.25; SQ counters on the plain GEMM (tools/pmc_gemm_plain.sh): matrix pipe busy
-// 59 -> 68 % of the kernel's cycles while the chip's clock under this load fell 1.58 -> 1.51 GHz (power: part of every
-// gain in MFMA density is given back as clock, MI355X_MICROARCH.md "DVFS give-back").
-template <typename T, int EPI>
-__global__ __launch_bounds__(512) void gemm_nt9_kernel(const GemmParams p) {
-  static_assert(sizeof(T) == 2, "16-bit element types only");
-  constexpr int EPC = 8, BK = 64;
-  constexpr int UNIT = 128 * 8;
-  __shared__ uint4 lds_all[2 * 4 * UNIT];             // [K-tile parity][A0, A1, W0, W1]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = uniform(tid >> 6);
-  const int wr = wave >> 2, wc = wave & 3;
-  const int g = lane >> 4, r = lane & 15;
-  // Tile order: workgroup ids b, b + 8, ... run on one XCD (one L2).  An XCD walks `group_m` of its m-tiles side by side,
-  // n-tile after n-tile: its 32 resident workgroups then cover group_m x (32 / group_m) tiles and pull group_m A panels +
-  // 32 / group_m W panels per K-tile through its L2 instead of 1 + 32 (group_m = 1: one m-tile after the other, which is what
-  // the layers' N <= 1 536 = 6 n-tiles want; a square GEMM with 32 n-tiles streams all of W per m-tile that way).
-  const int NB = (p.N + 255) / 256;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int per = p.group_m * NB, grp = local / per, within = local - grp * per;
-  const int left = (int)gridDim.x / (8 * NB) - grp * p.group_m;
-  const int gm = left < p.group_m ? left : p.group_m;
-  const int m_tile = (grp * p.group_m + within % gm) * 8 + xcd;
-  const int n0 = (within / gm) * 256;
-  const int m0 = m_tile * 256;
-  if (m0 >= p.M) return;
-  if (blockIdx.x == 0) {                              // framing rows of the output buffer (see gemm_nt_kernel)
-    T *o = static_cast<T *>(p.out);
-    T *x = (EPI != EPI_GLU && EPI != EPI_GLU_BWD && !(EPI == EPI_RELU && p.mask_bits)) ? static_cast<T *>(p.aux) : nullptr;
-    for (int64_t i = threadIdx.x; i < p.zero_head; i += 512) {
-      o[-1 - i] = Elem<T>::from_f(0.f);
-      if (x) x[-1 - i] = Elem<T>::from_f(0.f);
-    }
-    const int64_t tail0 = (int64_t)p.M * p.ldc, tailx = (int64_t)p.M * p.ldz;
-    for (int64_t i = threadIdx.x; i < p.zero_tail; i += 512) {
-      o[tail0 + i] = Elem<T>::from_f(0.f);
-      if (x) x[tailx + i] = Elem<T>::from_f(0.f);
-    }
-  }
-  const T *A = static_cast<const T *>(p.A);
-  const T *W = static_cast<const T *>(p.W);
-  const T *src[4][2];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int pos = it * 512 + tid;
-      const int row = pos >> 3, cphys = pos & 7;
-      const int clog = cphys ^ (row & 7);
-      if (u < 2) {
-        int am = m0 + 128 * u + row;
-        am = am < p.M ? am : p.M - 1;
-        src[u][it] = A + (int64_t)am * p.lda + clog * EPC;
-      } else {
-        int wn_ = n0 + 128 * (u - 2) + row;
-        wn_ = wn_ < p.N ? wn_ : p.N - 1;
-        src[u][it] = W + (int64_t)wn_ * p.ldw + clog * EPC;
-      }
-    }
-  typedef __attribute__((address_space(3))) void *lds_ptr;
-  typedef const __attribute__((address_space(1))) void *glb_ptr;
-#define CUM_STAGE(u, kt, par)                                                                                   \
-  do {                                                                                                          \
-    _Pragma("unroll") for (int it = 0; it < 2; ++it)                                                           \
-      __builtin_amdgcn_global_load_lds((glb_ptr)(src[u][it] + (kt) * BK),                                      \
-                                       (lds_ptr)(&lds_all[((par) * 4 + (u)) * UNIT + it * 512 + wave * 64]), 16, 0, 0); \
-  } while (0)
-
-  f32x4 acc[2][4][4];                                 // [m half][ni][mi]: rows 128 wr + 64 h + 16 mi, channels 64 wc + 16 ni
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  float bv[4][4];
-  nt_load_bias(p, n0, wc, g, bv);
-
-  const int nk = p.K / BK;
-#pragma unroll
-  for (int u = 0; u < 4; ++u) CUM_STAGE(u, 0, 0);
-  if (nk > 1) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) CUM_STAGE(u, 1, 1);
-  }
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)lds_all;
-  unsigned aA[2], aW[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int cl = ks * 4 + g;
-    aA[ks] = lds0 + (unsigned)((wr * UNIT + r * 8 + (cl ^ (r & 7))) * 16);
-    aW[ks] = lds0 + (unsigned)(((2 + (wc >> 1)) * UNIT + ((wc & 1) * 64 + r) * 8 + (cl ^ (r & 7))) * 16);
-  }
-#define CUM_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:" #off : "=v"(dst) : "v"(addr) : "memory")
-#ifdef CUM_NT9_TIMING_NO_W_READS   // timing-only build (wrong results): the W fragment reads = the third of the fragment
-#define CUM_DSRW(dst, addr, off) asm volatile("" : "=v"(dst) : "v"(addr))   // bytes four waves of 128 x 128 would not read
-#else
-#define CUM_DSRW(dst, addr, off) CUM_DSR(dst, addr, off)
-#endif
 #define CUM_BAR()                               \
   do {                                          \
     __builtin_amdgcn_sched_barrier(0);          \
@@ -1225,9 +1011,9 @@ __global__ __launch_bounds__(512) void gemm_nt9_kernel(const GemmParams p) {
     const unsigned a0 = aA[0] + pb, a1 = aA[1] + pb, w0 = aW[0] + pb, w1 = aW[1] + pb;
     const bool more1 = kt + 1 < nk, more2 = kt + 2 < nk;
     // ---- L1: W channels 0-31 and A rows 0-63; group 0 stages the W units of K-tile kt + 1 (freed one slot ago)
-    CUM_DSRW(wf[0][0], w0, 0);    CUM_DSRW(wf[0][1], w0, 2048);
+    CUM_DSR(wf[0][0], w0, 0);    CUM_DSR(wf[0][1], w0, 2048);
     CUM_DSR(af[0][0], a0, 0);     CUM_DSR(af[0][1], a0, 2048);  CUM_DSR(af[0][2], a0, 4096);  CUM_DSR(af[0][3], a0, 6144);
-    CUM_DSRW(wf[1][0], w1, 0);    CUM_DSRW(wf[1][1], w1, 2048);
+    CUM_DSR(wf[1][0], w1, 0);    CUM_DSR(wf[1][1], w1, 2048);
     CUM_DSR(af[1][0], a1, 0);     CUM_DSR(af[1][1], a1, 2048);  CUM_DSR(af[1][2], a1, 4096);  CUM_DSR(af[1][3], a1, 6144);
     if (wr == 0 && kt >= 1 && more1) {
       CUM_STAGE(2, kt + 1, par ^ 1);
@@ -1249,7 +1035,7 @@ __global__ __launch_bounds__(512) void gemm_nt9_kernel(const GemmParams p) {
     CUM_QUAD(1, 0);                                                       // C2
     CUM_BAR();
     // ---- L3: W channels 32-63; the A units of this parity are free: K-tile kt + 2
-    CUM_DSRW(wf[0][0], w0, 4096); CUM_DSRW(wf[0][1], w0, 6144); CUM_DSRW(wf[1][0], w1, 4096); CUM_DSRW(wf[1][1], w1, 6144);
+    CUM_DSR(wf[0][0], w0, 4096); CUM_DSR(wf[0][1], w0, 6144); CUM_DSR(wf[1][0], w1, 4096); CUM_DSR(wf[1][1], w1, 6144);
     if (more2) {
       CUM_STAGE(0, kt + 2, par);
       if (wr != 0) CUM_STAGE(1, kt + 2, par);
@@ -1281,7 +1067,6 @@ __global__ __launch_bounds__(512) void gemm_nt9_kernel(const GemmParams p) {
   }
   if (wr == 0) CUM_BAR();                                                // group 1's last slot
 #undef CUM_HALFQ
-#undef CUM_DSRW
 #undef CUM_DSR
 #undef CUM_QUAD
 #undef CUM_STAGE
@@ -1304,11 +1089,7 @@ __global__ __launch_bounds__(512) void gemm_nt9_kernel(const GemmParams p) {
 template <typename T, int EPI>
 __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmParams p) {
   static_assert(sizeof(T) == 2, "16-bit element types only");
-#ifndef CUM_RING_NST
-#define CUM_RING_NST 3      // (2: one K-step in flight -- the timing experiment of profiles/r06_nt_ring_ab.txt)
-#endif
-  constexpr int EPC = 8, BK = 64, BM = 128, BN = 256, NST = CUM_RING_NST;
-  static_assert(NST == 2 || NST == 3, "two or three stages");
+  constexpr int EPC = 8, BK = 64, BM = 128, BN = 256, NST = 3;
   constexpr int STAGE = (BM + BN) * 8;                // 16-byte chunks per stage: A rows, then W rows; 48 KB
   __shared__ uint4 lds_all[NST * STAGE];
 
@@ -1387,10 +1168,10 @@ __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmParams p) {
                  "+v"(af[KS][2]), "+v"(af[KS][3]) : "n"(n) : "memory")
   const int nk = p.K / BK;
   issue(0, 0);
-  if (NST == 3 && nk > 1) issue(1, 1);
+  if (nk > 1) issue(1, 1);
   int buf = 0;
   for (int kt = 0; kt < nk; ++kt) {
-    if (NST == 3 && kt + 1 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // K-step kt landed; kt + 1 stays in flight
+    if (kt + 1 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // K-step kt landed; kt + 1 stays in flight
     else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     asm volatile("s_barrier" ::: "memory");            // step kt is visible; every wave is done with step kt - 1
     if (kt + NST - 1 < nk) issue(kt + NST - 1, buf == 0 ? NST - 1 : buf - 1);
@@ -1428,231 +1209,6 @@ __global__ __launch_bounds__(512) void gemm_nt_ring_kernel(const GemmParams p) {
                                 reinterpret_cast<unsigned char *>(lds_all) + wave * nt_rows_lds(EPI));
 }
 
-#ifdef CUM_AB
-template <int I, int N, typename F>
-__device__ __forceinline__ void static_for(F &&f) {
-  if constexpr (I < N) {
-    f(std::integral_constant<int, I>{});
-    static_for<I + 1, N>(f);
-  }
-}
-
-// ---------------------------------------------------------------- 256 x 256 tile, FOUR waves of 128 x 128 (experiment)
-// Same tile, LDS units and LDS-DMA as gemm_nt9_kernel; one wave per SIMD, its 64 accumulator blocks in AGPRs.  What it is
-// for: a wave of 128 x 128 reads (128 + 128) x 64 x 2 B = 32 KB of fragments per K-tile, 128 KB per CU, where eight waves of
-// 128 x 64 read 192 KB -- with the 64 KB the DMA writes, gemm_nt9_kernel keeps the LDS as busy as the matrix pipe (256 KB =
-// 2 048 clk at 128 B/clk against 2 048 MFMA cycles per SIMD), and a timing-only build of it without the W fragment reads
-// runs the plain 8192^3 GEMM at 1.67 PFLOP/s against 1.30 (profiles/r06_nt_asm_ab.txt).  Every instruction of the K loop
-// is a volatile asm statement, so the order written here is the order issued:
-//   phase A (64 MFMAs on K-half 0): the 32 fragment reads of K-half 1 under MFMAs 0-31; after MFMA 39 lgkmcnt(0) + barrier
-//     (every wave is done reading this parity's units), then the 16 LDS-DMAs of K-tile kt + 2 under MFMAs 40-55;
-//   phase B (64 MFMAs on K-half 1): after MFMA 23 vmcnt(16) + barrier (K-tile kt + 1 has landed for every wave), then the
-//     32 fragment reads of its K-half 0 under MFMAs 24-55, lgkmcnt(0) behind MFMA 63.
-template <typename T, int EPI>
-__global__ __launch_bounds__(256) void gemm_nt4_kernel(const GemmParams p) {
-  static_assert(sizeof(T) == 2, "16-bit element types only");
-  constexpr int EPC = 8, BK = 64;
-  constexpr int UNIT = 128 * 8;
-  __shared__ uint4 lds_all[2 * 4 * UNIT];             // [K-tile parity][A0, A1, W0, W1]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = uniform(tid >> 6);
-  const int wr = wave >> 1, wc = wave & 1;
-  const int g = lane >> 4, r = lane & 15;
-  const int NB = (p.N + 255) / 256;
-  const int xcd = blockIdx.x & 7, local = blockIdx.x >> 3;
-  const int per = p.group_m * NB, grp = local / per, within = local - grp * per;
-  const int left = (int)gridDim.x / (8 * NB) - grp * p.group_m;
-  const int gm = left < p.group_m ? left : p.group_m;
-  const int m_tile = (grp * p.group_m + within % gm) * 8 + xcd;
-  const int n0 = (within / gm) * 256;
-  const int m0 = m_tile * 256;
-  if (m0 >= p.M) return;
-  if (blockIdx.x == 0) {                              // framing rows of the output buffer (see gemm_nt_kernel)
-    T *o = static_cast<T *>(p.out);
-    T *x = (EPI != EPI_GLU && EPI != EPI_GLU_BWD && !(EPI == EPI_RELU && p.mask_bits)) ? static_cast<T *>(p.aux) : nullptr;
-    for (int64_t i = threadIdx.x; i < p.zero_head; i += 256) {
-      o[-1 - i] = Elem<T>::from_f(0.f);
-      if (x) x[-1 - i] = Elem<T>::from_f(0.f);
-    }
-    const int64_t tail0 = (int64_t)p.M * p.ldc, tailx = (int64_t)p.M * p.ldz;
-    for (int64_t i = threadIdx.x; i < p.zero_tail; i += 256) {
-      o[tail0 + i] = Elem<T>::from_f(0.f);
-      if (x) x[tailx + i] = Elem<T>::from_f(0.f);
-    }
-  }
-  const T *A = static_cast<const T *>(p.A);
-  const T *W = static_cast<const T *>(p.W);
-  const T *src[4][4];
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      const int pos = it * 256 + tid;
-      const int row = pos >> 3, cphys = pos & 7;
-      const int clog = cphys ^ (row & 7);
-      if (u < 2) {
-        int am = m0 + 128 * u + row;
-        am = am < p.M ? am : p.M - 1;
-        src[u][it] = A + (int64_t)am * p.lda + clog * EPC;
-      } else {
-        int wn_ = n0 + 128 * (u - 2) + row;
-        wn_ = wn_ < p.N ? wn_ : p.N - 1;
-        src[u][it] = W + (int64_t)wn_ * p.ldw + clog * EPC;
-      }
-    }
-  typedef __attribute__((address_space(3))) void *lds_ptr;
-  typedef const __attribute__((address_space(1))) void *glb_ptr;
-#define CUM_DMA(u, it, kt, par)                                                                       \
-  __builtin_amdgcn_global_load_lds((glb_ptr)(src[u][it] + (kt) * BK),                                 \
-                                   (lds_ptr)(&lds_all[((par) * 4 + (u)) * UNIT + (it) * 256 + wave * 64]), 16, 0, 0)
-
-  f32x4 acc[8][8];                                    // [ni][mi] in AGPRs: channels 128 wc + 16 ni, rows 128 wr + 16 mi
-#pragma unroll
-  for (int i = 0; i < 8; ++i)
-#pragma unroll
-    for (int j = 0; j < 8; ++j) acc[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  const int nk = p.K / BK;
-#pragma unroll
-  for (int u = 0; u < 4; ++u)
-#pragma unroll
-    for (int it = 0; it < 4; ++it) CUM_DMA(u, it, 0, 0);
-  {
-    const int k1 = nk > 1 ? 1 : 0;
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-#pragma unroll
-      for (int it = 0; it < 4; ++it) CUM_DMA(u, it, k1, 1);
-  }
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)lds_all;
-  unsigned aA[2], aW[2];
-#pragma unroll
-  for (int ks = 0; ks < 2; ++ks) {
-    const int cl = ks * 4 + g;
-    aA[ks] = lds0 + (unsigned)((wr * UNIT + r * 8 + (cl ^ (r & 7))) * 16);
-    aW[ks] = lds0 + (unsigned)(((2 + wc) * UNIT + r * 8 + (cl ^ (r & 7))) * 16);
-  }
-#define CUM_DSR(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define CUM_WAIT_FRAGS(ks)                                                                                               \
-  asm volatile("s_waitcnt lgkmcnt(0)"                                                                                    \
-               : "+v"(af[ks][0]), "+v"(af[ks][1]), "+v"(af[ks][2]), "+v"(af[ks][3]), "+v"(af[ks][4]), "+v"(af[ks][5]),   \
-                 "+v"(af[ks][6]), "+v"(af[ks][7]), "+v"(wf[ks][0]), "+v"(wf[ks][1]), "+v"(wf[ks][2]), "+v"(wf[ks][3]),   \
-                 "+v"(wf[ks][4]), "+v"(wf[ks][5]), "+v"(wf[ks][6]), "+v"(wf[ks][7]) : : "memory")
-#define CUM_MFMA(ks, ni, mi)                                                                                             \
-  do {                                                                                                                   \
-    if constexpr (__is_same(T, f16))                                                                                     \
-      asm volatile("v_mfma_f32_16x16x32_f16 %0, %1, %2, %0" : "+a"(acc[ni][mi]) : "v"(wf[ks][ni]), "v"(af[ks][mi]));     \
-    else                                                                                                                 \
-      asm volatile("v_mfma_f32_16x16x32_bf16 %0, %1, %2, %0" : "+a"(acc[ni][mi]) : "v"(wf[ks][ni]), "v"(af[ks][mi]));    \
-  } while (0)
-  // fragment read number J (0-15) of K-half KS at parity offset pb: A block J / 2 (even J) or W block J / 2 (odd J)
-#define CUM_FRAG(KS, J, pb)                                                             \
-  do {                                                                                  \
-    if constexpr (((J) & 1) != 0) CUM_DSR(wf[KS][(J) >> 1], aW[KS] + (pb), ((J) >> 1) * 2048); \
-    else CUM_DSR(af[KS][(J) >> 1], aA[KS] + (pb), ((J) >> 1) * 2048);                   \
-  } while (0)
-
-  u32x4 af[2][8], wf[2][8];
-  asm volatile("s_waitcnt vmcnt(16)" ::: "memory");                     // K-tile 0 landed; K-tile 1 stays in flight
-  asm volatile("s_barrier" ::: "memory");
-  static_for<0, 16>([&](auto ic) {
-    constexpr int j = decltype(ic)::value;
-    CUM_FRAG(0, j, 0u);
-  });
-  CUM_WAIT_FRAGS(0);
-  // The loop body is branch-free (with accumulators in asm operands every branch costs the allocator its grip on them): the
-  // last two K-tiles re-fetch K-tile nk - 1 into the free parity and read fragments nobody uses.
-#ifndef CUM_NT4_PA
-#define CUM_NT4_PA 40      // MFMAs of phase A in front of the "units free" barrier (16 ... 48)
-#endif
-#ifndef CUM_NT4_PB
-#define CUM_NT4_PB 24      // MFMAs of phase B in front of the "next K-tile landed" barrier (0 ... 48)
-#endif
-#ifdef CUM_NT4_NOBAR       // timing-only: no barriers (races)
-#define CUM_NT4_BAR() asm volatile("" ::: "memory")
-#else
-#define CUM_NT4_BAR() asm volatile("s_barrier" ::: "memory")
-#endif
-#ifdef CUM_NT4_NODMA        // timing-only: no LDS-DMA in the loop
-#define CUM_DMA_L(u, it, kt, par) asm volatile("" ::: "memory")
-#else
-#define CUM_DMA_L(u, it, kt, par) CUM_DMA(u, it, kt, par)
-#endif
-#ifdef CUM_NT4_NOREAD       // timing-only: no fragment reads in the loop
-#define CUM_FRAG_L(KS, J, pb) asm volatile("" ::: "memory")
-#else
-#define CUM_FRAG_L(KS, J, pb) CUM_FRAG(KS, J, pb)
-#endif
-  constexpr int PA = CUM_NT4_PA, PB = CUM_NT4_PB;
-  for (int kt = 0; kt < nk; ++kt) {
-    const int par = kt & 1;
-    const unsigned pb = (unsigned)par * (4 * UNIT * 16), pn = pb ^ (4 * UNIT * 16);
-    const int kt2 = kt + 2 < nk ? kt + 2 : nk - 1;
-    // ---- phase A: K-half 0
-    static_for<0, PA>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      CUM_MFMA(0, i >> 3, i & 7);
-      if constexpr (i < 16) CUM_FRAG_L(1, i, pb);
-    });
-    CUM_WAIT_FRAGS(1);
-    CUM_NT4_BAR();                                                       // this parity's units are free
-    static_for<PA, PA + 16>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      CUM_MFMA(0, i >> 3, i & 7);
-      CUM_DMA_L((i - PA) >> 2, (i - PA) & 3, kt2, par);
-    });
-    static_for<PA + 16, 64>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      CUM_MFMA(0, i >> 3, i & 7);
-    });
-    // ---- phase B: K-half 1
-    static_for<0, PB>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      CUM_MFMA(1, i >> 3, i & 7);
-    });
-    #ifndef CUM_NT4_NODMA
-    asm volatile("s_waitcnt vmcnt(16)" ::: "memory");
-#endif
-    CUM_NT4_BAR();                                                       // K-tile kt + 1 is visible to every wave
-    static_for<PB, PB + 16>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      CUM_MFMA(1, i >> 3, i & 7);
-      CUM_FRAG_L(0, i - PB, pn);
-    });
-    static_for<PB + 16, 64>([&](auto ic) {
-      constexpr int i = decltype(ic)::value;
-      CUM_MFMA(1, i >> 3, i & 7);
-    });
-    CUM_WAIT_FRAGS(0);
-  }
-  asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#undef CUM_DSR
-#undef CUM_WAIT_FRAGS
-#undef CUM_MFMA
-#undef CUM_FRAG
-#undef CUM_DMA
-  // the last MFMAs' results must be in the AGPRs before anything the compiler emits reads them (it sees asm outputs as
-  // ready at once): the blocks of the last eight MFMAs go through the nops
-  asm volatile("s_nop 7\n\ts_nop 7\n\ts_nop 7\n\ts_barrier"
-               : "+a"(acc[7][0]), "+a"(acc[7][1]), "+a"(acc[7][2]), "+a"(acc[7][3]), "+a"(acc[7][4]), "+a"(acc[7][5]),
-                 "+a"(acc[7][6]), "+a"(acc[7][7]) : : "memory");
-#pragma unroll
-  for (int h = 0; h < 2; ++h) {
-    float bv[4][4];
-    nt_load_bias(p, n0, 2 * wc + h, g, bv);
-    f32x4 part[2][4][4];
-#pragma unroll
-    for (int hh = 0; hh < 2; ++hh)
-#pragma unroll
-      for (int ni = 0; ni < 4; ++ni)
-#pragma unroll
-        for (int mi = 0; mi < 4; ++mi) part[hh][ni][mi] = acc[4 * h + ni][4 * hh + mi];
-    nt_epilogue_any<T, EPI, 2, 1>(p, part, bv, m0, n0, 2 * wr, 2 * wc + h, lane,
-                                  reinterpret_cast<unsigned char *>(lds_all) + wave * nt_rows_lds(EPI));
-  }
-}
-#endif  // CUM_AB
 
 // ---------------------------------------------------------------- small-M variant (streaming hops)
 // Launches with only a few dozen 128x128 tiles (M = streams x a handful of rows) leave most of the chip idle while
@@ -1859,25 +1415,6 @@ __global__ void colsum_stage2(const float *__restrict__ part, int nparts, int n,
   out[c] = s;
 }
 
-#ifdef CUM_AB
-template <typename T>
-static int launch_gemm_nt8(const GemmParams &p, int epi, hipStream_t st) {
-  if constexpr (sizeof(T) == 2) {
-    const int NB = (p.N + 255) / 256, MB = (p.M + 255) / 256;
-    dim3 grid(8 * NB * ((MB + 7) / 8)), block(512);
-    switch (epi) {
-      case EPI_BIAS: hipLaunchKernelGGL((gemm_nt8_kernel<T, EPI_BIAS>), grid, block, 0, st, p); break;
-      case EPI_RELU: hipLaunchKernelGGL((gemm_nt8_kernel<T, EPI_RELU>), grid, block, 0, st, p); break;
-      case EPI_MASK: hipLaunchKernelGGL((gemm_nt8_kernel<T, EPI_MASK>), grid, block, 0, st, p); break;
-      case EPI_GLU_BWD: hipLaunchKernelGGL((gemm_nt8_kernel<T, EPI_GLU_BWD>), grid, block, 0, st, p); break;
-      default: hipLaunchKernelGGL((gemm_nt8_kernel<T, EPI_GLU>), grid, block, 0, st, p); break;
-    }
-    CUM_CHECK_LAUNCH();
-  }
-  return CUM_OK;
-}
-
-#endif  // CUM_AB
 
 template <typename T>
 static int launch_gemm_nt9(const GemmParams &p0, int epi, hipStream_t st) {
@@ -1885,30 +1422,7 @@ static int launch_gemm_nt9(const GemmParams &p0, int epi, hipStream_t st) {
     GemmParams p = p0;
     const int NB = (p.N + 255) / 256, MB = (p.M + 255) / 256;
     dim3 grid(8 * NB * ((MB + 7) / 8)), block(512);
-    p.group_m = (int)cum_knob("CUM_NT_GROUPM", NB >= 24 ? 4 : 1);
-    if (p.group_m < 1) p.group_m = 1;
-#ifdef CUM_AB
-#ifdef CUM_NT4_ONLY_BIAS                              // (tuning builds: one instantiation, a fifth of the compile time)
-    if (cum_knob("CUM_NT4", 0) != 0 && epi == EPI_BIAS) {
-      hipLaunchKernelGGL((gemm_nt4_kernel<T, EPI_BIAS>), grid, dim3(256), 0, st, p);
-      CUM_CHECK_LAUNCH();
-      return CUM_OK;
-    }
-#else
-    if (cum_knob("CUM_NT4", 0) != 0) {                 // the four-wave experiment (gemm_nt4_kernel)
-      const dim3 b4(256);
-      switch (epi) {
-        case EPI_BIAS: hipLaunchKernelGGL((gemm_nt4_kernel<T, EPI_BIAS>), grid, b4, 0, st, p); break;
-        case EPI_RELU: hipLaunchKernelGGL((gemm_nt4_kernel<T, EPI_RELU>), grid, b4, 0, st, p); break;
-        case EPI_MASK: hipLaunchKernelGGL((gemm_nt4_kernel<T, EPI_MASK>), grid, b4, 0, st, p); break;
-        case EPI_GLU_BWD: hipLaunchKernelGGL((gemm_nt4_kernel<T, EPI_GLU_BWD>), grid, b4, 0, st, p); break;
-        default: hipLaunchKernelGGL((gemm_nt4_kernel<T, EPI_GLU>), grid, b4, 0, st, p); break;
-      }
-      CUM_CHECK_LAUNCH();
-      return CUM_OK;
-    }
-#endif
-#endif
+    p.group_m = NB >= 24 ? 4 : 1;
     switch (epi) {
       case EPI_BIAS: hipLaunchKernelGGL((gemm_nt9_kernel<T, EPI_BIAS>), grid, block, 0, st, p); break;
       case EPI_RELU: hipLaunchKernelGGL((gemm_nt9_kernel<T, EPI_RELU>), grid, block, 0, st, p); break;
@@ -1960,40 +1474,28 @@ static int launch_gemm_tile(const GemmParams &p, int epi, hipStream_t st) {
 static int choose_tile(const GemmParams &p, int esz) {
   const int64_t mb256 = (p.M + 255) / 256;
   const int64_t tiles_256x256 = mb256 * ((p.N + 255) / 256), tiles_256x128 = mb256 * ((p.N + 127) / 128);
-  // AB build: CUM_NT_TILE=64|128|256|512 pins the tile (split-K 64x64 / 128x128 / 256x128 / 256x256)
-  int tile = (int)cum_knob("CUM_NT_TILE", 0);
   // few tiles and a K axis worth splitting: the small-M kernel (64x64 tiles, K split over the four waves)
   const int64_t tiles_128 = ((p.M + 127) / 128) * ((p.N + 127) / 128);
   const int bk = esz == 2 ? 64 : 32;
   // (allow_split_k == 2: the caller asks for it whatever the tile count -- the narrow Mamba projections, N <= 256 with
   //  K = 2048, where 128-wide tiles waste half of their columns and 78 row tiles do not fill the chip)
-  if ((tile == 64 || (!tile && (p.allow_split_k == 2 || (p.allow_split_k && tiles_128 <= 64)))) && p.K >= 4 * bk) return 64;
-  if (tile == 64) tile = 128;
-  if (!tile) {
-    // 256x256 (one workgroup per CU) once it fills the chip and N wastes little of the 256-wide tile; K >= 256 so the
-    // saved weight traffic matters (the outer layers are bound by their activation traffic, where the tile shape is
-    // irrelevant) ... and enough work per byte for one workgroup per CU to pay off: at N K / (N + K) < 256 (the 256 /
-    // 512-channel layers with 320 512 rows) four 128 x 128 workgroups per CU are 5-18 % faster (same-box per-call table)
-    if (esz == 2 && p.K >= 256 && tiles_256x256 >= 224 && p.N % 256 == 0 &&
-        (int64_t)p.N * p.K >= 256 * (int64_t)(p.N + p.K)) tile = 512;
-    // f32 (the parity path): 256-row tiles while they still give every CU >= 2 workgroups per XCD-round.  16-bit types
-    // never take this tile: the 128 x 128 kernel routes its epilogue through LDS, which the outer, HBM-bound layers gain
-    // more from than from the taller tile.
-    else if (esz == 4 && p.K >= 256 && tiles_256x128 >= 1024) tile = 256;
-    // few tiles, long K (M ~ 10 000 with N = 512 / 768): 128 x 256 tiles through the three-stage ring, one resident round
-    // (from 40 tiles up: below that -- batch-1 inference, M ~ 600 -- twice as many 128 x 128 workgroups measured 1-2 % ahead)
-    else if (esz == 2 && p.N % 256 == 0 && p.K >= 512 && ((p.M + 127) / 128) * (int64_t)(p.N / 256) <= cum_knob("CUM_NT_RING", 256) &&
-             ((p.M + 127) / 128) * (int64_t)(p.N / 256) >= 40)
-      tile = 384;
-    else tile = 128;
-  }
-  if (esz == 2) {
-#ifndef CUM_AB
-    if (tile == 256) tile = 128;
-#endif
-    return tile;
-  }
-  return tile == 512 ? 256 : tile;
+  if ((p.allow_split_k == 2 || (p.allow_split_k && tiles_128 <= 64)) && p.K >= 4 * bk) return 64;
+  // 256x256 (one workgroup per CU) once it fills the chip and N wastes little of the 256-wide tile; K >= 256 so the
+  // saved weight traffic matters (the outer layers are bound by their activation traffic, where the tile shape is
+  // irrelevant) ... and enough work per byte for one workgroup per CU to pay off: at N K / (N + K) < 256 (the 256 /
+  // 512-channel layers with 320 512 rows) four 128 x 128 workgroups per CU are 5-18 % faster (same-box per-call table)
+  if (esz == 2 && p.K >= 256 && tiles_256x256 >= 224 && p.N % 256 == 0 &&
+      (int64_t)p.N * p.K >= 256 * (int64_t)(p.N + p.K)) return 512;
+  // f32 (the parity path): 256-row tiles while they still give every CU >= 2 workgroups per XCD-round.  16-bit types
+  // never take this tile: the 128 x 128 kernel routes its epilogue through LDS, which the outer, HBM-bound layers gain
+  // more from than from the taller tile.
+  if (esz == 4 && p.K >= 256 && tiles_256x128 >= 1024) return 256;
+  // few tiles, long K (M ~ 10 000 with N = 512 / 768): 128 x 256 tiles through the three-stage ring, one resident round
+  // of at most 256 workgroups (from 40 tiles up: below that -- batch-1 inference, M ~ 600 -- twice as many 128 x 128
+  // workgroups measured 1-2 % ahead)
+  const int64_t tiles_128x256 = ((p.M + 127) / 128) * (int64_t)(p.N / 256);
+  if (esz == 2 && p.N % 256 == 0 && p.K >= 512 && tiles_128x256 <= 256 && tiles_128x256 >= 40) return 384;
+  return 128;
 }
 
 template <typename T>
@@ -2001,16 +1503,8 @@ static int launch_gemm(const GemmParams &p, int epi, hipStream_t st) {
   const int tile = choose_tile(p, (int)sizeof(T));
   if (tile == 64) return launch_gemm_splitk<T>(p, epi, st);
   if constexpr (sizeof(T) == 2) {
-    if (tile == 512) {
-#ifdef CUM_AB
-      if (cum_knob("CUM_NT9", 1) == 0) return launch_gemm_nt8<T>(p, epi, st);
-#endif
-      return launch_gemm_nt9<T>(p, epi, st);
-    }
+    if (tile == 512) return launch_gemm_nt9<T>(p, epi, st);
     if (tile == 384) return launch_gemm_ring<T>(p, epi, st);
-#ifdef CUM_AB
-    if (tile == 256) return launch_gemm_tile<T, 256, 128>(p, epi, st);
-#endif
     return launch_gemm_tile<T, 128, 128>(p, epi, st);
   } else {
     if (tile == 256) return launch_gemm_tile<T, 256, 128>(p, epi, st);
@@ -2052,7 +1546,7 @@ extern "C" int cum_gemm_nt(const cum_gemm_desc *d, const void *A, const void *W,
               "gemm: mask_bits applies to RELU (aux = sign array) and MASK (res = sign array)");
   p.M = d->M; p.N = d->N; p.K = d->K; p.pitch = d->pitch; p.valid = d->valid; p.n_store = d->n_store;
   p.zero_head = d->zero_head; p.zero_tail = d->zero_tail;
-  p.rows_epilogue = (int)cum_knob("CUM_NT8_ROWS", 1);      // AB build: 0 = the generic GLU-backward epilogue
+  p.rows_epilogue = 1;
   if (d->dtype == CUM_BF16) return launch_gemm<__bf16>(p, d->epilogue, (hipStream_t)stream);
   if (d->dtype == CUM_F16) return launch_gemm<f16>(p, d->epilogue, (hipStream_t)stream);
   return launch_gemm<float>(p, d->epilogue, (hipStream_t)stream);

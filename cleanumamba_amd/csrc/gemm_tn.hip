@@ -36,9 +36,6 @@ struct TnParams {
   int N, K;          // valid columns of dZ / of an X row (multiples of 4)
   int Np, Kp;        // slab dims (multiples of 128)
   int rows_per_split, nsplit;
-#ifdef CUM_AB
-  int skip_store;    // timing experiment (CUM_TN_NOSTORE=1, tools/tn_intercept.py): the slabs are not written
-#endif
 };
 
 constexpr int TN_T = 128;  // output tile (n and k)
@@ -465,14 +462,14 @@ __global__ __launch_bounds__(512) void gemm_tn_stream_kernel(const TnParams p) {
 }
 
 // ---------------------------------------------------------------- 256 x 256 output tile, 8 waves (16-bit types)
-// Same pipeline as gemm_nt8_kernel (gemm.hip): a reduction step of 64 rows is four 16 KB UNITS -- X columns 0-127 /
+// The unit pipeline of gemm_nt9_kernel (gemm.hip): a reduction step of 64 rows is four 16 KB UNITS -- X columns 0-127 /
 // 128-255 of the tile (X0, X1) and dZ columns 0-127 / 128-255 (Z0, Z1), each [64 rows][16 chunks] in the swizzled
 // layout of gemm_tn_kernel -- two steps of units = 128 KB of LDS, one workgroup per CU.  Wave (wk, wn) owns k columns
-// [128 wk, +128) x n columns [64 wn, +64): it reads unit X_wk whole at the start of the step (32 transposing reads, kept
-// in registers) and its half of Z_(wn >> 1) in two parts, so the X units are free after barrier B2 and the Z units after
-// B3, and step s + 2's units are DMA'd into them under step s's 64 MFMAs per wave; the top of step s + 1 waits
-// `vmcnt(8)`: step s + 1 has landed, step s + 2's eight DMAs stay in flight.  Fragment reads are inline asm for the
-// reason given in gemm.hip (the compiler would drain vmcnt before every LDS read of a DMA target).
+// [128 wk, +128) x n columns [64 wn, +64): it reads unit X_wk (32 transposing reads) and its half of Z_(wn >> 1) in two
+// parts, and step s + 2's units are DMA'd into step s's as they fall free, under step s's 64 MFMAs per wave; a counted
+// `vmcnt(4)` per step retires step s + 1 and leaves DMAs of step s + 2 in flight (schedule: in the kernel, in front of
+// the loop).  Fragment reads are inline asm for the reason given in gemm.hip (the compiler would drain vmcnt before
+// every LDS read of a DMA target).
 // The ragged step of a split (rows not a multiple of 64) is its FIRST one: its out-of-range rows are fetched from a
 // clamped row and zeroed in LDS in the prologue, where registers are plentiful; every later step is full.
 // Bias gradient: db[n] = sum_m dZ[m][n] is one more MFMA per dZ fragment with a 0/1 selector as the other operand
@@ -481,9 +478,9 @@ __global__ __launch_bounds__(512) void gemm_tn_stream_kernel(const TnParams p) {
 typedef __attribute__((ext_vector_type(2))) unsigned u32x2;
 typedef __attribute__((ext_vector_type(4))) unsigned u32x4;
 
-#ifdef CUM_AB   // gemm_tn8_kernel: the predecessor of gemm_tn9_kernel (same pipeline, all waves in one phase), CUM_TN9=0
+
 template <typename T>
-__global__ __launch_bounds__(512) void gemm_tn8_kernel(const TnParams p) {
+__global__ __launch_bounds__(512) void gemm_tn9_kernel(const TnParams p) {
   static_assert(sizeof(T) == 2, "16-bit element types only");
   constexpr int UNIT = 64 * 16;                      // 16-byte chunks of one unit
   __shared__ uint4 lds_all[2 * 4 * UNIT];            // [step parity][X0, X1, Z0, Z1]
@@ -612,250 +609,7 @@ __global__ __launch_bounds__(512) void gemm_tn8_kernel(const TnParams p) {
   // (x (ks, blk): v[176 + 32 ks + 4 blk ..+3], dZ (ks, ni): v[240 + 8 ks + 4 ni ..+3]).  A read defines its half, the wait
   // statement consumes both halves and defines the whole fragment in the same registers: no copies (checked in the ISA:
   // a v_mov of a half issued before the wait would read a register the LDS has not written yet).
-  for (int s = 0; s < nk; ++s) {
-    const int par = s & 1;
-    const bool more = s + 2 < nk;
-    if (s + 1 < nk) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");    // step s landed; step s + 1 stays in flight
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("s_barrier" ::: "memory");                              // B1
-    u32x2 xl[2][8], xh[2][8], zl[2][2], zh[2][2];
-    u32x4 xf[2][8], zf[2][2];
-    // ---- phase 1: reads in the order the MFMAs consume them
-    CUM_TR(zl[0][0], "v[240:241]", az[0], 0); CUM_TR(zh[0][0], "v[242:243]", az[0], 1024);  CUM_TR(zl[0][1], "v[244:245]", az[1], 0); CUM_TR(zh[0][1], "v[246:247]", az[1], 1024);
-    CUM_TR(xl[0][0], "v[176:177]", ax[0], 0); CUM_TR(xh[0][0], "v[178:179]", ax[0], 1024);  CUM_TR(xl[0][1], "v[180:181]", ax[1], 0); CUM_TR(xh[0][1], "v[182:183]", ax[1], 1024);
-    CUM_TR(xl[0][2], "v[184:185]", ax[2], 0); CUM_TR(xh[0][2], "v[186:187]", ax[2], 1024);  CUM_TR(xl[0][3], "v[188:189]", ax[3], 0); CUM_TR(xh[0][3], "v[190:191]", ax[3], 1024);
-    CUM_TR(zl[1][0], "v[248:249]", az[0], 8192); CUM_TR(zh[1][0], "v[250:251]", az[0], 9216);  CUM_TR(zl[1][1], "v[252:253]", az[1], 8192); CUM_TR(zh[1][1], "v[254:255]", az[1], 9216);
-    CUM_TR(xl[1][0], "v[208:209]", ax[0], 8192); CUM_TR(xh[1][0], "v[210:211]", ax[0], 9216);  CUM_TR(xl[1][1], "v[212:213]", ax[1], 8192); CUM_TR(xh[1][1], "v[214:215]", ax[1], 9216);
-    CUM_TR(xl[1][2], "v[216:217]", ax[2], 8192); CUM_TR(xh[1][2], "v[218:219]", ax[2], 9216);  CUM_TR(xl[1][3], "v[220:221]", ax[3], 8192); CUM_TR(xh[1][3], "v[222:223]", ax[3], 9216);
-    asm volatile("s_waitcnt lgkmcnt(12)"
-                 : "={v[240:243]}"(zf[0][0]), "={v[244:247]}"(zf[0][1]), "={v[176:179]}"(xf[0][0]), "={v[180:183]}"(xf[0][1]), "={v[184:187]}"(xf[0][2]), "={v[188:191]}"(xf[0][3])
-                 : "{v[240:241]}"(zl[0][0]), "{v[242:243]}"(zh[0][0]),
-                   "{v[244:245]}"(zl[0][1]), "{v[246:247]}"(zh[0][1]),
-                   "{v[176:177]}"(xl[0][0]), "{v[178:179]}"(xh[0][0]),
-                   "{v[180:181]}"(xl[0][1]), "{v[182:183]}"(xh[0][1]),
-                   "{v[184:185]}"(xl[0][2]), "{v[186:187]}"(xh[0][2]),
-                   "{v[188:189]}"(xl[0][3]), "{v[190:191]}"(xh[0][3]) : "memory");
-    __builtin_amdgcn_s_setprio(1);
-    CUM_HALFQ(0, 0, 0);
-    __builtin_amdgcn_sched_barrier(0);
-    CUM_TR(xl[0][4], "v[192:193]", ax[4], 0); CUM_TR(xh[0][4], "v[194:195]", ax[4], 1024);  CUM_TR(xl[0][5], "v[196:197]", ax[5], 0); CUM_TR(xh[0][5], "v[198:199]", ax[5], 1024);
-    CUM_TR(xl[0][6], "v[200:201]", ax[6], 0); CUM_TR(xh[0][6], "v[202:203]", ax[6], 1024);  CUM_TR(xl[0][7], "v[204:205]", ax[7], 0); CUM_TR(xh[0][7], "v[206:207]", ax[7], 1024);
-    asm volatile("s_waitcnt lgkmcnt(8)"
-                 : "={v[248:251]}"(zf[1][0]), "={v[252:255]}"(zf[1][1]), "={v[208:211]}"(xf[1][0]), "={v[212:215]}"(xf[1][1]), "={v[216:219]}"(xf[1][2]), "={v[220:223]}"(xf[1][3])
-                 : "{v[248:249]}"(zl[1][0]), "{v[250:251]}"(zh[1][0]),
-                   "{v[252:253]}"(zl[1][1]), "{v[254:255]}"(zh[1][1]),
-                   "{v[208:209]}"(xl[1][0]), "{v[210:211]}"(xh[1][0]),
-                   "{v[212:213]}"(xl[1][1]), "{v[214:215]}"(xh[1][1]),
-                   "{v[216:217]}"(xl[1][2]), "{v[218:219]}"(xh[1][2]),
-                   "{v[220:221]}"(xl[1][3]), "{v[222:223]}"(xh[1][3]) : "memory");
-    CUM_HALFQ(0, 0, 1);
-    __builtin_amdgcn_sched_barrier(0);
-    CUM_TR(xl[1][4], "v[224:225]", ax[4], 8192); CUM_TR(xh[1][4], "v[226:227]", ax[4], 9216);  CUM_TR(xl[1][5], "v[228:229]", ax[5], 8192); CUM_TR(xh[1][5], "v[230:231]", ax[5], 9216);
-    CUM_TR(xl[1][6], "v[232:233]", ax[6], 8192); CUM_TR(xh[1][6], "v[234:235]", ax[6], 9216);  CUM_TR(xl[1][7], "v[236:237]", ax[7], 8192); CUM_TR(xh[1][7], "v[238:239]", ax[7], 9216);
-    CUM_BIAS(0);
-    __builtin_amdgcn_s_setprio(0);
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "={v[192:195]}"(xf[0][4]), "={v[196:199]}"(xf[0][5]), "={v[200:203]}"(xf[0][6]), "={v[204:207]}"(xf[0][7]), "={v[224:227]}"(xf[1][4]), "={v[228:231]}"(xf[1][5]), "={v[232:235]}"(xf[1][6]), "={v[236:239]}"(xf[1][7])
-                 : "{v[192:193]}"(xl[0][4]), "{v[194:195]}"(xh[0][4]),
-                   "{v[196:197]}"(xl[0][5]), "{v[198:199]}"(xh[0][5]),
-                   "{v[200:201]}"(xl[0][6]), "{v[202:203]}"(xh[0][6]),
-                   "{v[204:205]}"(xl[0][7]), "{v[206:207]}"(xh[0][7]),
-                   "{v[224:225]}"(xl[1][4]), "{v[226:227]}"(xh[1][4]),
-                   "{v[228:229]}"(xl[1][5]), "{v[230:231]}"(xh[1][5]),
-                   "{v[232:233]}"(xl[1][6]), "{v[234:235]}"(xh[1][6]),
-                   "{v[236:237]}"(xl[1][7]), "{v[238:239]}"(xh[1][7]) : "memory");
-    asm volatile("s_barrier" ::: "memory");                              // B2: the X units of this parity are free
-    if (more) {
-      CUM_STAGE(0, s + 2, par);
-      CUM_STAGE(1, s + 2, par);
-    }
-    // ---- phase 2
-    __builtin_amdgcn_s_setprio(1);
-    CUM_HALFQ(1, 0, 0);
-    CUM_HALFQ(1, 0, 1);
-    __builtin_amdgcn_s_setprio(0);
-    __builtin_amdgcn_sched_barrier(0);
-    // ---- phase 3: dZ fragments of n columns 32-63 (same registers as columns 0-31)
-    CUM_TR(zl[0][0], "v[240:241]", az[2], 0); CUM_TR(zh[0][0], "v[242:243]", az[2], 1024);  CUM_TR(zl[0][1], "v[244:245]", az[3], 0); CUM_TR(zh[0][1], "v[246:247]", az[3], 1024);
-    CUM_TR(zl[1][0], "v[248:249]", az[2], 8192); CUM_TR(zh[1][0], "v[250:251]", az[2], 9216);  CUM_TR(zl[1][1], "v[252:253]", az[3], 8192); CUM_TR(zh[1][1], "v[254:255]", az[3], 9216);
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "={v[240:243]}"(zf[0][0]), "={v[244:247]}"(zf[0][1]), "={v[248:251]}"(zf[1][0]), "={v[252:255]}"(zf[1][1])
-                 : "{v[240:241]}"(zl[0][0]), "{v[242:243]}"(zh[0][0]),
-                   "{v[244:245]}"(zl[0][1]), "{v[246:247]}"(zh[0][1]),
-                   "{v[248:249]}"(zl[1][0]), "{v[250:251]}"(zh[1][0]),
-                   "{v[252:253]}"(zl[1][1]), "{v[254:255]}"(zh[1][1]) : "memory");
-    asm volatile("s_barrier" ::: "memory");                              // B3: the Z units of this parity are free
-    if (more) {
-      CUM_STAGE(2, s + 2, par);
-      CUM_STAGE(3, s + 2, par);
-    }
-    __builtin_amdgcn_s_setprio(1);
-    CUM_HALFQ(1, 2, 0);
-    CUM_HALFQ(1, 2, 1);
-    // ---- phase 4
-    CUM_HALFQ(0, 2, 0);
-    CUM_HALFQ(0, 2, 1);
-    CUM_BIAS(2);
-    __builtin_amdgcn_s_setprio(0);
-    const unsigned flip = par ? 0u - 65536u : 65536u;                   // the other parity's units
-#pragma unroll
-    for (int b = 0; b < 8; ++b) ax[b] += flip;
-#pragma unroll
-    for (int b = 0; b < 4; ++b) az[b] += flip;
-  }
-#undef CUM_TR
-#undef CUM_MFMA
-#undef CUM_HALFQ
-#undef CUM_BIAS
-#undef CUM_STAGE
-
-  // ---- slab store: lane holds D[k = kb + 4g + j][n = nb + r]
-  float *slab = p.slab + (int64_t)sp * p.Np * p.Kp;
-#pragma unroll
-  for (int ni = 0; ni < 4; ++ni) {
-    const int n = n0 + wn * 64 + ni * 16 + r;
-#pragma unroll
-    for (int h = 0; h < 2; ++h)
-#pragma unroll
-      for (int ki = 0; ki < 4; ++ki) {
-        const int k = k0 + wk * 128 + h * 64 + ki * 16 + 4 * g;
-        *reinterpret_cast<float4 *>(slab + (int64_t)n * p.Kp + k) =
-            make_float4(acc[h][ni][ki][0], acc[h][ni][ki][1], acc[h][ni][ki][2], acc[h][ni][ki][3]);
-      }
-  }
-  // selector rows 4 ni .. 4 ni + 3 (held by lane group g = ni) carry the column sums of fragment ni
-  if (bias_wave) p.bslab[(int64_t)sp * p.Np + n0 + wn * 64 + 16 * g + r] = bacc[0];
-}
-
-#endif  // CUM_AB
-
-template <typename T>
-__global__ __launch_bounds__(512) void gemm_tn9_kernel(const TnParams p) {
-  static_assert(sizeof(T) == 2, "16-bit element types only");
-  constexpr int UNIT = 64 * 16;                      // 16-byte chunks of one unit
-  __shared__ uint4 lds_all[2 * 4 * UNIT];            // [step parity][X0, X1, Z0, Z1]
-
-  const int tid = threadIdx.x, lane = tid & 63;
-  const int wave = uniform(tid >> 6);
-  const int wk = wave >> 2, wn = wave & 3;
-  const int g = lane >> 4, r = lane & 15;
-  // One resident round: work item w = xcd * (slots per XCD) + slot, split = w / tiles, tile = w % tiles (n fastest):
-  // the workgroups of one XCD hold consecutive tiles of one or two splits, so their rows meet in that XCD's L2.
-  const int ntn = p.Np / 256, ntk = p.Kp / 256, tiles = ntn * ntk;
-  const int w = (int)(blockIdx.x & 7) * (int)(gridDim.x >> 3) + (int)(blockIdx.x >> 3);
-  if (w >= tiles * p.nsplit) return;
-  const int sp = w / tiles, tile = w % tiles;
-  const int n0 = (tile % ntn) * 256, k0 = (tile / ntn) * 256;
-  const int64_t m_begin = (int64_t)sp * p.rows_per_split;
-  int64_t m_end = m_begin + p.rows_per_split;
-  m_end = m_end < p.M ? m_end : p.M;
-  const int len = (int)(m_end - m_begin);
-  const int nk = (len + 63) / 64;
-  const int rem = len - 64 * (nk - 1);               // rows of step 0 (1 .. 64)
-  const T *dZ = static_cast<const T *>(p.dZ);
-  const T *X = static_cast<const T *>(p.X);
-  const bool bias_wave = p.bslab != nullptr && k0 == 0 && wk == 0;
-
-  typedef __attribute__((address_space(3))) void *lds_ptr;
-  typedef const __attribute__((address_space(1))) void *glb_ptr;
-  // DMA sources: unit u, instruction it fills linear chunk it * 512 + tid of the unit = (row, physical chunk).  The
-  // address is a wave-uniform base (SGPRs: tile corner + step) plus a small per-thread byte offset (row * ld + chunk),
-  // so a step's eight DMAs need four offset registers and no vector address arithmetic.
-  const int64_t stepx = 128 * p.ldx, stepz = 128 * p.ldz;                 // bytes per 64-row step
-  const char *xb = reinterpret_cast<const char *>(X + k0) + m_begin * p.ldx * 2;
-  const char *zb = reinterpret_cast<const char *>(dZ + n0) + m_begin * p.ldz * 2;
-  unsigned xo[2], zo[2];
-#pragma unroll
-  for (int it = 0; it < 2; ++it) {
-    const int pos = it * 512 + tid;
-    const int row = pos >> 4;
-    const int clog = (pos & 15) ^ TnCfg<T>::swz(row);
-    const int rowc = row < rem ? row : rem - 1;                            // step 0: clamped rows (zeroed below)
-    xo[it] = (unsigned)(row * (int)p.ldx * 2 + clog * 16);
-    zo[it] = (unsigned)(row * (int)p.ldz * 2 + clog * 16);
-    const unsigned x0 = (unsigned)(rowc * (int)p.ldx * 2 + clog * 16), z0 = (unsigned)(rowc * (int)p.ldz * 2 + clog * 16);
-#pragma unroll
-    for (int u = 0; u < 4; ++u)
-      __builtin_amdgcn_global_load_lds((glb_ptr)((u < 2 ? xb + x0 : zb + z0) + 256 * (u & 1)),
-                                       (lds_ptr)(&lds_all[u * UNIT + it * 512 + wave * 64]), 16, 0, 0);
-  }
-  // step s >= 1 covers rows m_begin + rem + 64 (s - 1) ..: base of step s = b1 + s * step
-  const char *xb1 = xb + (int64_t)(rem - 64) * p.ldx * 2, *zb1 = zb + (int64_t)(rem - 64) * p.ldz * 2;
-#define CUM_STAGE(u, s, par)                                                                                    \
-  do {                                                                                                          \
-    const char *ub = ((u) < 2 ? xb1 + (s) * stepx : zb1 + (s) * stepz) + 256 * ((u) & 1);                        \
-    _Pragma("unroll") for (int it = 0; it < 2; ++it)                                                           \
-      __builtin_amdgcn_global_load_lds((glb_ptr)(ub + ((u) < 2 ? xo[it] : zo[it])),                            \
-                                       (lds_ptr)(&lds_all[((par) * 4 + (u)) * UNIT + it * 512 + wave * 64]), 16, 0, 0); \
-  } while (0)
-  if (nk > 1) {
-#pragma unroll
-    for (int u = 0; u < 4; ++u) CUM_STAGE(u, 1, 1);
-  }
-  if (rem < 64) {                                    // rows past the end of the split must contribute nothing
-    if (nk > 1) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#pragma unroll
-    for (int it = 0; it < 2; ++it) {
-      const int pos = it * 512 + tid;
-      if ((pos >> 4) >= rem) {                       // this thread's own DMA filled the chunk: no barrier needed
-#pragma unroll
-        for (int u = 0; u < 4; ++u) lds_all[u * UNIT + pos] = make_uint4(0, 0, 0, 0);
-      }
-    }
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-
-  f32x4 acc[2][4][4];                                // [k half][ni][ki]: k = 128 wk + 64 h + 16 ki + 4 g + j, n = 64 wn + 16 ni + r
-#pragma unroll
-  for (int h = 0; h < 2; ++h)
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) acc[h][i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
-  f32x4 bacc = f32x4{0.f, 0.f, 0.f, 0.f};
-
-  // Transposing reads (see gemm_tn_kernel): lane (g, q = r >> 2, pp = r & 3) addresses row 32 ks + 8 g + q (+ 4 for the
-  // upper half of the fragment), columns 16 blk + 4 pp ..; the row swizzle term t = q | (g & 1) << 2 is the same for both
-  // halves and both ks, so a block's four reads share one address register and differ by immediate offsets.
-  const int q = r >> 2, pp = r & 3, t = q | ((g & 1) << 2);
-  const unsigned lds0 = (unsigned)(uintptr_t)(lds_ptr)lds_all;
-  const unsigned lane_base = lds0 + (unsigned)((8 * g + q) * 256 + 8 * pp);
-  unsigned ax[8], az[4];
-#pragma unroll
-  for (int b = 0; b < 8; ++b) ax[b] = lane_base + (unsigned)(wk * UNIT * 16 + 32 * (b ^ t));
-#pragma unroll
-  for (int b = 0; b < 4; ++b) az[b] = lane_base + (unsigned)((2 + (wn >> 1)) * UNIT * 16 + 32 * ((4 * (wn & 1) + b) ^ t));
-  // bias selector for fragment ni: lanes whose MFMA row r lies in [4 ni, 4 ni + 4) hold ones
-  const unsigned one2 = __is_same(T, f16) ? 0x3C003C00u : 0x3F803F80u;
-
-#define CUM_TR(dst, reg, addr, off) asm volatile("ds_read_b64_tr_b16 %0, %1 offset:" #off : "={" reg "}"(dst) : "v"(addr) : "memory")
-#define CUM_MFMA(a, b, c)                                                                                      \
-  do {                                                                                                         \
-    if constexpr (__is_same(T, f16))                                                                           \
-      c = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, a), __builtin_bit_cast(f16x8, b), c, 0, 0, 0); \
-    else                                                                                                       \
-      c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, a), __builtin_bit_cast(bf16x8, b), c, 0, 0, 0); \
-  } while (0)
-#define CUM_HALFQ(h, nlo, ks)                                                                                  \
-  do {                                                                                                         \
-    _Pragma("unroll") for (int ni = 0; ni < 2; ++ni)                                                           \
-      _Pragma("unroll") for (int ki = 0; ki < 4; ++ki)                                                         \
-        CUM_MFMA(xf[ks][4 * (h) + ki], zf[ks][ni], acc[h][(nlo) + ni][ki]);                                    \
-  } while (0)
-#define CUM_BIAS(nlo)                                                                                          \
-  do {                                                                                                         \
-    if (bias_wave) {                                                                                           \
-      _Pragma("unroll") for (int ni = 0; ni < 2; ++ni) {                                                       \
-        const unsigned sv = q == (nlo) + ni ? one2 : 0u;                                                       \
-        const u32x4 sel = u32x4{sv, sv, sv, sv};                                                               \
-        _Pragma("unroll") for (int ks = 0; ks < 2; ++ks) CUM_MFMA(sel, zf[ks][ni], bacc);                      \
-      }                                                                                                        \
-    }                                                                                                          \
-  } while (0)
-
-  // Fragments are pinned to physical registers as in gemm_tn8_kernel (x (ks, blk): v[176 + 32 ks + 4 blk ..+3], dZ (ks, ni):
-  // v[240 + 8 ks + 4 ni ..+3]).  Schedule: gemm_nt9_kernel's ping-pong (gemm.hip) -- eight slots per reduction step, load
+  // Schedule: gemm_nt9_kernel's ping-pong (gemm.hip) -- eight slots per reduction step, load
   // and compute alternating, waves 4-7 (wk = 1, the X1 unit) one slot behind waves 0-3 (wk = 0, X0):
   //   L1: X columns 0-63 of the wave's half + dZ columns 0-31 (24 reads)   C1: (k 0-63,  n 0-31) + bias MFMAs
   //   L2: X columns 64-127 (16 reads)                                      C2: (k 64-127, n 0-31)
@@ -979,9 +733,6 @@ __global__ __launch_bounds__(512) void gemm_tn9_kernel(const TnParams p) {
 #undef CUM_BIAS
 #undef CUM_STAGE
 
-#ifdef CUM_AB
-  if (p.skip_store && acc[0][0][0][0] != 12345.f) return;
-#endif
   // ---- slab store: lane holds D[k = kb + 4g + j][n = nb + r]
   float *slab = p.slab + (int64_t)sp * p.Np * p.Kp;
 #pragma unroll
@@ -1060,29 +811,25 @@ __global__ __launch_bounds__(256) void tn_reduce_kernel(const ReduceJob j0, cons
 
 using namespace cum;
 
-static int tn8_enabled() { return (int)cum_knob("CUM_TN8", 1); }      // AB build: 0 = the 128 x 128 kernel everywhere
-
-// 256 x 256 tiles (gemm_tn8_kernel): 16-bit types, N and K multiples of 256.  One workgroup per CU, so the split count is
+// 256 x 256 tiles (gemm_tn9_kernel): 16-bit types, N and K multiples of 256.  One workgroup per CU, so the split count is
 // the largest that keeps tiles x splits within ONE resident round of 256 workgroups.
 static bool tn_use8(int64_t M, int32_t N, int32_t K, int32_t dtype) {
-  return is16(dtype) && N % 256 == 0 && K % 256 == 0 && M >= 256 && tn8_enabled();
+  return is16(dtype) && N % 256 == 0 && K % 256 == 0 && M >= 256;
 }
 
 // The streaming kernel (gemm_tn_stream_kernel): 16-bit types, a padded result of exactly 128 x 256 or 256 x 128, and enough
 // rows that 256 splits (one workgroup per CU, one resident round) still run >= 8 steps each.
 static bool tn_use_stream(int64_t M, int32_t N, int32_t K, int32_t dtype) {
-  if (!is16(dtype) || tn_use8(M, N, K, dtype) || cum_knob("CUM_TN_STREAM", 1) == 0) return false;
+  if (!is16(dtype) || tn_use8(M, N, K, dtype)) return false;
   const int np = (N + TN_T - 1) / TN_T, kp = (K + TN_T - 1) / TN_T;
   return np * kp == 2 && M >= 256 * 64 * 8;
 }
 
 static void tn_plan(int64_t M, int32_t N, int32_t K, int32_t dtype, int *Np, int *Kp, int *S, int *rps) {
-  const int force = (int)cum_knob("CUM_TN_SPLITS", 0);             // AB build: pins the split count
   if (tn_use_stream(M, N, K, dtype)) {
     *Np = (N + TN_T - 1) / TN_T * TN_T;
     *Kp = (K + TN_T - 1) / TN_T * TN_T;
     int64_t rows = (M + 255) / 256;
-    if (force > 0) rows = (M + force - 1) / force;
     rows = (rows + 63) / 64 * 64;
     *rps = (int)rows;
     *S = (int)((M + rows - 1) / rows);
@@ -1093,7 +840,6 @@ static void tn_plan(int64_t M, int32_t N, int32_t K, int32_t dtype, int *Np, int
     *Kp = K;
     const int tiles = (N / 256) * (K / 256);
     int64_t want = tiles >= 256 ? 1 : 256 / tiles;
-    if (force > 0) want = force;
     const int64_t max_s = (M + 255) / 256;              // at least 4 steps per split
     if (want > max_s) want = max_s;
     int64_t rows = (M + want - 1) / want;
@@ -1110,10 +856,9 @@ static void tn_plan(int64_t M, int32_t N, int32_t K, int32_t dtype, int *Np, int
   // with >= 96 tiles already fills its XCD: 8 splits.  Smaller tile counts take as many splits per XCD as fit into
   // ONE resident round (32 tiles -> 3 per XCD = 24 splits): a second, partly filled round costs a full round's
   // time (measured on the E8 shapes: -18...-27 % against "about 1024 workgroups"), and every extra split adds a
-  // slab of Np x Kp floats to write and reduce.  CUM_TN_SPLITS pins the count for experiments.
+  // slab of Np x Kp floats to write and reduce.
   const int per_xcd = tiles >= 96 ? 1 : 96 / tiles;
   int64_t want = 8 * per_xcd;
-  if (force > 0) want = force;
   const int64_t max_s = (M + 8 * bmk - 1) / (8 * bmk);  // at least 8 steps per split
   if (want > max_s) want = max_s;
   if (want < 1) want = 1;
@@ -1161,19 +906,10 @@ extern "C" int cum_gemm_tn(int32_t dtype, int64_t M, int32_t N, int32_t K, const
   p.nsplit = S;
   p.slab = workspace;
   p.bslab = want_bias ? workspace + (int64_t)S * Np * Kp : nullptr;
-#ifdef CUM_AB
-  p.skip_store = (int)cum_knob("CUM_TN_NOSTORE", 0);
-#endif
   dim3 grid(8 * (Np / TN_T) * (Kp / TN_T) * ((S + 7) / 8)), block(256);
   if (tn_use8(M, N, K, dtype)) {
     const int items = (N / 256) * (K / 256) * S;
     const dim3 grid8(8 * ((items + 7) / 8)), block8(512);
-#ifdef CUM_AB
-    if (cum_knob("CUM_TN9", 1) == 0) {
-      if (dtype == CUM_BF16) hipLaunchKernelGGL(gemm_tn8_kernel<__bf16>, grid8, block8, 0, st, p);
-      else hipLaunchKernelGGL(gemm_tn8_kernel<f16>, grid8, block8, 0, st, p);
-    } else
-#endif
     if (dtype == CUM_BF16)
       hipLaunchKernelGGL(gemm_tn9_kernel<__bf16>, grid8, block8, 0, st, p);
     else
@@ -1195,9 +931,6 @@ extern "C" int cum_gemm_tn(int32_t dtype, int64_t M, int32_t N, int32_t K, const
   else
     hipLaunchKernelGGL(gemm_tn_kernel<float>, grid, block, 0, st, p);
   CUM_CHECK_LAUNCH();
-#ifdef CUM_AB
-  if (cum_knob("CUM_TN_NOREDUCE", 0)) return CUM_OK;      // timing experiment: the slabs are not combined
-#endif
   // combine the slabs: one pass for few slabs, two passes (16 partial sums, then those) for many
   const int C = reduce_chunks(S);
   float *part = workspace + (int64_t)S * Np * Kp + (int64_t)S * Np;

@@ -154,9 +154,6 @@ __global__ __launch_bounds__(NW * 64) void scan_bwd_kernel(const ScanParams p) {
   const int nvalid = FULL ? NS : ((N - n0) < NS ? (N - n0) : NS);
   const int nchunks = p.nchunks;
   const int hm = lane_hmask(lane);       // slot k of this lane holds state n0 + (k ^ hm)
-#ifdef CUM_BWD_PRIO   // experiment: static priority for the second-dispatched half of the workgroup (MI355X_MICROARCH.md, item 4)
-  if (NW == 8 && w >= 4) __builtin_amdgcn_s_setprio(1);
-#endif
 
   f2 Ap[NP2], dAacc[NP2], dxc[NP2];
 #pragma unroll
@@ -719,13 +716,11 @@ static int scan_bwd_impl(const cum_scan_shape *s, const cum_scan_grad_strides *g
   switch ((s->dstate + NS - 1) / NS) {
     case 1:
     case 2: rc = launch_bwd_small(p, st); break;
-#ifndef CUM_ONLY8   // (compile-time experiments on the d_state-64 kernel alone)
     case 3: rc = launch_bwd<3>(p, st); break;
     case 4: rc = launch_bwd<4>(p, st); break;
     case 5: rc = launch_bwd<5>(p, st); break;
     case 6: rc = launch_bwd<6>(p, st); break;
     case 7: rc = launch_bwd<7>(p, st); break;
-#endif
     default: rc = launch_bwd<8>(p, st); break;
   }
   if (rc) return rc;

@@ -6,8 +6,8 @@
 //   * wave  <-> slice of NS = 8 states; the NW = ceil(N/8) waves of a workgroup cover
 //     all states of its 64 channels (N = 64 -> 8 waves, 512 threads),
 //   * time is walked sequentially; x_t lives in VGPRs for the whole sequence,
-//   * B_t / C_t are wave-uniform -> read through the constant address space so they
-//     arrive by s_load into SGPRs (no LDS traffic, no VGPRs),
+//   * B_t / C_t are wave-uniform -> a chunk's [16][N] tiles are staged in LDS with coalesced
+//     loads and read back as wave-uniform ds_read_b128 broadcasts,
 //   * per 16-step chunk the workgroup computes softplus / silu once per (t, d) into
 //     LDS (phase A), scans (phase B), and sums the per-wave partial results over the
 //     state slices through LDS (phase C).
@@ -50,12 +50,6 @@ struct ScanParams {
 // registers the recurrence walks, where the kernels set x = 0.  Padding states stay 0.  Called only by the ENTER
 // instantiations of the forward kernels (launched when init_state is given): the ones the plain entries reach carry
 // no trace of it -- a run-time test of the pointer cost them a register and scalar spills (profiles/scan_fwd_resources.md).
-__device__ __forceinline__ void scan_enter(const ScanParams &p, int b, int dc, int n0, int nvalid, float (&x)[NS]) {
-  const float *is = p.init_state + ((int64_t)b * p.s.dim + dc) * p.s.dstate + n0;
-#pragma unroll
-  for (int j = 0; j < NS; ++j)
-    if (j < nvalid) x[j] = is[j];
-}
 template <int NP2>
 __device__ __forceinline__ void scan_enter(const ScanParams &p, int b, int dc, int n0, int nvalid, f2 (&x)[NP2]) {
   const float *is = p.init_state + ((int64_t)b * p.s.dim + dc) * p.s.dstate + n0;
@@ -70,11 +64,6 @@ __device__ __forceinline__ void scan_enter(const ScanParams &p, int b, int dc, i
 __device__ __forceinline__ int64_t ckpt_slot(int b, int nchunks, int c, int h, int NW, int w, int Dm, int d) {
   return (((((int64_t)b * nchunks + c) * 2 + h) * NW + w) * Dm + d) * NS;
 }
-__device__ __forceinline__ void ckpt_store(float *ck, int64_t slot, const float (&x)[NS]) {
-  float4 *q = reinterpret_cast<float4 *>(ck + slot);
-  q[0] = make_float4(x[0], x[1], x[2], x[3]);
-  q[1] = make_float4(x[4], x[5], x[6], x[7]);
-}
 __device__ __forceinline__ void ckpt_store(float *ck, int64_t slot, const f2 (&x)[NS / 2]) {
   float4 *q = reinterpret_cast<float4 *>(ck + slot);
   q[0] = make_float4(x[0].x, x[0].y, x[1].x, x[1].y);
@@ -86,8 +75,8 @@ __device__ __forceinline__ void ckpt_load(const float *ck, int64_t slot, f2 (&x)
   x[0] = f2{a.x, a.y}; x[1] = f2{a.z, a.w}; x[2] = f2{c.x, c.y}; x[3] = f2{c.z, c.w};
 }
 
-// Checkpoint buffer, d_state > 16 (NW >= 3 waves per workgroup; written by scan_fwd_kernel / scan_fwd_lds_kernel /
-// scan_seg_kernel, read by scan_bwd_kernel): per (b, c, h, w, 64-channel group g) a block of 8 x 64 floats, STATE-major --
+// Checkpoint buffer, d_state > 16 (NW >= 3 waves per workgroup; written by scan_fwd_lds_kernel / scan_seg_kernel,
+// read by scan_bwd_kernel): per (b, c, h, w, 64-channel group g) a block of 8 x 64 floats, STATE-major --
 // [state n of the wave's slice][column pi(lane)], pi(l) = (l & 7) * 8 + (l >> 3).  The backward kernel keeps state
 // k ^ h(lane) in register slot k (scan_bwd.hip, "xor scatter"), h a function of lane & 7: in this layout its load of slot
 // k touches 8 whole 32-byte sectors per wave (lanes with equal lane & 7 sit side by side in one row), where a lane-major
@@ -99,7 +88,6 @@ __device__ __forceinline__ int64_t ckpt_wide_block(int b, int nchunks, int c, in
   const int G = (Dm + 63) >> 6;
   return (((((int64_t)b * nchunks + c) * 2 + h) * NW + w) * G + g) * (64 * NS);
 }
-__device__ __forceinline__ float ckpt_elem(const float (&x)[NS], int n) { return x[n]; }
 __device__ __forceinline__ float ckpt_elem(const f2 (&x)[NS / 2], int n) { return x[n / 2][n % 2]; }
 // the state a lane holds in natural order (x[n] = state n of the wave's slice) -> the layout its NW asks for
 template <int NW, typename X>
@@ -127,25 +115,6 @@ constexpr int kScanSoftplus = 1, kScanAIsLog = 2;
 __device__ __forceinline__ float scan_A(const ScanParams &p, int64_t idx) {
   const float a = p.A[idx];
   return (p.s.delta_softplus & kScanAIsLog) ? -expf(a) : a;
-}
-
-typedef const float __attribute__((address_space(4))) *cfp;
-
-// B_t or C_t slice of this wave (wave-uniform address -> s_load_dwordx8).
-template <bool FAST>
-__device__ __forceinline__ void load_bc(const float *base, int sn, int nvalid, float (&v)[NS]) {
-  cfp bp = (cfp)base;
-  if constexpr (FAST) {
-#pragma unroll
-    for (int j = 0; j < NS; ++j) v[j] = bp[j];
-  } else {
-#pragma unroll
-    for (int j = 0; j < NS; ++j) {
-      const int jj = j < nvalid ? j : nvalid - 1;
-      const float t = bp[jj * sn];
-      v[j] = j < nvalid ? t : 0.f;
-    }
-  }
 }
 
 int scan_check_shape(const cum_scan_shape *s);

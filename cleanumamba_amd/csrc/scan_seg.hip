@@ -242,16 +242,15 @@ void scan_seg_plan(int batch, int dim, int dstate, int len, int *nseg, int *seg_
   const int nchunks = (len + TB - 1) / TB;
   *nseg = 1;
   *seg_chunks = nchunks;
-  const int64_t force = cum_knob("CUM_SCAN_SEGMENTS", -1);       // AB build: 0 = never, n > 1 = that many segments
-  if (force == 0 || waves <= 0 || nchunks < 6) return;
+  if (waves <= 0 || nchunks < 6) return;
   // Measured on MI355X (bench.py scan rows, same box): at d_state > 16 the sequential kernel runs 8 waves per 64 channels and
   // the segmented form pays from < 1 wave per SIMD (batch <= 3 at D = 2048); at d_state <= 16 the sequential kernels are
   // the wave-specialised ones (producer + consumer waves: already two waves per SIMD at 512 "waves" here) and the
   // segmented form, which uses the generic chunk structure, only wins while the grid is <= 256 waves (B = 16, D = 2048,
   // N = 16: 0.56 ms sequential against 0.64 ms segmented -- not taken).
-  if (force < 0 && waves >= (NW > 2 ? 1024 : 257)) return;
+  if (waves >= (NW > 2 ? 1024 : 257)) return;
   const int64_t target = NW > 2 ? 2048 : 4096;
-  int64_t want = force > 1 ? force : (target + waves - 1) / waves;
+  const int64_t want = (target + waves - 1) / waves;
   int sc = (int)((nchunks + want - 1) / want);
   if (sc < 2) sc = 2;
   const int S = (nchunks + sc - 1) / sc;
@@ -271,10 +270,8 @@ void scan_seg_plan_bwd(int batch, int dim, int dstate, int len, int *nseg, int *
   const int nchunks = (len + TB - 1) / TB;
   *nseg = 1;
   *seg_chunks = nchunks;
-  const int64_t force = cum_knob("CUM_SCAN_BWD_SEGMENTS", -1);   // AB build: 0 = never, n > 1 = that many segments
-  if (dstate > 2 * NS || force == 0 || groups <= 0 || nchunks < 6) return;
-  if (force < 0 && groups > 192) return;
-  int64_t want = force > 1 ? force : (2560 + groups - 1) / groups;
+  if (dstate > 2 * NS || groups <= 0 || groups > 192 || nchunks < 6) return;
+  const int64_t want = (2560 + groups - 1) / groups;
   int sc = (int)((nchunks + want - 1) / want);
   if (sc < 2) sc = 2;
   const int S = (nchunks + sc - 1) / sc;

@@ -1,6 +1,6 @@
 """The weight gradients of the two widest layers (enc1 / dec6 at E8, B = 16: a 128 x 256 / 256 x 128 result over 641 024 rows),
-timed per call through network/convstack.py::wgrad (GEMM + slab reduce).  With the AB library (CUM_LIB=tools/_ab/lib_ab.so),
-CUM_TN_STREAM=0 runs the 128 x 128 kernel instead of gemm_tn_stream_kernel.  GPU box only.
+timed per call through network/convstack.py::wgrad (GEMM + slab reduce: gemm_tn_stream_kernel + tn_reduce_kernel).
+CUM_LIB=<another build> times that library instead (A/B on one machine).  Needs a GPU.
 
 usage: python tools/bench_tn_stream.py [bf16|f16]"""
 import json
@@ -32,4 +32,4 @@ for (M, N, K, ldz, ldx) in [(641024, 128, 256, 128, 128), (641024, 256, 128, 256
     by = 2 * (M * N + (M * ldx if ldx < K else M * K))
     print(json.dumps({"M": M, "N": N, "K": K, "ldx": ldx, "us": round(us, 1), "GBps": round(by / us * 1e-3, 0),
                       "hbm_frac": round(by / us * 1e-3 / 8000, 3), "TFLOPs": round(2 * M * N * K / us * 1e-6, 1),
-                      "stream": os.environ.get("CUM_TN_STREAM", "1"), "lib": os.environ.get("CUM_LIB", "default")}))
+                      "lib": os.environ.get("CUM_LIB", "default")}))

@@ -1,4 +1,4 @@
-"""cum_gemm_nt against torch.matmul on a few shapes (GPU box); CUM_NT_TILE pins the tile variant."""
+"""cum_gemm_nt against torch.matmul on a few shapes (needs a GPU)."""
 import sys
 import torch
 sys.path.insert(0, ".")

@@ -1,4 +1,4 @@
-// Diagnostic (not part of the library): the memory access pattern of the GLU-backward epilogue of gemm_nt8_kernel in
+// Diagnostic (not part of the library): the memory access pattern of the GLU-backward epilogue of the 256 x 256 NT GEMM in
 // isolation -- one 512-thread workgroup per CU (128 KB of LDS claimed), every wave reading three M x N bf16 tensors and
 // writing one M x 2N tensor for a 256 x 256 tile at a time, no MFMA work.
 //   variant A: the MFMA result layout (8 bytes per lane: 16 rows x 32 bytes per instruction), as the kernel does it

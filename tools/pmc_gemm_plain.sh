@@ -1,17 +1,19 @@
 #!/bin/bash
-# SQ counters of the 256x256 NT GEMM on a plain 8192^3 problem, gemm_nt8_kernel (CUM_NT9=0) vs gemm_nt9_kernel (CUM_NT9=1)
-cd /tmp && export TMPDIR=/tmp PYTHONPATH=$GRAFT_REPO_ROOT
-OUT=$GRAFT_REPO_ROOT/gpurun_out
-cp $GRAFT_REPO_ROOT/tools/gemm_plain.py /tmp/gemm_plain.py
-for v in 0 1; do
-  export CUM_NT9=$v
-  i=0
-  for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \
-             "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM" \
-             "GRBM_GUI_ACTIVE"; do
-    i=$((i+1))
-    (cd $GRAFT_REPO_ROOT && rocprofv3 --pmc $set --kernel-trace --output-format csv -d /tmp/pmc_gp_${v}_$i -- python3 /tmp/gemm_plain.py > $OUT/pmc_gp.log 2>&1)
-    python3 - /tmp/pmc_gp_${v}_$i $v <<'PY' >> $OUT/pmc_gemm_plain.txt
+# SQ counters of the 256x256 NT GEMM (gemm_nt9_kernel) on a plain 8192^3 problem, one rocprofv3 pass per counter set;
+# CUM_LIB selects the library build.  Prints the table; traces go to a temporary folder that is removed afterwards.
+#   bash tools/pmc_gemm_plain.sh
+root=$(cd "$(dirname "$0")/.." && pwd)
+work=$(mktemp -d)
+trap 'rm -rf "$work"' EXIT
+cd "$root"
+i=0
+for set in "SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" \
+           "SQ_VALU_MFMA_BUSY_CYCLES SQ_INSTS_MFMA SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INST_CYCLES_VMEM" \
+           "GRBM_GUI_ACTIVE"; do
+  i=$((i+1))
+  rocprofv3 --pmc $set --kernel-trace --output-format csv -d "$work/pass_$i" -- python3 tools/gemm_plain.py > "$work/pass_$i.log" 2>&1 \
+    || { tail -20 "$work/pass_$i.log"; exit 1; }
+  python3 - "$work/pass_$i" "${CUM_LIB:-default}" <<'PY'
 import csv, glob, sys, collections
 acc = collections.defaultdict(float); cnt = collections.Counter(); dur = []
 for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
@@ -21,9 +23,7 @@ for f in glob.glob(sys.argv[1] + "/**/*counter_collection.csv", recursive=True):
 for f in glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True):
     for r in csv.DictReader(open(f)):
         if "gemm_nt" in r["Kernel_Name"]: dur.append(int(r["End_Timestamp"]) - int(r["Start_Timestamp"]))
-print("CUM_NT9=%s  kernel us (median of %d): %.1f" % (sys.argv[2], len(dur), sorted(dur)[len(dur) // 2] / 1e3 if dur else -1))
+print("lib=%s  kernel us (median of %d): %.1f" % (sys.argv[2], len(dur), sorted(dur)[len(dur) // 2] / 1e3 if dur else -1))
 for c, v in sorted(acc.items()): print(f"   {c:30s} {v / cnt[c]:16.0f}")
 PY
-  done
 done
-cat $OUT/pmc_gemm_plain.txt

@@ -47,7 +47,7 @@ import csv, glob, json, sys
 f = glob.glob(sys.argv[1] + "/**/*kernel_trace.csv", recursive=True)[0]
 rows = [(int(r["Start_Timestamp"]), int(r["End_Timestamp"]), r["Kernel_Name"]) for r in csv.DictReader(open(f))]
 rows.sort()
-is_tn = lambda k: "gemm_tn" in k and "reduce" not in k        # gemm_tn_kernel / gemm_tn8_kernel / gemm_tn9_kernel
+is_tn = lambda k: "gemm_tn" in k and "reduce" not in k        # gemm_tn_kernel / gemm_tn9_kernel / gemm_tn_stream_kernel
 tn = [i for i, r in enumerate(rows) if is_tn(r[2])]
 n = 10 * 13          # the MFMA-bound group the roofline object is quoted on: the last 10 of the 16 shapes (enc3-enc7)
 first = tn[-n]
