@@ -50,8 +50,28 @@ struct LossTerms {
   bool live;         // re^2 + im^2 of x above the clamp (gradient flows)
 };
 
+// The rocFFT-route kernels spell the fused multiply-adds of their x / y arithmetic out and take no contraction from
+// the compiler (bin_power, packed_bin_sym): left to it, a * b - c * d rounds one product in the x copy of an expression
+// and the other in the y copy, and two EQUAL signals get magnitudes that differ in the last bit -- the loss of a signal
+// against itself must be exactly 0 and its gradient too.  (The fused kernels keep their arithmetic and see equal frames
+// when they load them: fused_load_frame.)
+__device__ __forceinline__ float bin_power(float2 s) {
+#pragma clang fp contract(off)
+  return __builtin_fmaf(s.x, s.x, s.y * s.y);
+}
+__device__ __forceinline__ float2 cmul_sym(float2 a, float2 b) {
+#pragma clang fp contract(off)
+  return make_float2(__builtin_fmaf(a.x, b.x, -(a.y * b.y)), __builtin_fmaf(a.x, b.y, a.y * b.x));
+}
+__device__ __forceinline__ float2 packed_bin_sym(float2 za, float2 zb, float2 w) {      // packed_bin of fft_lds.h
+#pragma clang fp contract(off)
+  const float2 c1 = make_float2(0.5f * (1.f + w.y), -0.5f * w.x), c2 = make_float2(0.5f * (1.f - w.y), 0.5f * w.x);
+  const float2 p = cmul_sym(c1, za), q = cmul_sym(c2, conjf2(zb));
+  return make_float2(p.x + q.x, p.y + q.y);
+}
+
 __device__ __forceinline__ LossTerms loss_terms(float2 sx, float2 sy) {
-  const float px = sx.x * sx.x + sx.y * sx.y, py = sy.x * sy.x + sy.y * sy.y;
+  const float px = bin_power(sx), py = bin_power(sy);
   LossTerms t;
   t.mx = sqrtf(fmaxf(px, kClamp));
   t.my = sqrtf(fmaxf(py, kClamp));
@@ -136,7 +156,7 @@ __global__ __launch_bounds__(256) void stft_loss_grad_kernel(const float2 *__res
                                                              float2 *__restrict__ z) {
   const int64_t r0 = (int64_t)blockIdx.x * kLossRows;
   const int nrow = (int)min((int64_t)kLossRows, rows - r0);
-  const float c_sc = g_sc[0] / (stats[2] * stats[3]);
+  const float c_sc = stats[2] > 0.f ? g_sc[0] / (stats[2] * stats[3]) : 0.f;   // 0 at |Y| = |X|, as torch's norm backward
   const float c_mag = g_mag[0] * inv_count;
   for (int r = 0; r < nrow; ++r) {
     const bool in_band = (r0 + r) % n_frames >= frame0;
@@ -175,7 +195,7 @@ __global__ __launch_bounds__(256) void stft_loss_partials_packed_kernel(const fl
     for (int k = threadIdx.x; k <= H; k += 256) {
       const int a = k == H ? 0 : k, b = k == 0 ? 0 : H - k;
       const float2 w = tw[k];
-      const LossTerms t = loss_terms(packed_bin(zx[base + a], zx[base + b], w), packed_bin(zy[base + a], zy[base + b], w));
+      const LossTerms t = loss_terms(packed_bin_sym(zx[base + a], zx[base + b], w), packed_bin_sym(zy[base + a], zy[base + b], w));
       const float d = t.my - t.mx;
       s1 += d * d;
       s2 += t.my * t.my;
@@ -216,7 +236,7 @@ __global__ __launch_bounds__(256) void stft_loss_grad_packed_kernel(const float2
                                                                     float2 *__restrict__ gz) {
   const int64_t r0 = (int64_t)blockIdx.x * kLossRows;
   const int nrow = (int)min((int64_t)kLossRows, rows - r0);
-  const float c_sc = g_sc[0] / (stats[2] * stats[3]);
+  const float c_sc = stats[2] > 0.f ? g_sc[0] / (stats[2] * stats[3]) : 0.f;   // 0 at |Y| = |X|, as torch's norm backward
   const float c_mag = g_mag[0] * inv_count;
   for (int r = 0; r < nrow; ++r) {
     const bool in_band = (r0 + r) % n_frames >= frame0;
@@ -233,8 +253,8 @@ __global__ __launch_bounds__(256) void stft_loss_grad_packed_kernel(const float2
           oj = make_float2(g0.x + gh.x, g0.x - gh.x);
         } else {
           const float2 wj = tw[j], wm = tw[H - j];
-          const float2 gj = bin_grad(packed_bin(xj, xm, wj), packed_bin(yj, ym, wj), c_sc, c_mag);
-          const float2 gm = bin_grad(packed_bin(xm, xj, wm), packed_bin(ym, yj, wm), c_sc, c_mag);
+          const float2 gj = bin_grad(packed_bin_sym(xj, xm, wj), packed_bin_sym(yj, ym, wj), c_sc, c_mag);
+          const float2 gm = bin_grad(packed_bin_sym(xm, xj, wm), packed_bin_sym(ym, yj, wm), c_sc, c_mag);
           // conj(c1_k) = ((1 + w.y) + i w.x)/2 ; c2_k = ((1 - w.y) + i w.x)/2
           const float2 c1j = make_float2(0.5f * (1.f + wj.y), 0.5f * wj.x), c2j = make_float2(0.5f * (1.f - wj.y), 0.5f * wj.x);
           const float2 c1m = make_float2(0.5f * (1.f + wm.y), 0.5f * wm.x), c2m = make_float2(0.5f * (1.f - wm.y), 0.5f * wm.x);
@@ -328,9 +348,13 @@ struct FusedStftParams {
   float *dframes;                                         // backward: [batch][n_frames][n_fft]
 };
 
-// the frame's packed samples of both signals -> buf (the window is read where it is used: win_len floats that stay in L1)
+// the frame's packed samples of both signals -> buf (the window is read where it is used: win_len floats that stay in L1).
+// Returns (wave-uniform) whether x == y on every sample the frame sees.  Such a frame has |Y| = |X| bin for bin: it adds
+// exactly 0 to ||Y| - |X||^2 and to the log-magnitude sum and gets a zero gradient.  The transform cannot be left to show
+// that: the compiler contracts a * b - c * d one way in the x half of a point and the other way in the y half, and two
+// equal signals come out of it differing in the last bit.
 template <int H>
-__device__ __forceinline__ void fused_load_frame(const FusedStftParams &p, int64_t b, int64_t f, int lane, float4 *buf) {
+__device__ __forceinline__ bool fused_load_frame(const FusedStftParams &p, int64_t b, int64_t f, int lane, float4 *buf) {
   typedef FusedFft<H> F;
   const int n_fft = 2 * H, off = (n_fft - p.win_len) / 2;
   const float *xb = p.x + b * p.x_sb, *yb = p.y + b * p.y_sb;
@@ -338,6 +362,7 @@ __device__ __forceinline__ void fused_load_frame(const FusedStftParams &p, int64
   // wave-uniform: no reflection and every pair 8-byte aligned (signals and window)
   const bool inner = s0 >= 0 && s0 + n_fft <= p.len && ((off | p.win_len) & 1) == 0 &&
                      ((((uintptr_t)(xb + s0)) | ((uintptr_t)(yb + s0)) | ((uintptr_t)p.window)) & 7) == 0;
+  bool same = true;
 #pragma unroll 2
   for (int i = 0; i < F::PER; ++i) {
     const int m = lane + 64 * i, n = 2 * m;
@@ -356,9 +381,11 @@ __device__ __forceinline__ void fused_load_frame(const FusedStftParams &p, int64
         w1 = (wi + 1 >= 0 && wi + 1 < p.win_len) ? p.window[wi + 1] : 0.f;
       }
       z = make_float4(w0 * x0, w1 * x1, w0 * y0, w1 * y1);
+      same = same && z.x == z.z && z.y == z.w;
     }
     buf[F::pad(m)] = z;
   }
+  return __all(same) != 0;
 }
 
 template <int H>
@@ -383,7 +410,8 @@ __global__ __launch_bounds__(64 * kFusedWaves) __attribute__((amdgpu_waves_per_e
   for (int fr = blockIdx.x * kFusedWaves + wave; fr < n_total; fr += nw) {
     const int b = fr / n_frames, f = fr - b * n_frames;
     if (f < p.frame0) continue;
-    fused_load_frame<H>(p, b, f, lane, buf);
+    const bool same = fused_load_frame<H>(p, b, f, lane, buf);
+    const float s1_in = s1, s3_in = s3;
     F::stage_fence();
     F::forward(buf, s_tw, lane);
     // bins in mirror pairs (j, H - j): both need exactly Z[j] and Z[H - j] -- one pair of LDS reads, two bins
@@ -406,6 +434,7 @@ __global__ __launch_bounds__(64 * kFusedWaves) __attribute__((amdgpu_waves_per_e
         }
       }
     }
+    if (same) { s1 = s1_in; s3 = s3_in; }                 // x == y over the frame: only |Y|^2 counts
     F::stage_fence();                                     // (the next frame's load overwrites what other lanes just read)
   }
   float v[3] = {s1, s2, s3};
@@ -432,22 +461,24 @@ __global__ __launch_bounds__(64 * kFusedWaves) __attribute__((amdgpu_waves_per_e
   const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6);
   fused_load_tables<H>(p, s_tw);
   float4 *buf = s_buf[wave];
-  const float c_sc = p.g_sc[0] / (p.stats[2] * p.stats[3]);
+  const float c_sc = p.stats[2] > 0.f ? p.g_sc[0] / (p.stats[2] * p.stats[3]) : 0.f;   // 0 at |Y| = |X|, as torch's norm backward
   const float c_mag = p.g_mag[0] * p.inv_count;
   const int n_fft = 2 * H, off = (n_fft - p.win_len) / 2;
   const int nw = gridDim.x * kFusedWaves, n_total = (int)p.n_total, n_frames = (int)p.n_frames;
   for (int fr = blockIdx.x * kFusedWaves + wave; fr < n_total; fr += nw) {
     const int b = fr / n_frames, f = fr - b * n_frames;
     float *dst = p.dframes + (int64_t)fr * n_fft;
-    if (f < p.frame0) {                                   // outside the band: no gradient, but cum_stft_fold reads the support
+    // outside the band, or x == y over the frame: no gradient, but cum_stft_fold reads the support
+    const bool same = f >= p.frame0 && fused_load_frame<H>(p, b, f, lane, buf);
+    if (f < p.frame0 || same) {
 #pragma unroll
       for (int i = 0; i < F::PER; ++i) {
         const int n = 2 * (lane + 64 * i);
         if (n + 1 >= off && n < off + p.win_len) *reinterpret_cast<float2 *>(dst + n) = make_float2(0.f, 0.f);
       }
+      F::stage_fence();
       continue;
     }
-    fused_load_frame<H>(p, b, f, lane, buf);
     F::stage_fence();
     F::forward(buf, s_tw, lane);
     // gradient spectrum gz over the transforms, in place: lanes own disjoint (j, H - j) pairs

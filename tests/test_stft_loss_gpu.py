@@ -6,7 +6,8 @@ reference's own module by tests/golden/loss.npz), evaluated in float64.  Toleran
 gradient of the spectral-convergence term 1e-5 rel-L2; gradient of the log-magnitude term 1e-3 rel-L2 -- it
 contains sign(log X - log Y), so every bin where the two magnitudes tie to within f32 rounding flips a +-1/(n X)
 contribution: the reference's own f32 arithmetic sits 1.6e-4..2.1e-4 from the f64 result for the same reason
-(tools/debug_stft.py prints both distances).
+(tools/debug_stft.py prints both distances).  Silence, the clamp, equal signals and odd window geometry:
+tests/test_stft_edges_gpu.py.
 """
 import pytest
 import torch
