@@ -179,6 +179,10 @@ SIGNATURES = {
     "cum_ssd_step": (c_i32, [c_i32] * 5 + [ctypes.c_float, _P, c_i64] + [_P] * 9 + [c_i64, _P]),
     "cum_optim_adam": (c_i32, [_P, _P, _P, _P, c_i64, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, ctypes.c_float,
                                _P]),
+    "cum_optim_group_tile_elems": (c_i32, []),
+    "cum_optim_max_groups": (c_i32, []),
+    "cum_optim_adam_groups": (c_i32, [_P, _P, _P, _P, c_i64, _P, ctypes.c_double, ctypes.c_double, ctypes.c_float, c_i32,
+                                      _P, c_i32, _P, _P, _P, c_i32, _P]),
     "cum_metrics_frame_count": (c_i64, [c_i64]),
     "cum_metrics_reduce_keep": (c_i64, [c_i64]),
     "cum_metrics_workspace_bytes": (c_i64, [c_i64, c_i64]),

@@ -415,9 +415,7 @@ def _compact_flat(flat, adam, keeps):
                                        hip.stream_ptr()))
     flat.replace_storage(new_data, new_grad, new_shapes)
     if adam is not None:
-        adam.exp_avg, adam.exp_avg_sq = new_m, new_v
-        adam.nparts = lib.cum_optim_sumsq_parts(numel)
-        adam.partials = torch.zeros(adam.nparts, dtype=torch.float32, device=dev)
+        adam.layout_changed(new_m, new_v)              # moments, norm partials, the group membership tables
     buckets = flat.buckets() if getattr(flat, "buckets", None) is not None else None
     if buckets is not None:
         buckets.rebuild()

@@ -11,6 +11,11 @@ second one, so that
     captured in a hipGraph (training/train_step.py).
 
 The host only writes the learning rate into the device-side state vector before each step.
+
+The reference's optimizer choice (src/training/train.py:126-154) is covered by the same three launches: ``"adam"`` is
+the default FlatAdam (one group, L2 decay), ``"adamw"`` is ``FlatAdam(groups=..., decoupled_weight_decay=True)``, whose
+update kernel (cum_optim_adam_groups) reads each group's learning rate and decay from a small device table and finds a
+float4's group through the tile / segment tables of ``group_tables`` below.
 """
 import ctypes
 import math
@@ -255,34 +260,147 @@ class FlatParams:
         return out
 
 
+def group_tables(offsets, numels, group_ids, tile_elems, align=FlatParams.ALIGN):
+    """Membership tables of cum_optim_adam_groups (csrc/optim.hip) for parameters laid out back to back at ``offsets``
+    (elements, ascending, each a multiple of ``align`` = 4, each parameter padded to a multiple of 4) with ``numels``
+    elements and the group ``group_ids[i]`` each.  A pure function of its arguments (CPU int32 tensors out):
+
+      tile_group[t]  for tile t = float4 [t * T, (t + 1) * T), T = tile_elems / 4: the group if one segment covers the
+                     whole tile, else -(s) - 1 with s the first segment that reaches into it
+      seg_end[s], seg_group[s]  runs of neighbouring parameters of one group: exclusive end in float4 units, group
+
+    O(tiles + segments) memory; a parameter's padding belongs to the parameter's group."""
+    if tile_elems <= 0 or tile_elems % 4 or align != 4:
+        raise ValueError("group_tables: the tile must be a positive multiple of 4 elements")
+    if not (len(offsets) == len(numels) == len(group_ids)) or not len(offsets):
+        raise ValueError("group_tables: offsets, numels and group_ids must have one entry per parameter")
+    tile4 = tile_elems // 4
+    seg_end, seg_group, at = [], [], 0
+    for off, n, k in zip(offsets, numels, group_ids):
+        if off != at or n < 0 or k < 0:
+            raise ValueError("group_tables: parameters must follow each other without gaps, 4-element aligned")
+        at = off + (n + 3) // 4 * 4
+        if at == off:
+            continue                                     # an empty parameter owns no float4
+        if seg_group and seg_group[-1] == k:
+            seg_end[-1] = at // 4
+        else:
+            seg_end.append(at // 4)
+            seg_group.append(int(k))
+    if not seg_end:
+        raise ValueError("group_tables: no elements")
+    total4 = seg_end[-1]
+    if total4 >= 2 ** 31:
+        raise ValueError("group_tables: more than 2^33 elements")
+    ends = torch.tensor(seg_end, dtype=torch.int64)
+    first4 = torch.arange(0, total4, tile4, dtype=torch.int64)             # first float4 of every tile
+    last4 = torch.clamp(first4 + tile4, max=total4) - 1                     # its last one
+    s_first = torch.searchsorted(ends, first4, right=True)                  # first segment with end > float4
+    s_last = torch.searchsorted(ends, last4, right=True)
+    groups = torch.tensor(seg_group, dtype=torch.int64)
+    tile_group = torch.where(s_first == s_last, groups[s_first], -s_first - 1)
+    return tile_group.to(torch.int32), ends.to(torch.int32), groups.to(torch.int32)
+
+
 class FlatAdam:
     """Adam with gradient-norm clipping and (optionally) dynamic loss scaling on a FlatParams.
 
     Arithmetic of ``torch.optim.Adam`` (no amsgrad; weight decay in the L2 form), ``clip_grad_norm_`` and
     ``torch.amp.GradScaler`` (init_scale 65536, growth 2 every 2000 clean steps, backoff 0.5; a step whose
     gradients hold inf / nan is skipped).  ``param_groups`` has one group so that the LR schedulers written
-    for torch optimizers (``group["lr"] = ...``) drive it unchanged."""
+    for torch optimizers (``group["lr"] = ...``) drive it unchanged.
+
+    groups: parameter groups in torch's form, ``[{"params": [...], "weight_decay": ..., "lr": ...}, ...]``; missing keys
+      take the constructor's values.  Every parameter of ``flat`` belongs to exactly one group; betas and eps are shared
+      (one pair of bias corrections).  ``param_groups`` then has one dict per group, and the update is ONE launch of
+      cum_optim_adam_groups whatever their number.  None: one group, cum_optim_adam, as ever.
+    decoupled_weight_decay: ``torch.optim.AdamW``'s form, ``p *= 1 - lr * weight_decay`` before the update, instead of
+      the L2 term in the gradient.  Membership follows the Parameter objects, so it survives pruning."""
 
     def __init__(self, flat, lr=1e-4, betas=(0.9, 0.999), eps=1e-8, weight_decay=0.0, max_grad_norm=0.0,
-                 loss_scaling=False, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000):
+                 loss_scaling=False, init_scale=65536.0, growth_factor=2.0, backoff_factor=0.5, growth_interval=2000,
+                 groups=None, decoupled_weight_decay=False):
         self.flat = flat
-        self.param_groups = [{"params": flat.params, "lr": lr, "betas": tuple(betas), "eps": eps,
-                              "weight_decay": weight_decay}]
+        self.decoupled = bool(decoupled_weight_decay)
+        self.grouped = groups is not None or self.decoupled
+        if groups is None:
+            self.param_groups = [{"params": flat.params, "lr": lr, "betas": tuple(betas), "eps": eps,
+                                  "weight_decay": weight_decay}]
+        else:
+            self.param_groups = self._checked_groups(flat, groups, lr, tuple(betas), eps, weight_decay)
         self.max_grad_norm = float(max_grad_norm or 0.0)
         self.loss_scaling = bool(loss_scaling)
         self.growth, self.backoff, self.growth_interval = growth_factor, backoff_factor, int(growth_interval)
         dev = flat.data.device
         lib = hip.lib()
+        if self.grouped and len(self.param_groups) > lib.cum_optim_max_groups():
+            raise ValueError(f"FlatAdam: {len(self.param_groups)} parameter groups; the update kernel takes at most "
+                             f"{lib.cum_optim_max_groups()}")
         self.exp_avg = torch.zeros_like(flat.data)
         self.exp_avg_sq = torch.zeros_like(flat.data)
         self.state_vec = torch.zeros(lib.cum_optim_state_elems(), dtype=torch.float32, device=dev)
         self.state_vec[ST_SCALE] = init_scale if loss_scaling else 1.0
         self.state_vec[ST_LR] = lr
-        self.nparts = lib.cum_optim_sumsq_parts(flat.numel)
-        self.partials = torch.zeros(self.nparts, dtype=torch.float32, device=dev)
         self._lr_written = lr
         self._listeners = []
+        if self.grouped:
+            # {lr, weight_decay, 1 - lr * weight_decay, unused} per group, at a fixed address: a captured step reads
+            # the values of the replay (write_lr), as it reads state_vec[ST_LR] with one group
+            self.group_hyper = torch.zeros(len(self.param_groups), 4, dtype=torch.float32, device=dev)
+            self._hyper_written = None
+        self.layout_changed()
         flat.optimizer = weakref.ref(self)
+
+    @staticmethod
+    def _checked_groups(flat, groups, lr, betas, eps, weight_decay):
+        """torch-style group dicts with the constructor's defaults filled in; every parameter of ``flat`` exactly once."""
+        def name(p):
+            i = flat.index.get(id(p))
+            return f"parameter {tuple(p.shape)}" + (f" (flat index {i})" if i is not None else "")
+        out, seen = [], set()
+        if not groups:
+            raise ValueError("FlatAdam: groups is empty")
+        for gi, g in enumerate(groups):
+            if not isinstance(g, dict) or "params" not in g:
+                raise ValueError(f"FlatAdam: group {gi} is not a dict with a 'params' list")
+            unknown = set(g) - {"params", "lr", "betas", "eps", "weight_decay"}
+            if unknown:
+                raise ValueError(f"FlatAdam: group {gi}: unsupported keys {sorted(unknown)}")
+            if tuple(g.get("betas", betas)) != betas or g.get("eps", eps) != eps:
+                raise ValueError(f"FlatAdam: group {gi}: betas and eps are shared by all groups (one pair of bias "
+                                 "corrections per step)")
+            params = list(g["params"])
+            for p in params:
+                if id(p) not in flat.index:
+                    raise ValueError(f"FlatAdam: group {gi}: {name(p)} is not a parameter of the FlatParams")
+                if id(p) in seen:
+                    raise ValueError(f"FlatAdam: group {gi}: {name(p)} is in more than one group")
+                seen.add(id(p))
+            out.append({"params": params, "lr": g.get("lr", lr), "betas": betas, "eps": eps,
+                        "weight_decay": g.get("weight_decay", weight_decay)})
+        for p in flat.params:
+            if id(p) not in seen:
+                raise ValueError(f"FlatAdam: {name(p)} is in no group")
+        return out
+
+    def layout_changed(self, exp_avg=None, exp_avg_sq=None):
+        """Everything that follows the flat layout: the partial-sum buffer of the norm and, with groups, the membership
+        tables of the update kernel.  Pruning (pruning/device.py) passes the moment buffers of the new layout."""
+        f, lib = self.flat, hip.lib()
+        dev = f.data.device
+        if exp_avg is not None:
+            self.exp_avg, self.exp_avg_sq = exp_avg, exp_avg_sq
+        self.nparts = lib.cum_optim_sumsq_parts(f.numel)
+        self.partials = torch.zeros(self.nparts, dtype=torch.float32, device=dev)
+        if self.grouped:
+            self.tile_group, self.seg_end, self.seg_group = (t.to(dev) for t in self.membership())
+
+    def membership(self):
+        """group_tables of the current layout (CPU tensors)."""
+        gid = {id(p): k for k, g in enumerate(self.param_groups) for p in g["params"]}
+        f = self.flat
+        return group_tables(f.offsets, [p.numel() for p in f.params], [gid[id(p)] for p in f.params],
+                            hip.lib().cum_optim_group_tile_elems())
 
     # ---- loss scaling (device scalars: no host sync)
     def scale_loss(self, loss):
@@ -307,10 +425,29 @@ class FlatAdam:
         self.flat.zero_grad()
 
     def write_lr(self):
-        """Push the host-side learning rate to the device (one fill kernel; call outside a captured graph)."""
-        lr = float(self.param_groups[0]["lr"])
-        self.state_vec[ST_LR:ST_LR + 1].fill_(lr)
-        self._lr_written = lr
+        """Push the host-side learning rate to the device (one fill kernel; call outside a captured graph).  With groups:
+        every group's lr, weight decay and 1 - lr * weight_decay (formed in double here, rounded once) go to the device
+        table -- fill kernels for the columns that changed, one per column while the groups agree; no synchronisation."""
+        if not self.grouped:
+            lr = float(self.param_groups[0]["lr"])
+            self.state_vec[ST_LR:ST_LR + 1].fill_(lr)
+            self._lr_written = lr
+            return
+        rows = [(float(g["lr"]), float(g["weight_decay"]), 1.0 - float(g["lr"]) * float(g["weight_decay"]))
+                for g in self.param_groups]
+        old = self._hyper_written
+        for c in range(3):
+            col = [r[c] for r in rows]
+            if old is not None and col == [r[c] for r in old]:
+                continue
+            if all(x == col[0] for x in col):
+                self.group_hyper[:, c].fill_(col[0])
+            else:
+                for k, x in enumerate(col):
+                    if old is None or old[k][c] != x:
+                        self.group_hyper[k, c:c + 1].fill_(x)
+        self._hyper_written = rows
+        self._lr_written = rows[0][0]
 
     def step(self, write_lr=True):
         """unscale + clip + Adam + scale update; three launches on the current stream."""
@@ -326,33 +463,66 @@ class FlatAdam:
             hip.check(lib.cum_optim_prepare(hip.ptr(self.state_vec), hip.ptr(self.partials), self.nparts,
                                             self.max_grad_norm, g["betas"][0], g["betas"][1], int(self.loss_scaling),
                                             self.growth, self.backoff, self.growth_interval, st))
-            hip.check(lib.cum_optim_adam(hip.ptr(f.data), hip.ptr(f.grad), hip.ptr(self.exp_avg),
-                                         hip.ptr(self.exp_avg_sq), f.numel, hip.ptr(self.state_vec), g["betas"][0],
-                                         g["betas"][1], g["eps"], g["weight_decay"], st))
+            if self.grouped:
+                hip.check(lib.cum_optim_adam_groups(hip.ptr(f.data), hip.ptr(f.grad), hip.ptr(self.exp_avg),
+                                                    hip.ptr(self.exp_avg_sq), f.numel, hip.ptr(self.state_vec),
+                                                    g["betas"][0], g["betas"][1], g["eps"], int(self.decoupled),
+                                                    hip.ptr(self.group_hyper), len(self.param_groups),
+                                                    hip.ptr(self.tile_group), hip.ptr(self.seg_end),
+                                                    hip.ptr(self.seg_group), self.seg_end.numel(), st))
+            else:
+                hip.check(lib.cum_optim_adam(hip.ptr(f.data), hip.ptr(f.grad), hip.ptr(self.exp_avg),
+                                             hip.ptr(self.exp_avg_sq), f.numel, hip.ptr(self.state_vec), g["betas"][0],
+                                             g["betas"][1], g["eps"], g["weight_decay"], st))
         f.bump_versions()
         self.grads_scale_slot = ST_GRAD_SCALE
 
     # ---- checkpoint format of torch.optim.Adam (src/training/train.py:183-186, 367: optimizer_state_dict)
+    def _numbering(self):
+        """{id(param): index in the checkpoint}.  One group: registration order, as torch numbers ``net.parameters()``.
+        Groups: through the groups in order, as torch numbers the parameters of a list of group dicts."""
+        if not self.grouped:
+            return {id(p): i for i, p in enumerate(reversed(self.flat.params))}
+        return {id(p): i for i, p in enumerate(p for g in self.param_groups for p in g["params"])}
+
     def state_dict(self):
         f = self.flat
-        order = {id(p): i for i, p in enumerate(reversed(f.params))}       # registration order, as torch numbers them
+        order = self._numbering()
         step = self.state_vec[ST_STEP].detach().clone()
         state = {}
         for p, o in zip(f.params, f.offsets):
             n = p.numel()
             state[order[id(p)]] = {"step": step.clone(), "exp_avg": self.exp_avg[o:o + n].view_as(p).clone(),
                                    "exp_avg_sq": self.exp_avg_sq[o:o + n].view_as(p).clone()}
-        g = dict(self.param_groups[0])
-        g["params"] = list(range(len(f.params)))
-        return {"state": state, "param_groups": [g], "flat_state": self.state_vec.detach().clone(),
+        groups = []
+        for g in self.param_groups:
+            d = dict(g)
+            d["params"] = [order[id(p)] for p in g["params"]] if self.grouped else list(range(len(f.params)))
+            groups.append(d)
+        if self.grouped:
+            state = {k: state[k] for k in sorted(state)}
+        return {"state": state, "param_groups": groups, "flat_state": self.state_vec.detach().clone(),
                 "loss_scaling": bool(self.loss_scaling)}
 
     def load_state_dict(self, sd):
         """Moments and the step count come from the checkpoint; the loss scale and its growth tracker only when both the
         checkpoint and this optimizer use loss scaling (a bf16 / f32 run saved scale 1.0: loaded into an fp16 run it
-        would underflow the gradients for thousands of steps); the learning rate is the scheduler's to write."""
+        would underflow the gradients for thousands of steps); the learning rate is the scheduler's to write.  The
+        checkpoint must have this optimizer's groups (their number and sizes): the parameter numbering depends on them."""
         f = self.flat
-        order = {id(p): i for i, p in enumerate(reversed(f.params))}
+        saved_groups = sd["param_groups"]
+        if len(saved_groups) != len(self.param_groups):
+            raise ValueError(f"FlatAdam.load_state_dict: the checkpoint has {len(saved_groups)} parameter group(s), this "
+                             f"optimizer {len(self.param_groups)}")
+        if self.grouped:
+            b0, e0 = saved_groups[0].get("betas"), saved_groups[0].get("eps")
+            for k, (mine, theirs) in enumerate(zip(self.param_groups, saved_groups)):
+                if len(theirs.get("params", mine["params"])) != len(mine["params"]):
+                    raise ValueError(f"FlatAdam.load_state_dict: group {k} of the checkpoint has "
+                                     f"{len(theirs['params'])} parameters, this optimizer's {len(mine['params'])}")
+                if (b0 is not None and tuple(theirs.get("betas", b0)) != tuple(b0)) or theirs.get("eps", e0) != e0:
+                    raise ValueError("FlatAdam.load_state_dict: betas and eps differ between the checkpoint's groups")
+        order = self._numbering()
         step = None
         with torch.no_grad():
             for p, o in zip(f.params, f.offsets):
@@ -379,9 +549,13 @@ class FlatAdam:
                     self.state_vec[ST_TRACKER] = float(saved[ST_TRACKER])
             if step is not None:
                 self.state_vec[ST_STEP] = step
-        for k in ("lr", "betas", "eps", "weight_decay"):
-            if k in sd["param_groups"][0]:
-                self.param_groups[0][k] = sd["param_groups"][0][k]
+        for mine, theirs in zip(self.param_groups, saved_groups):
+            for k in ("lr", "weight_decay"):
+                if k in theirs:
+                    mine[k] = theirs[k]
+            for k in ("betas", "eps"):                            # shared: the first group's
+                if k in saved_groups[0]:
+                    mine[k] = tuple(saved_groups[0][k]) if k == "betas" else saved_groups[0][k]
         t = float(step or 0.0)
         b1, b2 = self.param_groups[0]["betas"]
         if t > 0:

@@ -28,7 +28,7 @@ from ..util.stft_loss import MultiResolutionSTFTLoss
 from .flat_optim import ST_GRAD_SCALE
 from ..util.util import LinearWarmupCosineDecay, loss_fn
 
-DEFAULT_OPTIM = {"n_iters": 1600000, "learning_rate": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8,
+DEFAULT_OPTIM = {"optimizer": "adam", "n_iters": 1600000, "learning_rate": 1e-4, "betas": (0.9, 0.999), "eps": 1e-8,
                  "clip_grad_norm_max": 10, "weight_decay": 0, "fused_adam": True}
 DEFAULT_LOSS = {"ell_p": 1, "ell_p_lambda": 1, "stft_lambda": 1,
                 "stft_config": {"sc_lambda": 0.5, "mag_lambda": 0.5, "band": "full",
@@ -37,13 +37,26 @@ DEFAULT_LOSS = {"ell_p": 1, "ell_p_lambda": 1, "stft_lambda": 1,
 GRAPH_WARMUP_STEPS = 3       # eager steps before the capture (lazy initialisation, allocator warm-up)
 
 
+def decay_groups(net, weight_decay):
+    """The reference's two AdamW parameter groups (src/training/train.py:126-138), over the parameters that require grad
+    in ``named_parameters`` order: every tensor with ``dim() >= 2`` decays, the rest (biases, norm weights, other 1-D
+    tensors) do not.  The rule is the reference's, not upstream Mamba's: it does not consult the ``_no_weight_decay``
+    marks, so ``A_log`` (2-D) decays while ``D`` and ``dt_bias`` (1-D) do not."""
+    params = [p for _, p in net.named_parameters() if p.requires_grad]
+    return [{"params": [p for p in params if p.dim() >= 2], "weight_decay": weight_decay},
+            {"params": [p for p in params if p.dim() < 2], "weight_decay": 0.0}]
+
+
 class TrainStep:
     """``step = TrainStep(net, ...); loss, grad_norm = step(clean, noisy)``.
 
     repeats: gradient-accumulation micro-steps per optimizer step (reference: ``repeats`` of
       src/training/train.py:282-300).  ``__call__`` splits the batch it is given into ``repeats`` equal micro-batches;
       ``micro_step`` / ``optimizer_step`` expose the two halves for loaders that deliver micro-batches one by one.
-    flat_optimizer: None = on for fp32 CUDA models.  Off: torch.optim.Adam + clip_grad_norm_ + GradScaler.
+    optimization["optimizer"]: "adam" (default; torch.optim.Adam, L2 weight decay on every tensor) or "adamw"
+      (torch.optim.AdamW over the two groups of ``decay_groups``: decoupled decay on the ``dim() >= 2`` tensors, none on
+      the rest), as src/training/train.py:126-154; anything else raises ValueError.  Both on either optimizer route.
+    flat_optimizer: None = on for fp32 CUDA models.  Off: torch.optim.Adam / AdamW + clip_grad_norm_ + GradScaler.
     use_graph: None = on for CUDA runs with the flat optimizer (one graph for one process; two graphs around an eager
       whole-buffer all-reduce for several ranks, see the module docstring)."""
 
@@ -60,20 +73,32 @@ class TrainStep:
         self.autocast_dtype = autocast_dtype
         fp16 = autocast_dtype == torch.float16
         self.scaler = None
+        kind = self.opt_cfg["optimizer"]
+        if kind not in ("adam", "adamw"):
+            raise ValueError("Optimizer not supported")
+        adamw = kind == "adamw"
         if flat_optimizer:
             from .flat_optim import FlatAdam
             from .train_distributed import GradBuckets
             if self.buckets is None:          # single process: flat storage only, no exchange
                 self.buckets = net.grad_buckets = GradBuckets(net)
+            grouped = {}
+            if adamw:
+                grouped = dict(groups=decay_groups(net, self.opt_cfg["weight_decay"]), decoupled_weight_decay=True)
             self.optimizer = FlatAdam(self.buckets.flat, lr=self.opt_cfg["learning_rate"],
                                       betas=tuple(self.opt_cfg["betas"]), eps=self.opt_cfg["eps"],
                                       weight_decay=self.opt_cfg["weight_decay"],
-                                      max_grad_norm=self.opt_cfg["clip_grad_norm_max"], loss_scaling=fp16)
+                                      max_grad_norm=self.opt_cfg["clip_grad_norm_max"], loss_scaling=fp16, **grouped)
         else:
             fused = bool(self.opt_cfg["fused_adam"]) and dev.type == "cuda"
-            self.optimizer = torch.optim.Adam(net.parameters(), lr=self.opt_cfg["learning_rate"],
-                                              betas=tuple(self.opt_cfg["betas"]), eps=self.opt_cfg["eps"],
-                                              fused=fused, weight_decay=self.opt_cfg["weight_decay"])
+            if adamw:
+                self.optimizer = torch.optim.AdamW(decay_groups(net, self.opt_cfg["weight_decay"]),
+                                                   lr=self.opt_cfg["learning_rate"], betas=tuple(self.opt_cfg["betas"]),
+                                                   eps=self.opt_cfg["eps"], fused=fused)
+            else:
+                self.optimizer = torch.optim.Adam(net.parameters(), lr=self.opt_cfg["learning_rate"],
+                                                  betas=tuple(self.opt_cfg["betas"]), eps=self.opt_cfg["eps"],
+                                                  fused=fused, weight_decay=self.opt_cfg["weight_decay"])
             # fp16 autocast needs loss scaling (reference: GradScaler, train.py:158-160); bf16 does not
             self.scaler = torch.amp.GradScaler("cuda") if fp16 else None
         self.flat = flat_optimizer

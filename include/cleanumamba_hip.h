@@ -634,6 +634,28 @@ int cum_optim_adam(float *p, const float *g, float *m, float *v, int64_t n, cons
                    double beta2, float eps, float weight_decay, void *stream);   /* betas as double: 1 - beta must not
                                                                                     be formed in f32 (0.999f: 5e-5 off) */
 
+/* cum_optim_adam_groups: the update of cum_optim_adam with torch's parameter groups, in the same one launch -- what the
+ * reference's optimizer choice needs (src/training/train.py:126-154: "adam" = torch.optim.Adam, L2 decay on every
+ * tensor; "adamw" = torch.optim.AdamW over two groups, decoupled decay on the dim() >= 2 tensors and none on the rest).
+ * Takes the third place of the sequence above; state, betas and eps as there (shared by all groups).
+ *   decoupled    0: g += weight_decay_k * p (torch.optim.Adam; one group gives the bits of cum_optim_adam)
+ *                1: p *= 1 - lr_k * weight_decay_k before the update (torch.optim.AdamW)
+ *   group_hyper  device, 16-byte aligned, 4 f32 per group: {lr, weight_decay, 1 - lr * weight_decay rounded once from
+ *                double, unused}.  state[8] is not read.  ngroups in [1, cum_optim_max_groups()].
+ *   membership   per float4 of the flat buffers (every parameter starts on a 4-element boundary), in tiles of
+ *                cum_optim_group_tile_elems() elements, T = max(1, ceil(ceil(n / 4) / (tile / 4))) of them:
+ *                tile_group[T] (device i32): >= 0: the whole tile belongs to that group; < 0: -(value) - 1 is the first
+ *                entry of the segment list that reaches into the tile.  seg_end[nseg] / seg_group[nseg] (device i32):
+ *                segments in ascending order, exclusive end in float4 units and group; the last ends at ceil(n / 4).
+ * With found inf/nan the launch changes nothing, the decay included.  Zero padding (p = g = m = v = 0) stays zero.
+ * Null or misaligned pointers, n < 0 and ngroups outside its range are rejected (CUM_EINVAL) before any launch. */
+int32_t cum_optim_group_tile_elems(void);
+int32_t cum_optim_max_groups(void);
+int cum_optim_adam_groups(float *p, const float *g, float *m, float *v, int64_t n, const float *state, double beta1,
+                          double beta2, float eps, int32_t decoupled, const float *group_hyper, int32_t ngroups,
+                          const int32_t *tile_group, const int32_t *seg_end, const int32_t *seg_group, int32_t nseg,
+                          void *stream);
+
 /* ---- Mamba2 bottleneck (mamba_v2=True; csrc/ssd.hip).  ngroups 1, headdim and dstate in {16, 32, 64}, any len, any
  * batch.  Per head h: dt_t = softplus(dt_raw_t + dt_bias_h), A_h = -exp(A_log_h),
  *   state_t = exp(dt_t A_h) state_{t-1} + dt_t x_t B_t^T   (headdim x dstate),   y_t = state_t C_t + D_h x_t.
