@@ -198,6 +198,7 @@ SIGNATURES = {
     "cum_prune_mask_save_elems": (c_i64, [ctypes.POINTER(PruneMaskDesc), c_i32]),
     "cum_prune_mask_workspace_bytes": (c_i64, [c_i32, c_i64]),
     "cum_prune_mask": (c_i32, [ctypes.POINTER(PruneMaskDesc), c_i32, _P, c_i64, _P, c_i64, c_i32, _P, c_i64, _P]),
+    "cum_pcm_batch_f32": (c_i32, [_P, c_i64, _P, c_i32, c_i64, _P, c_i64, _P, c_i64, _P]),
 }
 
 _lib = None

@@ -1,0 +1,407 @@
+"""Batches for the train step straight from a dataset directory: the other half of the reference's hot loop
+(src/training/train.py:255-260 -- ``for clean_audio, noisy_audio, _, _ in trainloader: clean_audio = clean_audio.cuda()``).
+
+The reference's loader decodes both files of a pair to float on the CPU, crops, collates, and the loop uploads two float
+batches from pageable memory on the compute stream.  Here the samples stay int16 until they are on the device:
+
+  worker threads   dataset.read_pcm(index, start, count) straight into a pinned staging slot (the only time the host
+                   touches a sample);
+  next()           one ``copy_(non_blocking=True)`` of the slot -- the int16 rows of both signals and the table of clip
+                   lengths -- on the feeder's own stream, followed by an event.  The upload of batch k + 1 is issued
+                   while batch k is handed out, into one of depth + 1 device blocks, so it runs beside the steps
+                   before the one that uses it;
+  PcmBatch.into()  the current stream waits for that event (the host does not), and one launch of cum_pcm_batch_f32
+                   (csrc/pcm.hip) scales to float and tiles short clips into the tensors it is given -- for a replayed
+                   TrainStep these are the captured graph's own input buffers, so no float batch is ever copied.
+
+One scheduler owns all randomness: the order and the crop starts of epoch e come from
+``numpy.random.Generator(PCG64([seed, e]))`` and do not depend on the number of workers, on timing, or on the rank count
+beyond the documented sharding, so a run can be repeated and resumed.
+
+Every call into the GPU runtime is made on the consumer's thread (inside ``next()`` / ``into()``); the workers only read
+files.  A worker can therefore never disturb a hipGraph capture that the consumer's thread has open, and the consumer
+never calls ``next()`` while it captures.
+
+``device="cpu"`` keeps the same pipeline without pinning or streams and does the kernel's arithmetic with torch on the
+host, so the loop runs anywhere.
+"""
+import ctypes
+import inspect
+import threading
+import time
+
+import numpy as np
+import torch
+
+from .. import hip
+
+SAMPLE_RATE = 16000
+PCM_SCALE = 1.0 / 32768.0
+
+
+def _round_up(n, m):
+    return (n + m - 1) // m * m
+
+
+class _Slot:
+    """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths, as one int16 tensor so
+    that it moves in one copy."""
+
+    def __init__(self, batch, pitch, device, pin):
+        self.batch, self.pitch = batch, pitch
+        self.flat = torch.zeros(2 * batch * pitch + 2 * batch, dtype=torch.int16, device=device, pin_memory=pin)
+        self.seq = -1                # the batch this block holds
+        self.uploaded = None         # event after the upload (device blocks on a GPU)
+        self.released = []           # events after the assembling kernels that read this block
+
+    def rows(self, nb):
+        """(2, nb, pitch) int16 view: [0] the clean rows, [1] the noisy rows of a batch of nb clips."""
+        return self.flat[:2 * nb * self.pitch].view(2, nb, self.pitch)
+
+    def src_len(self):
+        return self.flat[2 * self.batch * self.pitch:].view(torch.int32)
+
+
+class _Pending:
+    """A batch on its way through the staging slots."""
+
+    def __init__(self, seq, epoch, entries):
+        self.seq, self.epoch, self.entries = seq, epoch, entries
+        self.todo = len(entries)     # rows not read yet
+        self.error = None
+
+
+class PcmBatch:
+    """What ``BatchFeeder.next()`` returns: the int16 crops of one batch on the feeder's device.
+
+    fileids: [(clean path, noisy path)] per clip;  entries: the plan's (index, start, count) per clip;  epoch;
+    shape: the (B, 1, L) of the float tensors it assembles."""
+
+    def __init__(self, feeder, seq, epoch, entries, slot):
+        self._feeder, self._seq, self._slot = feeder, seq, slot
+        self.epoch, self.entries = epoch, entries
+        files = getattr(feeder.dataset, "files", None)
+        self.fileids = [tuple(files[i]) if files is not None else i for i, _, _ in entries]
+        self.device = feeder.device
+        self.shape = torch.Size((len(entries), 1, feeder.crop_length))
+        self.uploaded = slot.uploaded        # the event after this batch's upload (None on the CPU)
+
+    def _live_slot(self):
+        slot = self._slot
+        if self._feeder._returned > self._seq + self._feeder.depth or slot.seq != self._seq:
+            raise RuntimeError(f"PcmBatch {self._seq} was used after {self._feeder.depth} further next() calls: its "
+                               "device slot holds another batch now (raise `depth` to keep batches longer)")
+        return slot
+
+    def into(self, clean, noisy):
+        """Assemble the float batch into ``clean`` and ``noisy`` ((B, 1, L) or (B, L) float32 on the feeder's device,
+        unit stride along time, 16-byte aligned) on the current stream.  Nothing here waits on the host."""
+        slot = self._live_slot()
+        nb, length = self.shape[0], self.shape[2]
+        strides = []
+        for name, t in (("clean", clean), ("noisy", noisy)):
+            if t.dtype != torch.float32 or t.device != self.device or tuple(t.shape) not in ((nb, 1, length), (nb, length)):
+                raise ValueError(f"PcmBatch.into: {name} must be a float32 {tuple(self.shape)} tensor on {self.device}; "
+                                 f"got {t.dtype} {tuple(t.shape)} on {t.device}")
+            if t.stride(-1) != 1 and length > 1:
+                raise ValueError(f"PcmBatch.into: {name} must have unit stride along time")
+            strides.append(t.stride(0) if nb > 1 else length)
+        if self.device.type == "cpu":
+            rows, n = slot.rows(nb), slot.src_len()[:nb].to(torch.int64).clamp(1, length)
+            idx = torch.arange(length)[None, :] % n[:, None]
+            for t, sb, src in ((clean, strides[0], rows[0]), (noisy, strides[1], rows[1])):
+                out = torch.as_strided(t, (nb, length), (sb, 1))
+                out.copy_(torch.gather(src, 1, idx).to(torch.float32) * PCM_SCALE)
+            return clean, noisy
+        with torch.cuda.device(self.device):
+            stream = torch.cuda.current_stream()
+            stream.wait_event(slot.uploaded)
+            hip.check(hip.lib().cum_pcm_batch_f32(hip.ptr(slot.flat), slot.pitch, hip.ptr(slot.src_len()), nb, length,
+                                                  hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
+                                                  ctypes.c_void_p(stream.cuda_stream)))
+            done = torch.cuda.Event()
+            done.record(stream)
+            slot.released.append(done)       # the next upload into this block waits for it (on the device)
+        return clean, noisy
+
+    def tensors(self):
+        """(clean, noisy): two fresh (B, 1, L) float32 tensors, assembled by ``into``."""
+        self._live_slot()
+        clean = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        noisy = torch.empty(self.shape, dtype=torch.float32, device=self.device)
+        return self.into(clean, noisy)
+
+
+class BatchFeeder:
+    """``for batch in BatchFeeder(dataset, 16, "cuda:0"): loss, gn = step(batch)`` -- one pass of the loop is one epoch,
+    the next ``for`` continues with the next epoch; the workers prefetch across the boundary.
+
+    dataset: anything with ``__len__``, ``pair_length(n)``, ``read_pcm(n, start, count)`` and (for the batch's
+      ``fileids``) ``files``: util/dataset.CleanNoisyPairDataset.
+    crop_length: samples per clip of the batch; default ``int(dataset.crop_length_sec * 16000)``.  A longer clip gives a
+      random window, a shorter one is uploaded whole and repeated on the device.
+    depth: staging slots, and the number of further ``next()`` calls a batch stays usable for.
+    workers: reader threads (at most; never more than the rows in flight).  Reading is I/O and memcpy, which release the
+      interpreter lock; a handful saturates the page cache, and the count is deliberately not taken from the machine's
+      CPU count.
+    rank / world: this process takes ``perm[rank::world]`` of every epoch's permutation, truncated to the common count.
+    timeout_s: the longest ``next()`` waits for the readers or an upload before it raises TimeoutError."""
+
+    def __init__(self, dataset, batch_size, device, crop_length=None, shuffle=True, seed=0, drop_last=True, depth=2,
+                 workers=4, rank=0, world=1, timeout_s=60):
+        self.dataset = dataset
+        self.batch_size = int(batch_size)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if crop_length is None:
+            crop_length = int(getattr(dataset, "crop_length_sec", 0) * SAMPLE_RATE)
+        self.crop_length = int(crop_length)
+        self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
+        self.depth, self.workers = int(depth), int(workers)
+        self.rank, self.world = int(rank), int(world)
+        self.timeout_s = float(timeout_s)
+        if self.batch_size < 1 or self.crop_length < 1 or self.depth < 1 or self.workers < 1:
+            raise ValueError("BatchFeeder: batch_size, crop_length, depth and workers must be at least 1")
+        if not 0 <= self.rank < self.world:
+            raise ValueError(f"BatchFeeder: rank {self.rank} outside world {self.world}")
+        self.per_rank = len(dataset) // self.world
+        if len(self) < 1:
+            raise ValueError(f"BatchFeeder: {len(dataset)} pairs over {self.world} rank(s) give no batch of "
+                             f"{self.batch_size}")
+        self._read_into = "out" in inspect.signature(dataset.read_pcm).parameters
+
+        self.pitch = _round_up(self.crop_length, 8)
+        gpu = self.device.type == "cuda"
+        if gpu:
+            hip.lib()                                   # a missing library is an error now, not at the first batch
+        self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu) for _ in range(self.depth)]
+        self._stage_np = [s.flat.numpy() for s in self._stage]
+        # one device block more than staging slots: batch k + 1 is uploaded while k and the depth - 1 before it are live
+        self._dev = [_Slot(self.batch_size, self.pitch, self.device, False) for _ in range(self.depth + 1)]
+        self._stream = torch.cuda.Stream(self.device) if gpu else None
+
+        self._cv = threading.Condition()
+        self._closed = False
+        self._failure = None           # an error outside any one batch (the plan)
+        self._cursor = (0, 0, 0)       # next row to hand to a worker: (epoch, batch within the epoch, row)
+        self._plan_cache = {}
+        self._pending = {}             # seq -> _Pending, from the first row handed out until next() returns the batch
+        self._next_seq = 0             # seq of the batch the cursor is in
+        self._returned = 0             # batches next() has handed out
+        self._uploaded = 0             # batches whose upload has been issued
+        self._epoch_left = len(self)   # batches left in the epoch the consumer is in
+        self.epoch = 0                 # the epoch the next batch belongs to
+        self.wait_read_s = self.wait_upload_s = 0.0       # what next() spent waiting for the readers / for an upload
+        self.uploads_late = 0          # uploads issued by the next() that returns the batch, not one call ahead
+        self._threads = [threading.Thread(target=self._work, name=f"BatchFeeder-{i}", daemon=True)
+                         for i in range(min(self.workers, self.depth * self.batch_size))]
+        for t in self._threads:
+            t.start()
+
+    # ------------------------------------------------------------------ plan
+    def __len__(self):
+        """Batches per epoch (of this rank)."""
+        if self.drop_last:
+            return self.per_rank // self.batch_size
+        return -(-self.per_rank // self.batch_size)
+
+    def plan(self, epoch):
+        """[[(index, start, count)] per batch] of ``epoch`` for this rank: a function of (seed, epoch, rank, world, the
+        clips' lengths) alone.  The crop start of a clip is drawn for every position of the permutation, so a rank's
+        draws do not depend on the other ranks' clip lengths."""
+        n = len(self.dataset)
+        rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch)]))
+        perm = rng.permutation(n) if self.shuffle else np.arange(n)
+        u = rng.random(n)
+        entries = []
+        for pos in range(self.rank, n, self.world)[:self.per_rank]:
+            index = int(perm[pos])
+            length = int(self.dataset.pair_length(index))
+            if length < 1:
+                raise ValueError(f"pair {index} of the dataset is empty")
+            if length <= self.crop_length:
+                entries.append((index, 0, length))
+            else:
+                room = length - self.crop_length
+                entries.append((index, min(int(u[pos] * (room + 1)), room), self.crop_length))
+        return [entries[i:i + self.batch_size] for i in range(0, len(self) * self.batch_size, self.batch_size)]
+
+    # ------------------------------------------------------------------ workers
+    def _take_row(self):
+        """Under the lock: the next (pending batch, row) whose staging slot is free, or None."""
+        if self._failure is not None:
+            return None
+        epoch, b, row = self._cursor
+        if self._next_seq >= self._returned + self.depth:       # the slot still holds a batch next() has not handed out
+            return None
+        plan = self._plan_cache.get(epoch)
+        if plan is None:
+            try:
+                plan = self.plan(epoch)
+            except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
+                self._failure = exc
+                self._cv.notify_all()
+                return None
+            self._plan_cache = {epoch: plan}
+        pend = self._pending.get(self._next_seq)
+        if pend is None:
+            pend = self._pending[self._next_seq] = _Pending(self._next_seq, epoch, plan[b])
+        taken, row = row, row + 1
+        if row == len(plan[b]):
+            row, b, self._next_seq = 0, b + 1, self._next_seq + 1
+            if b == len(plan):
+                b, epoch = 0, epoch + 1
+        self._cursor = (epoch, b, row)
+        return pend, taken
+
+    def _work(self):
+        while True:
+            with self._cv:
+                while True:
+                    if self._closed:
+                        return
+                    job = self._take_row()
+                    if job is not None:
+                        break
+                    self._cv.wait(0.5)
+            pend, r = job
+            index, start, count = pend.entries[r]
+            error = None
+            try:
+                nb = len(pend.entries)
+                k = pend.seq % self.depth
+                flat = self._stage_np[k]
+                rows = flat[:2 * nb * self.pitch].reshape(2, nb, self.pitch)
+                if self._read_into:
+                    self.dataset.read_pcm(index, start, count, out=(rows[0, r], rows[1, r]))
+                else:
+                    pair = self.dataset.read_pcm(index, start, count)
+                    for dst, src in zip((rows[0, r], rows[1, r]), pair):
+                        src = np.asarray(src)
+                        if src.dtype != np.int16 or src.shape != (count,):
+                            raise ValueError(f"read_pcm returned {src.dtype} {src.shape}, not int16 ({count},)")
+                        dst[:count] = src
+                flat[2 * self.batch_size * self.pitch:].view(np.int32)[r] = count
+            except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next() with the file's name
+                files = getattr(self.dataset, "files", None)
+                name = " / ".join(files[index]) if files is not None else f"pair {index}"
+                error = RuntimeError(f"BatchFeeder: reading {name} failed: {exc!r}")
+                error.__cause__ = exc
+            with self._cv:
+                if error is not None and pend.error is None:
+                    pend.error = error
+                pend.todo -= 1
+                if pend.todo == 0 or error is not None:
+                    self._cv.notify_all()
+
+    # ------------------------------------------------------------------ consumer
+    def _upload(self, pend):
+        """Issue the upload of a fully staged batch into its device block (consumer's thread)."""
+        stage, dev = self._stage[pend.seq % self.depth], self._dev[pend.seq % (self.depth + 1)]
+        if self._stream is None:
+            dev.flat.copy_(stage.flat)
+        else:
+            # The kernels that read the block's last batch (depth + 1 batches ago) must be done.  The HOST waits for them,
+            # bounded, and the copy is then issued with no dependency: chaining the copy behind their events on the
+            # device instead (stream.wait_event) cost the replayed E8 step one upload's duration, 0.2 ms in 19.7, although
+            # every upload ended three steps before its batch was used (profiles/feeder_bench.json,
+            # feeder_bench_device_gate.json).  A loop that synchronises every step never waits here; one that never
+            # does is kept from running more than depth + 1 steps ahead of the device.
+            t0, deadline = time.monotonic(), time.monotonic() + self.timeout_s
+            for ev in dev.released:
+                while not ev.query():
+                    if time.monotonic() > deadline:
+                        raise TimeoutError(f"BatchFeeder: a device block was not released within {self.timeout_s:g} s")
+                    time.sleep(1e-3)
+            self.wait_upload_s += time.monotonic() - t0
+            with torch.cuda.stream(self._stream):
+                dev.flat.copy_(stage.flat, non_blocking=True)
+                dev.uploaded = torch.cuda.Event(enable_timing=True)      # (timed: tools/bench_feeder.py places it)
+                dev.uploaded.record(self._stream)
+        dev.released = []
+        dev.seq = pend.seq
+        self._uploaded = pend.seq + 1
+
+    def _staged(self, seq):
+        pend = self._pending.get(seq)
+        return pend if pend is not None and pend.todo == 0 and pend.error is None else None
+
+    def next(self):
+        """The next batch of the current epoch; StopIteration once at the end of an epoch, after which the next call
+        starts the following one."""
+        if self._closed:
+            raise RuntimeError("BatchFeeder is closed")
+        if self._epoch_left == 0:
+            self._epoch_left = len(self)
+            self.epoch += 1
+            raise StopIteration
+        seq, deadline = self._returned, time.monotonic() + self.timeout_s
+        t0 = time.monotonic()
+        with self._cv:
+            while True:
+                pend = self._pending.get(seq)
+                if pend is not None and pend.error is not None:
+                    raise pend.error
+                if self._failure is not None:
+                    raise RuntimeError(f"BatchFeeder: planning an epoch failed: {self._failure!r}") from self._failure
+                if pend is not None and pend.todo == 0:
+                    break
+                left = deadline - time.monotonic()
+                if left <= 0:
+                    raise TimeoutError(f"BatchFeeder: batch {seq} was not read within {self.timeout_s:g} s")
+                self._cv.wait(min(left, 0.5))
+        t1 = time.monotonic()
+        self.wait_read_s += t1 - t0
+        if self._uploaded <= seq:                       # not prefetched (the first batch, or the readers were behind)
+            self._upload(pend)
+            self.uploads_late += 1
+        dev = self._dev[seq % (self.depth + 1)]
+        # The staging slot goes back to the readers once its upload has left it: a bounded host wait, normally over at
+        # once because the upload was issued one next() earlier.  Polled sparsely: a query is a call into the runtime.
+        if dev.uploaded is not None:
+            while not dev.uploaded.query():
+                if time.monotonic() > deadline:
+                    raise TimeoutError(f"BatchFeeder: the upload of batch {seq} did not finish within "
+                                       f"{self.timeout_s:g} s")
+                time.sleep(1e-3)
+        self.wait_upload_s += time.monotonic() - t1
+        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev)
+        with self._cv:
+            del self._pending[seq]
+            self._returned = seq + 1                    # frees staging slot seq % depth; batch seq - depth goes stale
+            ahead = self._staged(seq + 1)
+            self._cv.notify_all()
+        if ahead is not None:                           # its device block held batch seq - depth, stale as of now
+            self._upload(ahead)
+        self._epoch_left -= 1
+        return batch
+
+    __next__ = next
+
+    def __iter__(self):
+        return self
+
+    @property
+    def idle_seconds(self):
+        """Host time next() spent waiting, for the readers and for uploads."""
+        return self.wait_read_s + self.wait_upload_s
+
+    def close(self):
+        """Stop and join the reader threads (a thread stuck inside the dataset is abandoned after a bounded wait; it
+        is a daemon)."""
+        with self._cv:
+            self._closed = True
+            self._cv.notify_all()
+        for t in self._threads:
+            t.join(timeout=max(1.0, min(self.timeout_s, 5.0)))
+        self._threads = [t for t in self._threads if t.is_alive()]
+        if self._stream is not None:
+            self._stream.synchronize()
+
+    def __enter__(self):
+        return self
+
+    def __exit__(self, *exc):
+        self.close()
+        return False

@@ -25,6 +25,7 @@ import torch
 import torch.nn as nn
 
 from ..util.stft_loss import MultiResolutionSTFTLoss
+from .feeder import PcmBatch
 from .flat_optim import ST_GRAD_SCALE
 from ..util.util import LinearWarmupCosineDecay, loss_fn
 
@@ -48,7 +49,8 @@ def decay_groups(net, weight_decay):
 
 
 class TrainStep:
-    """``step = TrainStep(net, ...); loss, grad_norm = step(clean, noisy)``.
+    """``step = TrainStep(net, ...); loss, grad_norm = step(clean, noisy)``, or ``step(batch)`` with a batch of
+    training/feeder.BatchFeeder.
 
     repeats: gradient-accumulation micro-steps per optimizer step (reference: ``repeats`` of
       src/training/train.py:282-300).  ``__call__`` splits the batch it is given into ``repeats`` equal micro-batches;
@@ -308,27 +310,43 @@ class TrainStep:
                     warnings.warn("TrainStep: another rank failed to capture the train step; every rank runs eagerly")
         self._graph = g
 
-    def __call__(self, clean_audio, noisy_audio):
-        """Returns (loss tensor on device, grad_norm tensor)."""
+    def __call__(self, clean_audio, noisy_audio=None):
+        """``step(clean, noisy)`` or ``step(batch)`` with a training/feeder.PcmBatch.  Returns (loss tensor on device,
+        grad_norm tensor).  A replayed step assembles a PcmBatch straight into the captured graph's input buffers; the
+        eager and the capturing steps take its ``tensors()``."""
         t0 = time.perf_counter()
+        batch = None
+        if noisy_audio is None:
+            if not isinstance(clean_audio, PcmBatch):
+                raise TypeError("TrainStep: call step(clean, noisy) with two tensors or step(batch) with a PcmBatch")
+            batch, clean_audio = clean_audio, None
         g = self._graph
         if self.use_graph and g is None and self._eager_steps >= GRAPH_WARMUP_STEPS:
+            if batch is not None:
+                (clean_audio, noisy_audio), batch = batch.tensors(), None
             self._capture(clean_audio, noisy_audio)       # capture does not execute: the replay below is this step
             g = self._graph
         replay = self.use_graph and g is not None and "graph" in g
-        if replay and not ((g["clean"].shape, g["clean"].dtype) == (clean_audio.shape, clean_audio.dtype)
-                           and (g["noisy"].shape, g["noisy"].dtype) == (noisy_audio.shape, noisy_audio.dtype)):
+        given = (batch.shape, torch.float32) if batch is not None else (clean_audio.shape, clean_audio.dtype)
+        given_noisy = given if batch is not None else (noisy_audio.shape, noisy_audio.dtype)
+        if replay and not ((g["clean"].shape, g["clean"].dtype) == given
+                           and (g["noisy"].shape, g["noisy"].dtype) == given_noisy):
             if "optim_graph" in g:
                 # several ranks: falling back to the eager step on THIS rank alone would mismatch the collectives
                 raise RuntimeError(
                     f"TrainStep: the captured multi-rank step takes batches of {tuple(g['clean'].shape)} "
-                    f"{g['clean'].dtype}; got {tuple(clean_audio.shape)} {clean_audio.dtype}.  Keep the batch shape "
+                    f"{g['clean'].dtype}; got {tuple(given[0])} {given[1]}.  Keep the batch shape "
                     "fixed (drop the last partial batch) or build the step with use_graph=False")
             replay = False
+        if batch is not None and not replay:
+            (clean_audio, noisy_audio), batch = batch.tensors(), None
         if replay:
             self.buckets.flat.require_intact()
-            g["clean"].copy_(clean_audio)
-            g["noisy"].copy_(noisy_audio)
+            if batch is not None:
+                batch.into(g["clean"], g["noisy"])        # no float batch exists outside the graph's own inputs
+            else:
+                g["clean"].copy_(clean_audio)
+                g["noisy"].copy_(noisy_audio)
             self.optimizer.write_lr()
             g["graph"].replay()
             if "enc_graph" in g:

@@ -806,6 +806,20 @@ int64_t cum_prune_mask_workspace_bytes(int32_t n_desc, int64_t n_idx);
 int cum_prune_mask(const cum_prune_mask_desc *descs, int32_t n_desc, const int32_t *idx, int64_t n_idx, float *save,
                    int64_t n_save, int32_t restore, void *workspace, int64_t workspace_bytes, void *stream);
 
+/* ---- input end of the train step (csrc/pcm.hip) --------------------------------------------------------------------
+ * cum_pcm_batch_f32 <- the int16 -> float scaling and the short-clip tiling of CleanNoisyPairDataset.__getitem__
+ * (src/util/dataset.py:108-150) and the two batch uploads of the train loop (src/training/train.py:259-260): the
+ * loader stages int16 crops and uploads them once; this launch writes the float batch where the step reads it.
+ * pcm: device buffer of 2 * batch rows, `pitch` int16 apart; row b is clean clip b, row batch + b noisy clip b, and
+ * only the first min(src_len[b], len) samples of a row are meaningful.  src_len: device i32[batch].
+ *   clean[b clean_sb + t] = pcm[b][t mod n_b] 2^-15,  noisy[b noisy_sb + t] = pcm[batch + b][t mod n_b] 2^-15,  t < len
+ * with n_b = src_len[b] clamped into [1, len] inside the kernel (a bad table never indexes outside a row).  The
+ * results are exact (an int16 times 2^-15 is a float).  Rows with n_b == len move 16 bytes per lane and access.
+ * batch < 1, len < 1, pitch < len, pitch % 8 != 0, clean_sb < len, noisy_sb < len, a null pointer, or pcm / clean /
+ * noisy off a 16-byte boundary: CUM_EINVAL before any launch. */
+int cum_pcm_batch_f32(const int16_t *pcm, int64_t pitch, const int32_t *src_len, int32_t batch, int64_t len,
+                      float *clean, int64_t clean_sb, float *noisy, int64_t noisy_sb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
