@@ -36,12 +36,22 @@ struct Dec7FwdParams {
   int pitch, valid;    // rows per clip, real rows per clip (T); pair row p <= T produces output rows 2 p, 2 p + 1
   int64_t zero_tail;   // elements to clear behind output row 2 M
   int steps_per_wg;
+  static constexpr bool ragged = false;
+};
+
+// Ragged inference batches (network/ragged.py): clip c = m / pitch keeps only its own vtab[c] <= valid rows of the GLU
+// output -- the rows it would have if it ran alone; everything else is the forward kernel below.
+struct Dec7RaggedParams : Dec7FwdParams {
+  const int *vtab;     // [batch] rows of the GLU output each clip keeps
+  int batch;
+  static constexpr bool ragged = true;
 };
 
 // One workgroup walks a contiguous run of 32-row steps: output row 2 m + q needs the taps q of row m and q + 2 of row m - 1,
 // so the last row's taps are carried from step to step (the run's first step is preceded by one silent step).
-template <typename T>
-__global__ __launch_bounds__(256) void dec7_fwd_kernel(const Dec7FwdParams p) {
+// P: Dec7FwdParams or Dec7RaggedParams -- a compile-time switch, so the plain entry keeps the code it had.
+template <typename T, typename P>
+__global__ __launch_bounds__(256) void dec7_fwd_kernel(const P p) {
   static_assert(sizeof(T) == 2, "16-bit element types only");
   __shared__ __attribute__((aligned(16))) unsigned char ut_all[2][D7_R * D7_US];
   __shared__ float4 pv_all[2][4][D7_R];                  // [step parity][wave][row]: the wave's 16 channels x 4 taps
@@ -114,7 +124,13 @@ __global__ __launch_bounds__(256) void dec7_fwd_kernel(const Dec7FwdParams p) {
         da = e0_mfma<T>(wA[0][ks], ub, da);
         db = e0_mfma<T>(wA[1][ks], ub, db);
       }
-      const bool ok = e0_row_ok(t0, 16 * mt + r, m0, p.M, (unsigned)p.pitch, (unsigned)p.valid);
+      unsigned own = (unsigned)p.valid;                  // rows of the GLU output this row's clip keeps
+      if constexpr (P::ragged) {
+        const unsigned c = (unsigned)m0 / (unsigned)p.pitch + (t0 + (unsigned)(16 * mt + r) >= (unsigned)p.pitch ? 1u : 0u);
+        const unsigned v = (unsigned)p.vtab[c < (unsigned)p.batch ? c : (unsigned)p.batch - 1u];
+        own = v < own ? v : own;
+      }
+      const bool ok = e0_row_ok(t0, 16 * mt + r, m0, p.M, (unsigned)p.pitch, own);
       float pv[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
@@ -476,9 +492,35 @@ extern "C" int cum_dec7_fwd(int32_t dtype, int64_t M, int32_t pitch, int32_t val
   p.steps_per_wg = (int)((steps + nwg - 1) / nwg);
   nwg = (int)((steps + p.steps_per_wg - 1) / p.steps_per_wg);
   if (dtype == CUM_F16)
-    hipLaunchKernelGGL(dec7_fwd_kernel<f16>, dim3(nwg), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((dec7_fwd_kernel<f16, Dec7FwdParams>), dim3(nwg), dim3(256), 0, st, p);
   else
-    hipLaunchKernelGGL(dec7_fwd_kernel<__bf16>, dim3(nwg), dim3(256), 0, st, p);
+    hipLaunchKernelGGL((dec7_fwd_kernel<__bf16, Dec7FwdParams>), dim3(nwg), dim3(256), 0, st, p);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_dec7_fwd_ragged(int32_t dtype, int64_t M, int32_t pitch, int32_t valid, const int32_t *valid_rows,
+                                   int32_t batch, const void *u, const void *w1p, const float *b1p, const float *wt,
+                                   const float *bt, void *out, int64_t zero_tail, void *stream) {
+  CUM_REQUIRE(is16(dtype), "dec7_fwd_ragged: 16-bit element types only (f32 takes the generic path)");
+  CUM_REQUIRE(batch >= 1 && M > 0 && M < 1073741823LL && pitch >= 32 && valid > 0 && valid < pitch &&
+                  M == (int64_t)batch * pitch && zero_tail >= 0, "dec7_fwd_ragged: bad geometry (M must be batch x pitch)");
+  CUM_REQUIRE(u && w1p && b1p && wt && bt && out && valid_rows, "dec7_fwd_ragged: null tensor");
+  CUM_REQUIRE(((uintptr_t)u & 15) == 0 && ((uintptr_t)out & 15) == 0 && ((uintptr_t)w1p & 15) == 0 &&
+                  ((uintptr_t)valid_rows & 3) == 0,
+              "dec7_fwd_ragged: u, out and w1p must be 16-byte aligned, valid_rows 4-byte aligned");
+  hipStream_t st = (hipStream_t)stream;
+  Dec7RaggedParams p{};
+  p.u = u; p.w1p = w1p; p.b1p = b1p; p.wt = wt; p.bt = bt; p.out = out; p.M = M; p.pitch = pitch; p.valid = valid;
+  p.zero_tail = zero_tail; p.vtab = valid_rows; p.batch = batch;
+  const int64_t steps = (M + D7_R - 1) / D7_R;
+  int nwg = dec7_fwd_workgroups(M);
+  p.steps_per_wg = (int)((steps + nwg - 1) / nwg);
+  nwg = (int)((steps + p.steps_per_wg - 1) / p.steps_per_wg);
+  if (dtype == CUM_F16)
+    hipLaunchKernelGGL((dec7_fwd_kernel<f16, Dec7RaggedParams>), dim3(nwg), dim3(256), 0, st, p);
+  else
+    hipLaunchKernelGGL((dec7_fwd_kernel<__bf16, Dec7RaggedParams>), dim3(nwg), dim3(256), 0, st, p);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

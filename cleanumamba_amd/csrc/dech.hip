@@ -30,10 +30,20 @@ struct DecHParams {
   unsigned char *bits;
   int64_t M, u_rows, g_tail, out_tail;
   int pitch, valid;                    // of the input rows: data row d is real iff (d mod pitch) < valid
+  static constexpr bool ragged = false;
 };
 
-template <typename T>
-__global__ __launch_bounds__(512) void dech_fwd_kernel(const DecHParams p) {
+// Ragged inference batches (network/ragged.py): clip c = d / pitch keeps only its own vtab[c] <= valid rows of the GLU
+// output -- the rows it would have if it ran alone; everything else is the kernel above.
+struct DecHRaggedParams : DecHParams {
+  const int *vtab;                     // [batch] rows of the GLU output each clip keeps
+  int batch;
+  static constexpr bool ragged = true;
+};
+
+// P: DecHParams or DecHRaggedParams -- a compile-time switch, so the plain entry keeps the code it had.
+template <typename T, typename P>
+__global__ __launch_bounds__(512) void dech_fwd_kernel(const P p) {
   __shared__ __attribute__((aligned(16))) unsigned char uimg[DH_UR * DH_S];
   __shared__ __attribute__((aligned(16))) unsigned char gimg[DH_UR * DH_S];
   __shared__ __attribute__((aligned(16))) unsigned char bimg[DH_R * 32];
@@ -106,6 +116,8 @@ __global__ __launch_bounds__(512) void dech_fwd_kernel(const DecHParams p) {
       }
     }
     const unsigned t0 = (unsigned)((uint64_t)m0 % (unsigned)p.pitch);      // position of buffer row m0 + 1's data row ...
+    [[maybe_unused]] int c0 = 0;                       // ragged: the clip buffer row m0 belongs to
+    if constexpr (P::ragged) c0 = (int)((uint64_t)m0 / (unsigned)p.pitch);
     // (buffer row b carries data row b - 1; GEMM row m pairs buffer rows m, m + 1 = data rows m - 1, m.  With tt = m mod
     //  pitch: data row m - 1 is real iff 1 <= tt <= valid, GEMM row m has real outputs iff tt <= valid.)
     // ---- GLU tile: g[buffer row m0 + i][16 w + 4 g4 + j] for the 9 groups of 16 rows (i = 0: halo, i > 128: unused)
@@ -120,9 +132,18 @@ __global__ __launch_bounds__(512) void dech_fwd_kernel(const DecHParams p) {
         ab = e0_mfma<T>(wA1b[s], bf, ab);
       }
       unsigned tt = t0 + (unsigned)i;
-      while (tt >= (unsigned)p.pitch) tt -= (unsigned)p.pitch;
+      [[maybe_unused]] int clip = c0;
+      while (tt >= (unsigned)p.pitch) {
+        tt -= (unsigned)p.pitch;
+        if constexpr (P::ragged) ++clip;
+      }
       const int64_t b = m0 + i;                        // buffer row
-      const bool real = b >= 1 && b <= p.M && tt >= 1u && tt <= (unsigned)p.valid;
+      bool real = b >= 1 && b <= p.M && tt >= 1u && tt <= (unsigned)p.valid;
+      if constexpr (P::ragged) {
+        // real so far: b = clip pitch + tt with 1 <= tt < pitch and b <= M = batch pitch, so clip < batch
+        const int own = real ? p.vtab[clip < p.batch ? clip : p.batch - 1] : 0;
+        real = real && tt <= (unsigned)own;
+      }
       const float a[4] = {aa[0] + ba.x, aa[1] + ba.y, aa[2] + ba.z, aa[3] + ba.w};
       const float bg[4] = {ab[0] + bb.x, ab[1] + bb.y, ab[2] + bb.z, ab[3] + bb.w};
       float o[4];
@@ -212,9 +233,35 @@ extern "C" int cum_dech_fwd(int32_t dtype, int64_t M, int32_t pitch, int32_t val
   const int grid = (int)(ntiles < 256 ? ntiles : 256);
   hipStream_t st = (hipStream_t)stream;
   if (dtype == CUM_F16)
-    hipLaunchKernelGGL(dech_fwd_kernel<f16>, dim3(grid), dim3(512), 0, st, p);
+    hipLaunchKernelGGL((dech_fwd_kernel<f16, DecHParams>), dim3(grid), dim3(512), 0, st, p);
   else
-    hipLaunchKernelGGL(dech_fwd_kernel<__bf16>, dim3(grid), dim3(512), 0, st, p);
+    hipLaunchKernelGGL((dech_fwd_kernel<__bf16, DecHParams>), dim3(grid), dim3(512), 0, st, p);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_dech_fwd_ragged(int32_t dtype, int64_t M, int32_t pitch, int32_t valid, const int32_t *valid_rows,
+                                   int32_t batch, const void *u, int64_t u_rows, const void *w1p, const float *b1p,
+                                   const void *wtp, const float *btp, const void *skip, void *out, int64_t out_tail,
+                                   void *stream) {
+  CUM_REQUIRE(is16(dtype), "dech_fwd_ragged: 16-bit element types only");
+  CUM_REQUIRE(batch >= 1 && pitch >= 3 && valid >= 0 && valid < pitch && M == (int64_t)batch * pitch && u_rows >= 1 &&
+                  out_tail >= 0, "dech_fwd_ragged: bad sizes (M must be batch x pitch)");
+  CUM_REQUIRE(u && w1p && b1p && wtp && btp && out && valid_rows, "dech_fwd_ragged: null tensor");
+  CUM_REQUIRE((((uintptr_t)u | (uintptr_t)w1p | (uintptr_t)wtp | (uintptr_t)b1p | (uintptr_t)btp | (uintptr_t)skip |
+                (uintptr_t)out) & 15) == 0 && ((uintptr_t)valid_rows & 3) == 0,
+              "dech_fwd_ragged: pointers must be 16-byte aligned, valid_rows 4-byte aligned");
+  DecHRaggedParams p{};
+  p.u = u; p.w1p = w1p; p.wtp = wtp; p.skip = skip; p.b1p = b1p; p.btp = btp;
+  p.out = out; p.M = M; p.u_rows = u_rows; p.out_tail = out_tail; p.pitch = pitch; p.valid = valid;
+  p.vtab = valid_rows; p.batch = batch;                  // inference only: g, gate and the sign nibbles stay NULL
+  const int64_t ntiles = (M + DH_R - 1) / DH_R;
+  const int grid = (int)(ntiles < 256 ? ntiles : 256);
+  hipStream_t st = (hipStream_t)stream;
+  if (dtype == CUM_F16)
+    hipLaunchKernelGGL((dech_fwd_kernel<f16, DecHRaggedParams>), dim3(grid), dim3(512), 0, st, p);
+  else
+    hipLaunchKernelGGL((dech_fwd_kernel<__bf16, DecHRaggedParams>), dim3(grid), dim3(512), 0, st, p);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

@@ -199,6 +199,12 @@ SIGNATURES = {
     "cum_prune_mask_workspace_bytes": (c_i64, [c_i32, c_i64]),
     "cum_prune_mask": (c_i32, [ctypes.POINTER(PruneMaskDesc), c_i32, _P, c_i64, _P, c_i64, c_i32, _P, c_i64, _P]),
     "cum_pcm_batch_f32": (c_i32, [_P, c_i64, _P, c_i32, c_i64, _P, c_i64, _P, c_i64, _P]),
+    "cum_clip_std_ragged": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, ctypes.c_float, _P, _P]),
+    "cum_frame_rows_ragged": (c_i32, [c_i32, c_i32, _P, c_i32, c_i64, c_i64, _P, c_i64, c_i64, _P, _P, _P]),
+    "cum_rows_zero_tail": (c_i32, [c_i32, _P, c_i32, c_i64, c_i32, _P, _P]),
+    "cum_unframe_rows_ragged": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, _P, _P, _P]),
+    "cum_dech_fwd_ragged": (c_i32, [c_i32, c_i64, c_i32, c_i32, _P, c_i32, _P, c_i64, _P, _P, _P, _P, _P, _P, c_i64, _P]),
+    "cum_dec7_fwd_ragged": (c_i32, [c_i32, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, _P, _P, c_i64, _P]),
 }
 
 _lib = None

@@ -297,14 +297,17 @@ class CleanUMamba(nn.Module):
             return dt
         return torch.float32
 
-    def _forward_fused(self, buf, B, T0, dt, carry=None):
+    def _forward_fused(self, buf, B, T0, dt, carry=None, ragged=None):
         """Encoder, bottleneck and decoder on channels-last row buffers (network/convstack.py).
         buf: row buffer of the (B, 1, T0 = valid_length) input in element type dt.  Returns (row buffer of the output,
         its Geo, skips deepest first as (B, C, T) views, tsfm_out).
         carry (network/blockdenoise.py, inference only): the input is one window of a longer signal -- its first
         ``carry.context`` bottleneck columns were already seen by the previous window.  The Mamba blocks then run on the
         new columns only, continuing from the states in ``carry.params``, and ``carry.join`` puts the previous window's
-        last norm_f outputs back in front for tsfm_conv2 and the decoder."""
+        last norm_f outputs back in front for tsfm_conv2 and the decoder.
+        ragged (network/ragged.py RaggedTables, inference only): the batch holds clips of different lengths, zero padded
+        to T0 -- every decoder layer keeps only the rows of its GLU output that a clip has when it runs alone; the
+        encoder, the bottleneck, tsfm_conv2 and every GEMM are the same launches as without it."""
         E = self.encoder_n_layers
         save = torch.is_grad_enabled()
         self._activate_pack_plan(dt)
@@ -369,7 +372,12 @@ class CleanUMamba(nn.Module):
             dec_geos.append((geo, g_glu, g_out))
             dec_params += [dec[0].weight, dec[0].bias, dec[2].weight, dec[2].bias]
             geo = g_out
-        if getattr(self, "use_stack_backward", True):
+        if ragged is not None:
+            if save:
+                raise RuntimeError("ragged batches are inference only: run them under torch.no_grad()")
+            buf = cs.decoder_layers(buf, dec_geos, False, dec_skips + [None] * (E - len(dec_skips)), dec_params,
+                                    ragged=ragged)[0][-1]
+        elif getattr(self, "use_stack_backward", True):
             buf = cs.DecoderStack.apply(buf, dec_geos, save, len(dec_skips), *dec_skips, *dec_params)
         else:
             for j, ((gi, gg, go), dec) in enumerate(zip(dec_geos, self.decoder)):
@@ -391,6 +399,27 @@ class CleanUMamba(nn.Module):
         gives host output, and device memory does not depend on L."""
         from .blockdenoise import denoise_long
         return denoise_long(self, noisy, block_size=block_size, block_hops=block_hops)
+
+    # ------------------------------------------------------------ ragged batches
+    def forward_ragged(self, x, lengths):
+        """``forward`` on a batch of clips of DIFFERENT lengths in one pass (network/ragged.py).  x: (B, Lmax) int16 PCM, or
+        (B, 1, Lmax) / (B, Lmax) f32, on the GPU, clip b in its first lengths[b] samples; lengths: a host sequence or a
+        device i32 tensor.  -> (B, 1, Lmax) f32: clip b's ``forward`` in [b, 0, :lengths[b]], zeros behind.  no_grad only."""
+        from .ragged import forward_ragged
+        return forward_ragged(self, x, lengths)
+
+    def denoise_batch(self, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+        """[model(c[None, None])[0, 0, :len(c)] for c in clips] for a list of 1-D clips (int16 PCM or f32, host or device)
+        of any lengths, batched by network/ragged.py plan_batches and run by ``forward_ragged``; a clip longer than the
+        sample budget goes through ``denoise_long``.  -> list of f32 device tensors, in the order of ``clips``."""
+        from .ragged import denoise_batch
+        return denoise_batch(self, clips, max_batch=max_batch, budget_samples=budget_samples, max_waste=max_waste)
+
+    @property
+    def ragged_dispatch(self):
+        """The route every decoder layer took in the last ``forward_ragged``: "gemm+zero_tail", "dech_ragged",
+        "dec7_ragged", or the plain name where no clip of the batch is shorter than the batch at that layer."""
+        return list(self.__dict__.get("_ragged_routes", ()))
 
     def _activate_pack_plan(self, dt):
         """One batched re-pack of all conv weights for this forward (and its backward); see cs.PackPlan.  Skipped

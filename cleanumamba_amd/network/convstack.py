@@ -1225,9 +1225,10 @@ def _dech_ok(w1, wt, skip, relu, gi, gg, go, dt):
             and gi.Cp == 128 and gg.Cp == 128 and go.Cp == 64 and gg.P >= 3)
 
 
-def _dech_fwd(ubuf, w1, b1, wt, bt, skip, gi, gg, go, save_z):
+def _dech_fwd(ubuf, w1, b1, wt, bt, skip, gi, gg, go, save_z, valid_rows=None):
     """-> (g buffer, gate, output buffer, sign nibbles): what _glu_fwd + _convt_fwd produce, in one launch
-    (csrc/dech.hip).  Without a backward to come neither g nor the gate nor the nibbles are stored."""
+    (csrc/dech.hip).  Without a backward to come neither g nor the gate nor the nibbles are stored.
+    valid_rows (ragged inference batches, network/ragged.py): device i32[B], the rows of the GLU output each clip keeps."""
     dt, dev = ubuf.dtype, ubuf.device
     sh1, sht = tuple(w1.shape), tuple(wt.shape)
     w1p = take(w1, ("glu_fwd", sh1, 256, 128), lambda: lay_glu_fwd(sh1, 256, 128), dt)
@@ -1243,6 +1244,13 @@ def _dech_fwd(ubuf, w1, b1, wt, bt, skip, gi, gg, go, save_z):
     g = gg.new(dt, dev) if save_z else None
     z = torch.empty(gg.M, 128, dtype=dt, device=dev) if save_z else None
     act = torch.empty(go.R * go.Cp // 4, dtype=torch.uint8, device=dev) if save_z else None
+    if valid_rows is not None:
+        assert not save_z, "ragged batches are inference only"
+        with torch.cuda.device(dev):
+            hip.check(hip.lib().cum_dech_fwd_ragged(
+                hip.dtype_code(dt), gg.M, gg.P, gg.T, hip.ptr(valid_rows), gg.B, hip.ptr(ubuf), gi.R, hip.ptr(w1p),
+                hip.ptr(b1p), hip.ptr(wtp), hip.ptr(btp), hip.ptr(skip[1:]), hip.ptr(ybuf[1:]), go.tail, hip.stream_ptr()))
+        return None, None, ybuf, None
     with torch.cuda.device(dev):
         hip.check(hip.lib().cum_dech_fwd(
             hip.dtype_code(dt), gg.M, gg.P, gg.T, hip.ptr(ubuf), gi.R, hip.ptr(w1p), hip.ptr(b1p), hip.ptr(wtp),
@@ -1274,11 +1282,18 @@ def _dec7_ok(w1, wt, gi, gg, go, dt):
             and wt.dtype == torch.float32)
 
 
-def _dec7_fwd(ubuf, w1, b1, wt, bt, gi, go):
+def _dec7_fwd(ubuf, w1, b1, wt, bt, gi, go, valid_rows=None):
+    """valid_rows (ragged inference batches, network/ragged.py): device i32[B], the rows of the GLU output each clip keeps."""
     dt, dev = ubuf.dtype, ubuf.device
     wp = _enc0_w2p(w1, gi, dt)
     bp = take(b1, ("glu_vec", w1.shape[0]), lambda: lay_glu_vec(w1.shape[0]), torch.float32)
     ybuf = go.new(dt, dev)
+    if valid_rows is not None:
+        with torch.cuda.device(dev):
+            hip.check(hip.lib().cum_dec7_fwd_ragged(hip.dtype_code(dt), gi.M, gi.P, gi.T, hip.ptr(valid_rows), gi.B,
+                                                    hip.ptr(ubuf), hip.ptr(wp), hip.ptr(bp), hip.ptr(wt.detach()),
+                                                    hip.ptr(bt.detach()), hip.ptr(ybuf), go.tail, hip.stream_ptr()))
+        return ybuf
     with torch.cuda.device(dev):
         hip.check(hip.lib().cum_dec7_fwd(hip.dtype_code(dt), gi.M, gi.P, gi.T, hip.ptr(ubuf), hip.ptr(wp), hip.ptr(bp),
                                          hip.ptr(wt.detach()), hip.ptr(bt.detach()), hip.ptr(ybuf), go.tail, hip.stream_ptr()))
@@ -1438,6 +1453,61 @@ def _convt_bias_grad(bt, dbp, Cp, C, dtype):
     return (dbp[:Cp] + dbp[Cp:2 * Cp])[:C].to(dtype)
 
 
+def rows_zero_tail(buf, geo, valid_rows):
+    """Clear rows [valid_rows[b], T) of every clip of a row buffer, in place (csrc/ragged.hip cum_rows_zero_tail):
+    the rows clip b does not have when it runs alone.  valid_rows: device i32[B]."""
+    with torch.cuda.device(buf.device):
+        hip.check(hip.lib().cum_rows_zero_tail(hip.dtype_code(buf.dtype), hip.ptr(buf), geo.B, geo.T, geo.Cp,
+                                               hip.ptr(valid_rows), hip.stream_ptr()))
+    return buf
+
+
+def decoder_layers(ubuf, geos, save_z, skips, params, ragged=None):
+    """The forward of every decoder layer -> (us, gs, zs, acts, fused_last): layer inputs / outputs, GLU outputs, gate
+    pre-activations and ReLU records as DecoderStack keeps them.
+    ragged (network/ragged.py RaggedTables, inference only): the batch holds clips of different lengths; layer j's GLU
+    output keeps only the first ragged.dec_rows[j][b] rows of clip b -- cleared behind the GEMM (cum_rows_zero_tail), or
+    inside the fused kernels that never store it (cum_dech_fwd_ragged / cum_dec7_fwd_ragged).  The route of every layer
+    is appended to ragged.routes."""
+    E = len(geos)
+    assert ragged is None or not save_z, "ragged batches are inference only"
+    us, gs, zs, acts = [ubuf], [], [], []
+    fused_last = False
+    for j, (gi, gg, go) in enumerate(geos):
+        w1, b1, wt, bt = params[4 * j:4 * j + 4]
+        assert gi.T == gg.T and go.P == 2 * gg.P and gg.C == wt.shape[0] and go.C == wt.shape[1]
+        relu = j < E - 1
+        rows = None if ragged is None else ragged.rows_of(j, gg)
+        # last layer (64 -> 1): g and the gate are rebuilt from u where the backward needs them (csrc/dec7.hip); the
+        # fused backward takes the ReLU of the layer below as sign bits and writes into the stack's arena
+        if (j == E - 1 and skips[j] is None and _dec7_ok(w1, wt, gi, gg, go, ubuf.dtype)
+                and (not save_z or (E >= 2 and skips[E - 2] is not None and _SIGN_MASK))):
+            us.append(_dec7_fwd(us[-1], w1, b1, wt, bt, gi, go, valid_rows=rows))
+            gs.append(None)
+            zs.append(None)
+            acts.append(None)
+            fused_last = True
+            if ragged is not None:
+                ragged.routes.append("dec7" if rows is None else "dec7_ragged")
+            continue
+        if _dech_ok(w1, wt, skips[j], relu, gi, gg, go, ubuf.dtype):
+            g, z, y, act = _dech_fwd(us[-1], w1, b1, wt, bt, skips[j], gi, gg, go, save_z, valid_rows=rows)   # one launch (csrc/dech.hip)
+            route = "dech" if rows is None else "dech_ragged"
+        else:
+            g, z = _glu_fwd(us[-1], w1, b1, gi, gg, save_z)
+            if rows is not None:
+                rows_zero_tail(g, gg, rows)
+            y, act = _convt_fwd(g, wt, bt, skips[j], gg, go, relu)
+            route = "gemm" if rows is None else "gemm+zero_tail"
+        if ragged is not None:
+            ragged.routes.append(route)
+        us.append(y)
+        gs.append(g)
+        zs.append(z)
+        acts.append(act)
+    return us, gs, zs, acts, fused_last
+
+
 class DecoderStack(torch.autograd.Function):
     """u_0 -> u_E: every decoder layer [Conv1d 1x1, GLU, ConvTranspose1d k4 s2, (ReLU)] with the encoder skip added
     to its output (src/network/CleanUMamba.py:121-130, 313-316).  geos[j] = (g_in, g_glu, g_out); skips[j] is added
@@ -1447,31 +1517,7 @@ class DecoderStack(torch.autograd.Function):
     def forward(ctx, ubuf, geos, save_z, n_skips, *rest):
         E = len(geos)
         skips, params = list(rest[:n_skips]) + [None] * (E - n_skips), rest[n_skips:]
-        us, gs, zs, acts = [ubuf], [], [], []
-        fused_last = False
-        for j, (gi, gg, go) in enumerate(geos):
-            w1, b1, wt, bt = params[4 * j:4 * j + 4]
-            assert gi.T == gg.T and go.P == 2 * gg.P and gg.C == wt.shape[0] and go.C == wt.shape[1]
-            relu = j < E - 1
-            # last layer (64 -> 1): g and the gate are rebuilt from u where the backward needs them (csrc/dec7.hip); the
-            # fused backward takes the ReLU of the layer below as sign bits and writes into the stack's arena
-            if (j == E - 1 and skips[j] is None and _dec7_ok(w1, wt, gi, gg, go, ubuf.dtype)
-                    and (not save_z or (E >= 2 and skips[E - 2] is not None and _SIGN_MASK))):
-                us.append(_dec7_fwd(us[-1], w1, b1, wt, bt, gi, go))
-                gs.append(None)
-                zs.append(None)
-                acts.append(None)
-                fused_last = True
-                continue
-            if _dech_ok(w1, wt, skips[j], relu, gi, gg, go, ubuf.dtype):
-                g, z, y, act = _dech_fwd(us[-1], w1, b1, wt, bt, skips[j], gi, gg, go, save_z)   # one launch (csrc/dech.hip)
-            else:
-                g, z = _glu_fwd(us[-1], w1, b1, gi, gg, save_z)
-                y, act = _convt_fwd(g, wt, bt, skips[j], gg, go, relu)
-            us.append(y)
-            gs.append(g)
-            zs.append(z)
-            acts.append(act)
+        us, gs, zs, acts, fused_last = decoder_layers(ubuf, geos, save_z, skips, params)
         ctx.geos, ctx.E, ctx.saved_z, ctx.n_skips = geos, E, save_z, n_skips
         ctx.has_act = [a is not None for a in acts]
         ctx.fused_last = fused_last

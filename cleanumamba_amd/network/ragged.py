@@ -1,0 +1,227 @@
+"""Ragged batches: clips of different lengths through ONE fused forward, each equal to its forward alone.
+
+The reference denoises a folder one file per forward (src/examples/denoise.py:42-60: ``batch_size=1``, then
+``sampling(model, noisy_audio)``), because a batch there is a rectangle and padding changes the answer.  Why it does, and
+what repairs it: the encoder (row t reads rows 2t .. 2t + 3 below it) and the Mamba bottleneck (causal)
+give a clip's own rows the same values whatever stands behind them in the batch; a transposed conv's output rows
+2T, 2T + 1 take taps from input row T, which does not exist when the clip runs alone and is not zero in a padded batch
+(biases, skips).  Clearing rows ``t >= T_j(b)`` of the GLU output of each of the E decoder layers -- ``T_j(b)`` the row
+count of that level when clip b runs alone, ``level_rows`` -- makes the padded batch equal the lone forwards (1e-15 on the
+f64 oracle).  Nothing else changes: the encoder, the bottleneck, tsfm_conv2 and every GEMM are the launches ``forward``
+makes.
+
+  level_rows        rows of every level of the U-net for a clip of L samples (pure)
+  plan_batches      which clips share a batch: bounded batch, sample budget and padding waste (pure)
+  forward_ragged    one padded batch: per-clip std, framing, the masked decoder, per-clip crop (csrc/ragged.hip)
+  denoise_batch     a list of clips of any lengths -> their denoised versions, in order
+"""
+import collections
+import ctypes
+
+import torch
+
+from .. import hip
+from . import convstack as cs
+
+Batch = collections.namedtuple("Batch", ["indices", "long"])
+PCM_SCALE = 1.0 / 32768.0
+
+
+def level_rows(L, E, kernel_size=4, stride=2):
+    """[t_0, ..., t_E]: rows of the padded input and of every encoder level for a clip of L samples -- t_0 =
+    valid_length(L) (src/network/CleanUMamba.py:210-225), t_{i+1} = (t_i - k) / s + 1.  Decoder layer j (0 = deepest) reads
+    t_{E-j} rows and limits its GLU output to them."""
+    t = int(L)
+    for _ in range(E):
+        t = 1 if t < kernel_size else 1 + -(-(t - kernel_size) // stride)
+    rows = [t]
+    for _ in range(E):
+        rows.append((rows[-1] - 1) * stride + kernel_size)
+    return rows[::-1]
+
+
+def plan_batches(lengths, valid_length, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+    """Batches for ``forward_ragged``: [Batch(indices, long)], every index exactly once.  Clips are taken longest first;
+    a clip joins the open batch only if afterwards the batch has at most ``max_batch`` clips, B * valid_length(longest)
+    <= ``budget_samples`` and waste = 1 - sum(valid_length(L_i)) / (B * valid_length(longest)) <= ``max_waste`` -- so the
+    padded share of a batch is capped by construction.  A clip that alone exceeds the budget is a batch of one marked
+    ``long`` (it goes through ``denoise_long``).  The defaults are the benched E6 shape: 32 clips of 10 s."""
+    if max_batch < 1:
+        raise ValueError("plan_batches: max_batch must be at least 1")
+    vl = [int(valid_length(int(n))) for n in lengths]
+    order = sorted(range(len(vl)), key=lambda i: (-int(lengths[i]), i))
+    batches, cur, cur_sum = [], [], 0
+    for i in order:
+        if vl[i] > budget_samples:
+            batches.append(Batch([i], True))
+            continue
+        if cur:
+            n, top = len(cur) + 1, vl[cur[0]]
+            if n <= max_batch and n * top <= budget_samples and 1 - (cur_sum + vl[i]) / (n * top) <= max_waste:
+                cur.append(i)
+                cur_sum += vl[i]
+                continue
+            batches.append(Batch(cur, False))
+        cur, cur_sum = [i], vl[i]
+    if cur:
+        batches.append(Batch(cur, False))
+    return batches
+
+
+class RaggedTables:
+    """What a ragged batch carries through ``_forward_fused`` (the way ``carry=`` travels): the clips' lengths and, per
+    decoder layer, the rows of the GLU output each clip keeps -- one i32 device tensor [1 + E, B], uploaded once."""
+
+    def __init__(self, lengths, Lmax, E, kernel_size, stride, device):
+        self.lengths = [int(n) for n in lengths]
+        levels = [level_rows(n, E, kernel_size, stride) for n in self.lengths]
+        self.batch_rows = level_rows(Lmax, E, kernel_size, stride)
+        dec = [[lv[E - j] for lv in levels] for j in range(E)]
+        self.full = [all(r == self.batch_rows[E - j] for r in dec[j]) for j in range(E)]
+        self.table = torch.tensor([self.lengths] + dec, dtype=torch.int32).to(device)
+        self.len = self.table[0]
+        self.dec_rows = [self.table[1 + j] for j in range(E)]
+        self.E = E
+        self.routes = []
+
+    def rows_of(self, j, geo):
+        """Device i32[B] row limits of decoder layer j's GLU output (geometry ``geo``), or None where every clip of the
+        batch has all of the batch's rows at that layer (nothing to clear: the plain launch)."""
+        if geo.T != self.batch_rows[self.E - j] or geo.B != len(self.lengths):
+            raise RuntimeError("ragged tables do not belong to this batch geometry")
+        return None if self.full[j] else self.dec_rows[j]
+
+
+def _check_lengths(lengths, normalize, Lmax=None):
+    low = 2 if normalize else 1
+    for n in lengths:
+        if n < low or (Lmax is not None and n > Lmax):
+            raise ValueError(f"ragged batch: a clip of {n} samples -- lengths must be at least {low}"
+                             + (" (the std of one sample is undefined)" if normalize else "")
+                             + (f" and at most the batch's {Lmax}" if Lmax is not None else ""))
+
+
+def _rows2d(x):
+    if x.dim() == 3:
+        if x.shape[1] != 1:
+            raise ValueError("forward_ragged takes (B, Lmax) or (B, 1, Lmax)")
+        x = x[:, 0]
+    if x.dim() != 2:
+        raise ValueError("forward_ragged takes (B, Lmax) or (B, 1, Lmax)")
+    if x.dtype not in (torch.int16, torch.float32):
+        raise ValueError(f"forward_ragged takes int16 PCM or float32 samples (got {x.dtype})")
+    if not x.is_cuda:
+        raise RuntimeError("forward_ragged: the batch must be on the GPU (there is no CPU fallback)")
+    if x.stride(1) != 1:
+        x = x.contiguous()
+    return x
+
+
+def clip_std_ragged(x2, lens, eps):
+    """(B, Lmax) int16 / f32 rows, device i32[B] -> (B,) f32: unbiased std of each clip's own samples + eps."""
+    B, Lmax = x2.shape
+    out = torch.empty(B, dtype=torch.float32, device=x2.device)
+    with torch.cuda.device(x2.device):
+        hip.check(hip.lib().cum_clip_std_ragged(int(x2.dtype == torch.int16), hip.ptr(x2), B, Lmax, x2.stride(0),
+                                                hip.ptr(lens), ctypes.c_float(eps), hip.ptr(out), hip.stream_ptr()))
+    return out
+
+
+def frame_input_ragged(x2, lens, std, T, dtype):
+    """Rows / std (int16 rows times 2^-15 first) -> the row buffer of Geo(B, T, 1): zeros from each clip's length on."""
+    B, Lmax = x2.shape
+    geo = cs.Geo(B, T, 1)
+    buf = geo.new(dtype, x2.device)
+    with torch.cuda.device(x2.device):
+        hip.check(hip.lib().cum_frame_rows_ragged(hip.dtype_code(dtype), int(x2.dtype == torch.int16), hip.ptr(x2), B, Lmax,
+                                                  x2.stride(0), hip.ptr(lens), T, geo.R, hip.ptr(std), hip.ptr(buf),
+                                                  hip.stream_ptr()))
+    return buf
+
+
+def unframe_ragged(buf, geo, lens, std, Lmax):
+    """Row buffer of the 1-channel output -> (B, 1, Lmax) f32: rows * std in each clip's own length, zeros behind."""
+    y = torch.empty(geo.B, 1, Lmax, dtype=torch.float32, device=buf.device)
+    with torch.cuda.device(buf.device):
+        hip.check(hip.lib().cum_unframe_rows_ragged(hip.dtype_code(buf.dtype), hip.ptr(buf), geo.B, Lmax, geo.T, hip.ptr(lens),
+                                                    hip.ptr(std), hip.ptr(y), hip.stream_ptr()))
+    return y
+
+
+def forward_ragged(model, x, lengths):
+    if torch.is_grad_enabled():
+        raise RuntimeError("forward_ragged is inference only: call it under torch.no_grad()")
+    x2 = _rows2d(x)
+    B, Lmax = x2.shape
+    if B < 1 or Lmax < 1:
+        raise ValueError("forward_ragged: an empty batch")
+    if not getattr(model, "use_fused_convs", True) or not cs.supported(model) or model.channels_output != 1:
+        raise NotImplementedError("forward_ragged runs on the fused conv stack: kernel 4 / stride 2 / ungrouped / "
+                                  "sigmoid-GLU layers, one output channel")
+    if torch.is_tensor(lengths):
+        lengths = lengths.tolist()               # (a device table comes back once: the row limits are built on the host)
+    lengths = [int(n) for n in lengths]
+    if len(lengths) != B:
+        raise ValueError(f"forward_ragged: {len(lengths)} lengths for {B} clips")
+    _check_lengths(lengths, model.normalize_input, Lmax)
+    E = model.encoder_n_layers
+    tables = RaggedTables(lengths, Lmax, E, model.kernel_size, model.stride, x2.device)
+    std = clip_std_ragged(x2, tables.len, 1e-3) if model.normalize_input else None
+    T0 = model.valid_length(Lmax)
+    dt = model._fused_dtype()
+    buf = frame_input_ragged(x2, tables.len, std, T0, dt)
+    with cs.small_m_gemms():                     # as ``forward`` without grad
+        buf, geo, _, _ = model._forward_fused(buf, B, T0, dt, ragged=tables)
+    model.__dict__["_ragged_routes"] = tables.routes
+    return unframe_ragged(buf, geo, tables.len, std, Lmax)
+
+
+def stack_clips(clips, device, pinned=None):
+    """1-D clips (all int16, or f32 / mixed: int16 ones are scaled by 2^-15) -> ((B, pitch) device tensor, Lmax): host
+    clips are gathered in one pinned staging tensor and uploaded ONCE; device clips are copied row by row.  The samples
+    behind a clip's length are never read by the ragged kernels and are left as they are."""
+    Lmax = max(int(c.shape[0]) for c in clips)
+    pitch = cs.rup(Lmax, 8)                      # 16-byte rows for both element types
+    dtype = torch.int16 if all(c.dtype == torch.int16 for c in clips) else torch.float32
+    host = not any(c.is_cuda for c in clips)
+    if host:
+        stage = pinned if pinned is not None and pinned.dtype == dtype and pinned.numel() >= len(clips) * pitch else \
+            torch.empty(len(clips) * pitch, dtype=dtype, pin_memory=True)
+        rows = stage[:len(clips) * pitch].view(len(clips), pitch)
+    else:
+        rows = torch.empty(len(clips), pitch, dtype=dtype, device=device)
+    for b, c in enumerate(clips):
+        if c.dtype == torch.int16 and dtype == torch.float32:
+            c = c.to(torch.float32) * PCM_SCALE
+        rows[b, :c.shape[0]].copy_(c)
+    if host:
+        rows = rows.to(device, non_blocking=True)
+    return rows, Lmax
+
+
+def denoise_batch(model, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+    if torch.is_grad_enabled():
+        with torch.no_grad():
+            return denoise_batch(model, clips, max_batch, budget_samples, max_waste)
+    clips = list(clips)
+    for c in clips:
+        if not torch.is_tensor(c) or c.dim() != 1 or c.dtype not in (torch.int16, torch.float32):
+            raise ValueError("denoise_batch takes 1-D int16 or float32 tensors")
+    lengths = [int(c.shape[0]) for c in clips]
+    _check_lengths(lengths, model.normalize_input)
+    device = next(model.parameters()).device
+    out = [None] * len(clips)
+    for batch in plan_batches(lengths, model.valid_length, max_batch, budget_samples, max_waste):
+        if batch.long:
+            i = batch.indices[0]
+            c = clips[i]
+            c = (c.to(torch.float32) * PCM_SCALE) if c.dtype == torch.int16 else c
+            y = model.denoise_long(c.to(device).view(1, -1))
+            out[i] = y[0, 0, :lengths[i]]
+            continue
+        rows, Lmax = stack_clips([clips[i] for i in batch.indices], device)
+        lens = [lengths[i] for i in batch.indices]
+        y = forward_ragged(model, rows[:, :Lmax], lens)
+        for b, i in enumerate(batch.indices):
+            out[i] = y[b, 0, :lens[b]]
+    return out

@@ -266,3 +266,65 @@ def load_CleanNoisyPairDataset(root="./", subset="training", dataset="dns", crop
     if num_gpus > 1:
         return DataLoader(pairs, sampler=DistributedSampler(pairs), **kwargs)
     return DataLoader(pairs, sampler=None, shuffle=shuffle, **kwargs)
+
+
+class NosyOnlyDataset(Dataset):
+    """Noisy recordings of one folder, with the interface of the reference's class of the same (misspelt) name
+    (src/util/dataset.py:187-208).  Element n: ``(noisy (L,) float32, the same tensor, (-1, 1), file name)``: channel 0 of
+    the file, scaled to [-1, 1) as torchaudio.load scales it.  The files are read by this module's RIFF reader (16-bit mono
+    PCM) or scipy (everything else), not torchaudio; their order is the sorted directory listing, where the reference
+    keeps the order ``os.listdir`` happens to return.  ``info(n)`` and ``read_pcm(n, out)`` expose the header and the raw
+    int16 samples: the route of examples/denoise.py, which leaves scaling to the device (csrc/ragged.hip)."""
+
+    def __init__(self, folder='./'):
+        super().__init__()
+        self.folder = folder
+        self.noisy_files = sorted(os.listdir(folder))
+        self.crop_length_sec = 0
+        self._info = {}
+
+    def info(self, n):
+        """WavInfo of file n, parsed once."""
+        info = self._info.get(n)
+        if info is None:
+            info = self._info[n] = read_wav_info(os.path.join(self.folder, self.noisy_files[n]))
+        return info
+
+    def read_pcm(self, n, out=None):
+        """Channel 0 of file n as int16: straight from the file for 16-bit mono PCM (into ``out`` if given, e.g. a row of a
+        pinned staging tensor); other 16-bit PCM layouts through scipy.  Other encodings raise ValueError."""
+        info = self.info(n)
+        if info.is_pcm16_mono:
+            return _read_range_int16(info, 0, info.frames, out)
+        if info.tag != WAVE_FORMAT_PCM or info.bits != 16:
+            raise ValueError(f"{info.path}: read_pcm takes 16-bit PCM, this file is {info.describe()}")
+        from scipy.io import wavfile
+        x = wavfile.read(info.path)[1]
+        x = np.ascontiguousarray(x[:, 0] if x.ndim == 2 else x)
+        if out is None:
+            return x
+        out[:len(x)] = x
+        return out[:len(x)]
+
+    def __getitem__(self, n):
+        fileid = self.noisy_files[n]
+        info = self.info(n)
+        if info.is_pcm16_mono:
+            x = _read_range_int16(info, 0, info.frames).astype(np.float32) * np.float32(PCM_SCALE)
+        else:
+            x = _read_whole_float(info.path)[1]
+        noisy_audio = torch.from_numpy(np.ascontiguousarray(x))
+        return noisy_audio, noisy_audio, (-1, 1), fileid
+
+    def __len__(self):
+        return len(self.noisy_files)
+
+
+def load_NoisyDataset(folder, batch_size, sample_rate, num_gpus=1):
+    """The reference's DataLoader over a folder of noisy files (src/util/dataset.py:211-224): a DistributedSampler for
+    several GPUs, shuffling otherwise.  ``sample_rate`` is accepted and not used, as in the reference."""
+    dataset = NosyOnlyDataset(folder=folder)
+    kwargs = {"batch_size": batch_size, "num_workers": 0, "pin_memory": False, "drop_last": False}
+    if num_gpus > 1:
+        return DataLoader(dataset, sampler=DistributedSampler(dataset), **kwargs)
+    return DataLoader(dataset, sampler=None, shuffle=True, **kwargs)

@@ -820,6 +820,49 @@ int cum_prune_mask(const cum_prune_mask_desc *descs, int32_t n_desc, const int32
 int cum_pcm_batch_f32(const int16_t *pcm, int64_t pitch, const int32_t *src_len, int32_t batch, int64_t len,
                       float *clean, int64_t clean_sb, float *noisy, int64_t noisy_sb, void *stream);
 
+/* ---- ragged inference batches (csrc/ragged.hip, csrc/dech.hip, csrc/dec7.hip; network/ragged.py) --------------------
+ * The reference denoises a folder one file per forward (src/examples/denoise.py:42-60, batch_size = 1).  Here clips of
+ * different lengths share one forward, zero padded to the longest (lmax samples, T = valid_length(lmax) rows), and the
+ * result of every clip equals its forward alone: each keeps its own std, its own framing and crop, and each decoder
+ * layer's GLU output is cleared past the rows the clip would have alone.  len / valid / valid_rows are
+ * device i32[batch] tables; the kernels clamp them, so a bad table never indexes outside a row.  x holds `batch` rows
+ * `stride` elements apart: int16 PCM (src_i16 = 1, a sample is x 2^-15, exact) or f32 (src_i16 = 0).
+ * Every entry returns CUM_EINVAL before any launch for batch < 1, lmax < 1 (T < 1 where there is no lmax), a null
+ * pointer or a misaligned buffer (row buffers and packed operands 16 bytes; tables and f32 arrays 4; int16 rows 2).
+ *
+ * cum_clip_std_ragged <- `noisy_audio.std(dim=2, keepdim=True) + 1e-3` (src/network/CleanUMamba.py:260-262) of every
+ *   file: out[b] = unbiased std of the first len[b] samples of row b + eps.  One launch for the batch, one workgroup
+ *   per clip: Welford per thread over 8-sample chunks, Chan merges in a fixed order that depends on len[b] alone, so a
+ *   clip's value does not depend on its batch mates, on stride or on alignment.  len[b] = 1 gives nan, as torch.std.
+ * cum_frame_rows_ragged <- `noisy / std` + pad_signal (CleanUMamba.py:262-264) into the row buffer of Geo(batch, T, 1)
+ *   in element type dtype: x / scale[b] for t < len[b] (a true division), zero for len[b] <= t < T, and the zero head
+ *   row, the two pad rows per clip and the slack rows, as cum_frame_rows writes them (total_rows in all).  scale may be
+ *   NULL (= 1).  16-byte loads where a row starts on a 16-byte boundary, 16-byte stores always.
+ * cum_rows_zero_tail: on the row buffer of Geo(batch, T, C) (cp = C rounded up to 8 elements per row) clear rows
+ *   [valid[b], T) of every clip and touch nothing else -- the rows `glu(conv1x1(x))` (CleanUMamba.py:121-130, decoder
+ *   modules 0-1) does not have when clip b runs alone.  Work is proportional to the rows cleared.
+ * cum_unframe_rows_ragged <- `x[:, :, :L] * std` (CleanUMamba.py:319) per clip: y[b][t] = rows[1 + b (T + 2) + t][0] *
+ *   scale[b] for t < len[b], 0 for len[b] <= t < lmax; y is (batch, lmax) f32, contiguous.  scale may be NULL. */
+int cum_clip_std_ragged(int32_t src_i16, const void *x, int32_t batch, int64_t lmax, int64_t stride, const int32_t *len,
+                        float eps, float *out, void *stream);
+int cum_frame_rows_ragged(int32_t dtype, int32_t src_i16, const void *x, int32_t batch, int64_t lmax, int64_t stride,
+                          const int32_t *len, int64_t T, int64_t total_rows, const float *scale, void *out, void *stream);
+int cum_rows_zero_tail(int32_t dtype, void *rows, int32_t batch, int64_t T, int32_t cp, const int32_t *valid,
+                       void *stream);
+int cum_unframe_rows_ragged(int32_t dtype, const void *rows, int32_t batch, int64_t lmax, int64_t T, const int32_t *len,
+                            const float *scale, float *y, void *stream);
+
+/* cum_dech_fwd_ragged / cum_dec7_fwd_ragged: cum_dech_fwd / cum_dec7_fwd (the decoder layers of
+ * src/network/CleanUMamba.py:121-130 at widths 128 and 64, which never store their GLU output) for a ragged batch: the
+ * GLU output of clip c = row / pitch is kept for its first min(valid_rows[c], valid) rows only; M must be batch x pitch.
+ * The same kernel bodies, switched at compile time.  Inference only: no GLU output, gate or sign nibbles are stored. */
+int cum_dech_fwd_ragged(int32_t dtype, int64_t M, int32_t pitch, int32_t valid, const int32_t *valid_rows, int32_t batch,
+                        const void *u, int64_t u_rows, const void *w1p, const float *b1p, const void *wtp,
+                        const float *btp, const void *skip, void *out, int64_t out_tail, void *stream);
+int cum_dec7_fwd_ragged(int32_t dtype, int64_t M, int32_t pitch, int32_t valid, const int32_t *valid_rows, int32_t batch,
+                        const void *u, const void *w1p, const float *b1p, const float *wt, const float *bt, void *out,
+                        int64_t zero_tail, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
