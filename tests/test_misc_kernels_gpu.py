@@ -1,5 +1,6 @@
 """Small C-ABI entry points against their torch equivalents (GPU): operand gather, hipFFT wrappers, the waveform-end
-kernels of csrc/loss.hip (time-domain loss term, per-clip std, input / output framing)."""
+kernels of csrc/loss.hip (time-domain loss term, per-clip std, input / output framing), the streaming glue of
+csrc/stream.hip (window update on every path, overlap-add)."""
 import pytest
 import torch
 
@@ -173,3 +174,116 @@ def test_clip_std_and_framing(cuda, shape):
         wleaf = ref.clone().float().requires_grad_(True)
         ((cs.from_rows(wleaf.to(dt), geo).float()[:, :, :L] * std) * dy).sum().backward()
         assert rel_l2(leaf.grad, wleaf.grad) < (1e-6 if dt == torch.float32 else 4e-3)
+
+
+# ---- streaming glue (csrc/stream.hip): pure data movement and single IEEE additions, so every assertion is torch.equal
+def _window_case(cuda, dt, S, rows, n_new, Cp, tail, compact):
+    from cleanumamba_amd import hip
+    pitch = rows + 3
+    g = torch.Generator().manual_seed(rows * 31 + n_new)
+    window = torch.randn(S, pitch, Cp, generator=g).to(dt).to(cuda)
+    full = torch.randn(S, pitch, Cp, generator=g).to(dt).to(cuda)
+    want = torch.cat([window[:, n_new:rows], full[:, rows - n_new:rows]], 1)
+    w = window.clone()
+    fresh = full[:, rows - n_new:rows].contiguous() if compact else full
+    fresh0 = fresh.clone()
+    tmp = torch.empty(S * rows * Cp, dtype=dt, device=cuda)
+    nxt = torch.full((S, n_new + 4, Cp), 7.0, dtype=dt, device=cuda) if tail else None
+    with torch.cuda.device(cuda):
+        hip.check(hip.lib().cum_stream_window_update(hip.dtype_code(dt), S, rows, n_new, Cp, hip.ptr(w), hip.ptr(fresh), pitch,
+                                                     n_new if compact else pitch, rows - n_new if compact else 0,
+                                                     hip.ptr(tmp), hip.ptr(nxt), n_new + 4, hip.stream_ptr()))
+    assert torch.equal(w[:, :rows], want)
+    assert torch.equal(w[:, rows:], window[:, rows:])           # the rows of the pitch behind the window are untouched
+    assert torch.equal(fresh, fresh0)
+    if tail:          # the n_new + 2 newest rows, and the sentinel rows behind them
+        assert torch.equal(nxt[:, :n_new + 2], want[:, rows - n_new - 2:])
+        assert bool((nxt[:, n_new + 2:] == 7.0).all())
+
+
+@pytest.mark.parametrize("compact", [False, True])
+@pytest.mark.parametrize("dt,S,rows,n_new,Cp,tail", [
+    (torch.float32, 5, 300, 4, 128, True),      # keep = 296: six chunks of 6 vectors, the last holds two
+    (torch.float32, 5, 22, 22, 24, False),      # n_new == rows: nothing is kept
+    (torch.bfloat16, 5, 22, 22, 24, False),
+    (torch.float32, 5, 10, 8, 24, True),        # keep == 2: the carried rows of tail_dst are all that is kept
+    (torch.float16, 5, 10, 8, 24, True),
+    (torch.bfloat16, 3, 2052, 4, 8, True),      # keep = 2048: the most the in-place kernel holds (8 vectors a thread)
+    (torch.float16, 3, 2053, 4, 8, False),      # keep = 2049: the two-launch path through tmp
+    (torch.bfloat16, 5, 22, 8, 20, False),      # 40-byte rows: the two-launch path through alignment
+    (torch.float32, 5, 22, 8, 6, False),        # 24-byte rows
+])
+def test_stream_window_update_paths(cuda, dt, S, rows, n_new, Cp, tail, compact):
+    """cum_stream_window_update against slicing on every path: the in-place kernel with several channel chunks and a
+    ragged last one, with nothing kept, with exactly the two carried rows, at its register limit; the shift + store pair
+    beyond that limit and on rows that are not 16-byte multiples."""
+    _window_case(cuda, dt, S, rows, n_new, Cp, tail, compact)
+
+
+def _overlap_add(cuda, dt, y, tail, bias, skip, S, L2, Cp, C, relu):
+    """One hop through cum_stream_overlap_add; -> (out buffer with two sentinel rows per stream, the tail it left) and
+    the same from the formula in the header of csrc/stream.hip, in f32 from the stored values, rounded once."""
+    from cleanumamba_amd import hip
+    out = torch.full((S, L2 + 2, Cp), 7.0, dtype=dt, device=cuda)
+    t_new = tail.clone()
+    with torch.cuda.device(cuda):
+        hip.check(hip.lib().cum_stream_overlap_add(hip.dtype_code(dt), S, L2, Cp, C, hip.ptr(y), y.shape[1], hip.ptr(t_new),
+                                                   hip.ptr(bias), hip.ptr(skip), 0 if skip is None else skip.shape[1],
+                                                   hip.ptr(out), L2 + 2, relu, hip.stream_ptr()))
+    o = y[:, :L2].float().clone()
+    o[:, :2] += tail.float()
+    if relu:
+        o = o.clamp_min(0)
+    if skip is not None:
+        o = o + skip[:, :L2].float()
+    live = (torch.arange(Cp, device=cuda) < C).view(1, 1, Cp)
+    zero = torch.zeros((), device=cuda)
+    want = torch.where(live, o, zero).to(dt)
+    b = torch.zeros(Cp, device=cuda)
+    if bias is not None:
+        b[:C] = bias[:C]
+    want_tail = torch.where(live, y[:, L2:L2 + 2].float() - b, zero).to(dt)
+    return out, t_new, want, want_tail
+
+
+@pytest.mark.parametrize("L2", [2, 4, 256])
+@pytest.mark.parametrize("relu", [0, 1])
+@pytest.mark.parametrize("dt", [torch.float32, torch.bfloat16, torch.float16])
+def test_stream_overlap_add(cuda, dt, relu, L2):
+    """out = act(y + old tail on the first two rows) + skip, tail = the frame's last two rows minus the bias, with C < Cp
+    (pad channels of out and tail are exact zeros whatever y, skip and the old tail hold there), pitches larger than
+    needed (sentinel rows stay) and skip / bias present or null."""
+    S, Cp, C = 3, 24, 20
+    g = torch.Generator().manual_seed(L2 + relu)
+    rn = lambda *s: torch.randn(*s, generator=g)
+    y = rn(S, L2 + 5, Cp).to(dt).to(cuda)
+    skip_t = rn(S, L2 + 1, Cp).to(dt).to(cuda)
+    bias_t = rn(Cp).to(cuda)
+    tail = rn(S, 2, Cp).to(dt).to(cuda)
+    y0, tail0, skip0 = y.clone(), tail.clone(), skip_t.clone()
+    for skip in (skip_t, None):
+        for bias in (bias_t, None):
+            out, t_new, want, want_tail = _overlap_add(cuda, dt, y, tail, bias, skip, S, L2, Cp, C, relu)
+            assert torch.equal(out[:, :L2], want) and torch.equal(t_new, want_tail)
+            assert bool((out[:, L2:] == 7.0).all())
+            assert float(out[:, :L2, C:].abs().max()) == 0.0 and float(t_new[:, :, C:].abs().max()) == 0.0
+            assert torch.equal(y, y0) and torch.equal(tail, tail0) and torch.equal(skip_t, skip0)
+
+
+def test_stream_overlap_add_two_hops_and_the_grid_stride_pass(cuda):
+    """Two consecutive hops: the tail the first writes is what the second adds to its first two rows.  37 streams of
+    L2 = 256 at Cp = 128 are 1 221 888 elements, more than 4096 workgroups of 256 threads: the second pass of the
+    grid-stride loop."""
+    for dt, S, L2, Cp, C in ((torch.bfloat16, 3, 4, 24, 20), (torch.float32, 37, 256, 128, 128), (torch.float16, 37, 256, 128, 100)):
+        g = torch.Generator().manual_seed(S)
+        rn = lambda *s: torch.randn(*s, generator=g)
+        bias = rn(Cp).to(cuda)
+        tail = torch.zeros(S, 2, Cp, dtype=dt, device=cuda)
+        for hop in range(2):
+            y, skip = rn(S, L2 + 2, Cp).to(dt).to(cuda), rn(S, L2, Cp).to(dt).to(cuda)
+            out, t_new, want, want_tail = _overlap_add(cuda, dt, y, tail, bias, skip, S, L2, Cp, C, 1)
+            assert torch.equal(out[:, :L2], want) and torch.equal(t_new, want_tail), (dt, hop)
+            if hop == 1:      # the first hop's tail was consumed: without it the first two rows differ
+                assert not torch.equal(_overlap_add(cuda, dt, y, torch.zeros_like(tail), bias, skip, S, L2, Cp, C, 1)[0][:, :2],
+                                       out[:, :2])
+            tail = t_new
