@@ -14,7 +14,8 @@ reference does.  Differences from the reference, on purpose:
     alone (DESIGN.md 7f).  A file longer than ``budget_samples`` goes through ``model.denoise_long``;
   * a file whose sample rate is not 16000 raises ValueError naming the files, before any GPU work; the reference ignores
     the rate (torchaudio.load's second result is dropped, src/util/dataset.py:203) and so denoises such a file at the
-    wrong rate.  There is no resampling here;
+    wrong rate.  With ``resample=True`` (``--resample``) such a file is converted to 16000 Hz on the GPU, denoised,
+    converted back and written at its own rate and its own length (util/resample.py, DESIGN.md 7g);
   * no ``torchinfo`` model summary is printed and there is no ``tqdm`` bar.
 """
 import argparse
@@ -28,6 +29,7 @@ import torch
 from ..network import convstack as cs
 from ..network.ragged import PCM_SCALE, plan_batches
 from ..util.dataset import WAVE_FORMAT_PCM, NosyOnlyDataset, _read_whole_float
+from ..util.resample import out_length, plan as resample_plan
 from .loading_pretrained_models import load_pretrained_CleanUMamba
 
 SAMPLE_RATE = 16000
@@ -39,7 +41,8 @@ def check_rates(dataset, sample_rate=SAMPLE_RATE):
     bad = [f"{name} ({dataset.info(n).rate} Hz)" for n, name in enumerate(dataset.noisy_files)
            if dataset.info(n).rate != sample_rate]
     if bad:
-        raise ValueError(f"denoise: the model runs at {sample_rate} Hz and nothing here resamples; other rates in "
+        raise ValueError(f"denoise: the model runs at {sample_rate} Hz and nothing here resamples (resample=True / "
+                         f"--resample converts); other rates in "
                          f"{dataset.folder}: " + ", ".join(bad))
 
 
@@ -66,8 +69,12 @@ def _stage(dataset, indices, pool):
     return stage, lengths, [pool.submit(read, b, n) for b, n in enumerate(indices)]
 
 
+def _clip_f32(row):
+    return row.to(torch.float32) * PCM_SCALE if row.dtype == torch.int16 else row
+
+
 def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batch=32, budget_samples=32 * 160000,
-            autocast_dtype=None):
+            autocast_dtype=None, resample=False):
     """
     Denoise audio
 
@@ -77,9 +84,15 @@ def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batc
     output_directory (str/None):    save generated speeches to this path if provided
     max_batch, budget_samples:      bounds of one ragged batch (network/ragged.py plan_batches)
     autocast_dtype:                 torch.float16 / torch.bfloat16 to run under autocast, None for float32
+    resample:                       take files at any sample rate: each is converted to the model's rate, denoised,
+                                    converted back and written (and returned) at its own rate and length
     """
     dataset = NosyOnlyDataset(folder=input_directory)
-    check_rates(dataset)
+    rates = [dataset.info(n).rate for n in range(len(dataset))]
+    if resample:
+        plans = {r: resample_plan(r, SAMPLE_RATE) for r in set(rates)}     # ValueError for a rate that cannot be converted
+    else:
+        check_rates(dataset)
 
     model = load_pretrained_CleanUMamba(checkpoint_path)
     model.eval()
@@ -93,6 +106,8 @@ def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batc
     from scipy.io.wavfile import write as wavwrite
     device = next(model.parameters()).device
     lengths = [dataset.info(n).frames for n in range(len(dataset))]
+    if resample:                                                           # batches hold what the model will see
+        lengths = [out_length(n, plans[r].up, plans[r].down) for n, r in zip(lengths, rates)]
     batches = plan_batches(lengths, model.valid_length, max_batch=max_batch, budget_samples=budget_samples)
     all_noisy_audio, all_cleaned_audio = [None] * len(dataset), [None] * len(dataset)
     amp = torch.autocast("cuda", dtype=autocast_dtype) if autocast_dtype is not None else contextlib.nullcontext()
@@ -104,19 +119,28 @@ def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batc
                 r.result()
             # the next batch is read while the device runs this one
             staged = _stage(dataset, batches[k + 1].indices, pool) if k + 1 < len(batches) else None
-            if batch.long:
-                clean = model.denoise_batch([stage[0, :lens[0]]], max_batch=max_batch, budget_samples=budget_samples)[0]
-                clean = clean.view(1, 1, -1)
+            brates = [rates[n] for n in batch.indices]
+            if all(r == SAMPLE_RATE for r in brates):
+                if batch.long:
+                    clean = model.denoise_batch([stage[0, :lens[0]]], max_batch=max_batch, budget_samples=budget_samples)[0]
+                    clean = clean.view(1, 1, -1)
+                else:
+                    rows = stage.to(device, non_blocking=True)             # one upload per batch
+                    clean = model.forward_ragged(rows[:, :max(lens)], lens)
+                clean = clean.cpu()
+                cleans = [clean[b, 0, :lens[b]] for b in range(len(lens))]
+            elif batch.long:                                               # host in, host out: a piece at a time
+                cleans = [model.denoise_long(_clip_f32(stage[0, :lens[0]]).view(1, -1), rate=brates[0])[0, 0]]
             else:
-                rows = stage.to(device, non_blocking=True)                 # one upload per batch
-                clean = model.forward_ragged(rows[:, :max(lens)], lens)
-            clean = clean.cpu()
+                cleans = [c.cpu() for c in model.denoise_batch([stage[b, :lens[b]] for b in range(len(lens))],
+                                                               max_batch=max_batch, budget_samples=budget_samples,
+                                                               rates=brates)]
             for b, n in enumerate(batch.indices):
                 noisy = stage[b, :lens[b]].numpy()
                 noisy = noisy.astype(np.float32) * np.float32(PCM_SCALE) if noisy.dtype == np.int16 else noisy.copy()
-                generated = clean[b, 0, :lens[b]].numpy().copy()
+                generated = cleans[b].numpy().copy()
                 if output_directory:
-                    wavwrite(os.path.join(output_directory, f'enhanced_{dataset.noisy_files[n]}'), SAMPLE_RATE, generated)
+                    wavwrite(os.path.join(output_directory, f'enhanced_{dataset.noisy_files[n]}'), brates[b], generated)
                 all_noisy_audio[n] = noisy
                 all_cleaned_audio[n] = generated
     return all_noisy_audio, all_cleaned_audio
@@ -132,6 +156,8 @@ if __name__ == "__main__":
                         help='Output folder path to save the audio to')
     parser.add_argument('--max_batch', type=int, default=32, help='Most files in one forward')
     parser.add_argument('--autocast', choices=['f16', 'bf16'], default=None, help='Run under autocast in this type')
+    parser.add_argument('--resample', action='store_true',
+                        help='Take files at any sample rate: convert to 16000 Hz, denoise, write at the file\'s own rate')
     args = parser.parse_args()
     denoise(args.checkpoint_path, args.input_directory, args.output_directory, max_batch=args.max_batch,
-            autocast_dtype={None: None, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.autocast])
+            autocast_dtype={None: None, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.autocast], resample=args.resample)

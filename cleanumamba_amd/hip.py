@@ -205,6 +205,9 @@ SIGNATURES = {
     "cum_unframe_rows_ragged": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, _P, _P, _P]),
     "cum_dech_fwd_ragged": (c_i32, [c_i32, c_i64, c_i32, c_i32, _P, c_i32, _P, c_i64, _P, _P, _P, _P, _P, _P, c_i64, _P]),
     "cum_dec7_fwd_ragged": (c_i32, [c_i32, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, _P, _P, c_i64, _P]),
+    "cum_resample_tile": (c_i32, []),
+    "cum_resample_ragged": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, _P, c_i32, c_i32, c_i32, c_i32, c_i32, _P, c_i32,
+                                    _P, c_i64, c_i64, _P]),
 }
 
 _lib = None

@@ -394,11 +394,13 @@ class CleanUMamba(nn.Module):
         from .blockdenoise import BlockDenoiser
         return BlockDenoiser(self, streams, std=std, block_hops=block_hops)
 
-    def denoise_long(self, noisy, block_size=160000, block_hops=None):
+    def denoise_long(self, noisy, block_size=160000, block_hops=None, rate=None, model_rate=16000):
         """``forward`` on a (B, L) / (B, 1, L) signal of any length, block by block (network/blockdenoise.py).  Host input
-        gives host output, and device memory does not depend on L."""
+        gives host output, and device memory does not depend on L.  rate: the signal's sample rate if it is not the
+        model's -- the signal is converted to ``model_rate``, denoised and converted back as one stream
+        (util/resample.py StreamResampler), and comes back (B, 1, L) at its own rate."""
         from .blockdenoise import denoise_long
-        return denoise_long(self, noisy, block_size=block_size, block_hops=block_hops)
+        return denoise_long(self, noisy, block_size=block_size, block_hops=block_hops, rate=rate, model_rate=model_rate)
 
     # ------------------------------------------------------------ ragged batches
     def forward_ragged(self, x, lengths):
@@ -408,12 +410,16 @@ class CleanUMamba(nn.Module):
         from .ragged import forward_ragged
         return forward_ragged(self, x, lengths)
 
-    def denoise_batch(self, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+    def denoise_batch(self, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25, rates=None, model_rate=16000):
         """[model(c[None, None])[0, 0, :len(c)] for c in clips] for a list of 1-D clips (int16 PCM or f32, host or device)
         of any lengths, batched by network/ragged.py plan_batches and run by ``forward_ragged``; a clip longer than the
-        sample budget goes through ``denoise_long``.  -> list of f32 device tensors, in the order of ``clips``."""
+        sample budget goes through ``denoise_long``.  -> list of f32 device tensors, in the order of ``clips``.
+        rates: one sample rate for all clips or one per clip; a clip at another rate than ``model_rate`` is converted to
+        it, denoised, converted back and cropped to its own length (util/resample.py).  None: every clip is at the
+        model's rate."""
         from .ragged import denoise_batch
-        return denoise_batch(self, clips, max_batch=max_batch, budget_samples=budget_samples, max_waste=max_waste)
+        return denoise_batch(self, clips, max_batch=max_batch, budget_samples=budget_samples, max_waste=max_waste,
+                             rates=rates, model_rate=model_rate)
 
     @property
     def ragged_dispatch(self):

@@ -178,12 +178,61 @@ class BlockDenoiser:
         return out if device is None else out.to(device)
 
 
+def _denoise_long_at_rate(model, noisy, bh, rate, model_rate):
+    """``denoise_long`` for a (B, L) signal at ``rate``: the chain StreamResampler -> BlockDenoiser.push ->
+    StreamResampler, a piece at a time, so device memory does not depend on L.  The std the block denoiser needs is
+    that of the WHOLE converted signal: a first conversion pass accumulates its sum and sum of squares in f64 (as
+    ``host_clip_std`` does) and discards the samples.  -> (B, 1, L) at ``rate``, on noisy's device: the converted-back
+    signal cropped to L (a round trip never shortens a signal)."""
+    from ..util.resample import StreamResampler, out_length, plan
+    p = plan(rate, model_rate)
+    plan(model_rate, rate)
+    B, L = noisy.shape
+    dev = next(model.parameters()).device
+    hop = model.total_stride
+    step = max(1, out_length(bh * hop, p.down, p.up))        # input samples of about one block
+    std = None
+    if model.normalize_input:
+        n = out_length(L, p.up, p.down)
+        s = torch.zeros(B, dtype=torch.float64, device=dev)
+        q = torch.zeros(B, dtype=torch.float64, device=dev)
+        first = StreamResampler(B, rate, model_rate, dev)
+        for i in range(0, L, step):
+            y = first.push(noisy[:, i:i + step].to(dev)).double()
+            s += y.sum(1)
+            q += (y * y).sum(1)
+        y = first.finish().double()
+        s += y.sum(1)
+        q += (y * y).sum(1)
+        var = (q - s * s / n).clamp_(min=0) / (n - 1)          # one converted sample: nan, as torch.std
+        std = (var.sqrt() + 1e-3).float().view(B, 1)
+    to_model = StreamResampler(B, rate, model_rate, dev)
+    den = BlockDenoiser(model, B, std=std, block_hops=bh)
+    back = StreamResampler(B, model_rate, rate, dev)
+    out = torch.empty(B, 1, L, dtype=torch.float32, device=noisy.device)
+    pos = 0
+
+    def emit(y):
+        nonlocal pos
+        m = min(y.shape[1], L - pos)
+        out[:, 0, pos:pos + m] = y[:, :m]
+        pos += m
+    for i in range(0, L, step):
+        emit(back.push(den.push(to_model.push(noisy[:, i:i + step].to(dev)))))
+    emit(back.push(den.push(to_model.finish())))
+    emit(back.push(den.finish()))
+    emit(back.finish())
+    assert pos == L
+    return out
+
+
 @torch.no_grad()
-def denoise_long(model, noisy, block_size=DEFAULT_BLOCK, block_hops=None):
+def denoise_long(model, noisy, block_size=DEFAULT_BLOCK, block_hops=None, rate=None, model_rate=16000):
     """What ``model(noisy)`` returns -- (B, 1, L) with ``normalize_input``, (B, 1, valid_length(L)) without -- computed
     block by block.  noisy: (B, L) or (B, 1, L), on the GPU or on the host; host input is copied in and out a block at a
     time and gives host output, so device memory does not depend on L.  ``block_size`` (samples) is rounded down to
-    whole hops; ``block_hops`` gives the columns per block directly."""
+    whole hops; ``block_hops`` gives the columns per block directly.  ``rate``: the signal's sample rate; one other than
+    ``model_rate`` converts the signal to the model's rate and back as a stream (``_denoise_long_at_rate``: (B, 1, L))."""
     check_model(model)
     if noisy.dim() == 3:
         if noisy.shape[1] != 1:
@@ -196,6 +245,8 @@ def denoise_long(model, noisy, block_size=DEFAULT_BLOCK, block_hops=None):
     bh = int(block_hops) if block_hops is not None else int(block_size) // hop
     if bh < 2:
         raise ValueError("block denoising needs at least 2 columns per block: block_size >= 2 * total_stride")
+    if rate is not None and rate != model_rate:
+        return _denoise_long_at_rate(model, noisy.float(), bh, rate, model_rate)
     dev = next(model.parameters()).device
     host = not noisy.is_cuda
     noisy = noisy.float()

@@ -13,7 +13,8 @@ makes.
   level_rows        rows of every level of the U-net for a clip of L samples (pure)
   plan_batches      which clips share a batch: bounded batch, sample budget and padding waste (pure)
   forward_ragged    one padded batch: per-clip std, framing, the masked decoder, per-clip crop (csrc/ragged.hip)
-  denoise_batch     a list of clips of any lengths -> their denoised versions, in order
+  denoise_batch     a list of clips of any lengths -> their denoised versions, in order; with ``rates`` each clip at
+                    its own sample rate (converted to the model's and back by util/resample.py)
 """
 import collections
 import ctypes
@@ -199,14 +200,20 @@ def stack_clips(clips, device, pinned=None):
     return rows, Lmax
 
 
-def denoise_batch(model, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+def denoise_batch(model, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25, rates=None, model_rate=16000):
     if torch.is_grad_enabled():
         with torch.no_grad():
-            return denoise_batch(model, clips, max_batch, budget_samples, max_waste)
+            return denoise_batch(model, clips, max_batch, budget_samples, max_waste, rates, model_rate)
     clips = list(clips)
     for c in clips:
         if not torch.is_tensor(c) or c.dim() != 1 or c.dtype not in (torch.int16, torch.float32):
             raise ValueError("denoise_batch takes 1-D int16 or float32 tensors")
+    if rates is not None:
+        rates = [rates] * len(clips) if not isinstance(rates, (list, tuple)) else list(rates)
+        if len(rates) != len(clips):
+            raise ValueError(f"denoise_batch: {len(rates)} rates for {len(clips)} clips")
+        if any(r != model_rate for r in rates):
+            return _denoise_batch_at_rates(model, clips, rates, model_rate, max_batch, budget_samples, max_waste)
     lengths = [int(c.shape[0]) for c in clips]
     _check_lengths(lengths, model.normalize_input)
     device = next(model.parameters()).device
@@ -224,4 +231,41 @@ def denoise_batch(model, clips, max_batch=32, budget_samples=32 * 160000, max_wa
         y = forward_ragged(model, rows[:, :Lmax], lens)
         for b, i in enumerate(batch.indices):
             out[i] = y[b, 0, :lens[b]]
+    return out
+
+
+def _resample_group(clips, rate_in, rate_out, device, max_batch):
+    """1-D clips of one rate -> their conversions to ``rate_out`` (f32 device tensors), ``max_batch`` clips a launch.
+    int16 clips stay int16 up to the kernel."""
+    from ..util.resample import resample_ragged
+    out = []
+    for k in range(0, len(clips), max_batch):
+        part = clips[k:k + max_batch]
+        rows, Lmax = stack_clips(part, device)
+        y, n = resample_ragged(rows[:, :Lmax], [int(c.shape[0]) for c in part], rate_in, rate_out)
+        out += [y[b, :n[b]] for b in range(len(part))]
+    return out
+
+
+def _denoise_batch_at_rates(model, clips, rates, model_rate, max_batch, budget_samples, max_waste):
+    """``denoise_batch`` for clips at their own sample rates: every clip whose rate is not the model's is converted to
+    it (one launch per rate and ``max_batch`` clips, util/resample.py), the whole list is denoised as one
+    ``denoise_batch`` call at the model's rate -- so the batches are planned, and the lengths checked, on the converted
+    lengths -- and every converted clip is taken back to its own rate and cropped to its own length (a round trip never
+    shortens a clip).  Clips at the model's rate pass through untouched."""
+    from ..util.resample import plan
+    groups = {}
+    for i, r in enumerate(rates):
+        if r != model_rate:
+            plan(r, model_rate), plan(model_rate, r)         # ValueError for a rate that cannot be converted, before any work
+            groups.setdefault(int(r), []).append(i)
+    device = next(model.parameters()).device
+    at_model = list(clips)
+    for r, idx in groups.items():
+        for i, y in zip(idx, _resample_group([clips[i] for i in idx], r, model_rate, device, max_batch)):
+            at_model[i] = y
+    out = denoise_batch(model, at_model, max_batch, budget_samples, max_waste)
+    for r, idx in groups.items():
+        for i, y in zip(idx, _resample_group([out[i] for i in idx], model_rate, r, device, max_batch)):
+            out[i] = y[:clips[i].shape[0]]
     return out

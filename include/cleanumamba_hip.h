@@ -863,6 +863,34 @@ int cum_dec7_fwd_ragged(int32_t dtype, int64_t M, int32_t pitch, int32_t valid, 
                         const void *u, const void *w1p, const float *b1p, const float *wt, const float *bt, void *out,
                         int64_t zero_tail, void *stream);
 
+/* ---- sample-rate conversion of a ragged batch (csrc/resample.hip; util/resample.py) -------------------
+ * The reference has no resampler: it drops the rate torchaudio.load returns (src/util/dataset.py:203).  For
+ * rate_in -> rate_out with g = gcd, up = rate_out / g, down = rate_in / g and the n_taps = 2H + 1 taps h (odd count,
+ * symmetric, sum up):   y[m] = sum_{j < K} x[n_hi - j] h[r + j up],  c = m down + H, r = c mod up, n_hi = c / up,
+ * K = ceil(n_taps / up), samples outside the signal zero.  One f32 fma chain per output, j ascending: its order depends
+ * on (m, up, down, H) alone.
+ *
+ * cum_resample_tile: outputs one workgroup produces.
+ * cum_resample_ragged: one launch for `batch` rows of x (int16 PCM x 2^-15 with src_i16 = 1, or f32), in_pitch elements
+ *   apart, row b holding len[b] samples (device i32[batch], clamped into [0, lmax] inside the kernel).  table: the taps
+ *   as the polyphase table [up][table_pitch] f32 on the device, table[r][j] = h[r + j up], zero behind the taps;
+ *   table_pitch >= K and a multiple of 4.  origin: device i64[batch][2] or NULL (zeros) -- the absolute input position
+ *   of x_b[0] and the absolute output position of y_b[0], so that the same launch computes outputs [m0, m1) of a longer
+ *   signal from a window of it.  Inputs before position 0 are zero.  With ends != 0 the signal of row b ends at
+ *   origin + len[b] and the row gets outputs up to ceil((in0 + len) up / down); with ends == 0 only the outputs no
+ *   later input can change, max(0, ceil(((in0 + len) up - H) / down)), are written.  Either count is taken from out0
+ *   and capped at max_out.  y: f32 rows out_pitch apart; nothing is written behind a row's count, nothing is read
+ *   behind len[b].  Needs no workspace.
+ *   CUM_EINVAL before any launch: src_i16 not 0 / 1, batch outside [1, 65534], up or down outside [1, 1024], an even
+ *   tap count, K up < n_taps, table_pitch < K or not a multiple of 4, a null table / len / y (x may be NULL with
+ *   lmax = 0), a negative pitch or length, a pitch below its length, a misaligned pointer (table 16 bytes, origin 8,
+ *   f32 and i32 4, int16 2), or a ratio whose tile span (tile down / up + K samples) exceeds 48 KB of LDS. */
+int32_t cum_resample_tile(void);
+int cum_resample_ragged(int32_t src_i16, const void *x, int32_t batch, int64_t lmax, int64_t in_pitch, const int32_t *len,
+                        const int64_t *origin, int32_t ends, int32_t up, int32_t down, int32_t n_taps, int32_t K,
+                        const float *table, int32_t table_pitch, float *y, int64_t out_pitch, int64_t max_out,
+                        void *stream);
+
 #ifdef __cplusplus
 }
 #endif
