@@ -19,8 +19,6 @@ Differences from the reference, on purpose:
     bottleneck) is supported: mamba_ssm/modules/mamba2.py, csrc/ssd.hip.
 """
 import os
-import warnings
-import time
 import weakref
 from functools import partial
 
@@ -31,11 +29,10 @@ import torch.nn.functional as F
 
 from ..mamba_ssm.models.mixer_seq_simple import _init_weights, create_block
 from ..mamba_ssm.ops import layernorm as _ln
-from ..mamba_ssm.utils.generation import InferenceParams
 from ..util.util import weight_scaling_init
 from .. import hip
 from . import convstack as cs
-from . import hopplan
+from . import streaming
 from .layers import Activation
 
 
@@ -131,38 +128,31 @@ class CleanUMamba(nn.Module):
         # True: after the first hop of a stream the (launch-bound, ~100 tiny kernels) hop is captured once in a
         # hipGraph and replayed; stream state lives in static buffers updated in place.
         self.use_hop_graph = True
-        # True: streaming hops run on the fused GEMM kernels (_denoise_frame_fused); False: torch modules with
-        # per-layer encoder caches (_denoise_frame, the reference's structure)
+        # True: streaming hops run on the fused GEMM kernels (streaming.fused_hop); False: torch modules with
+        # per-layer encoder caches (streaming.cached_hop, the reference's structure)
         self.use_fused_stream = True
         # True: the fused streaming hop stores activations and runs its GEMMs in bf16 (f32 accumulate; the Mamba
         # steps and all stream state stay f32).  Off by default: the hop then matches ``forward`` to 1e-4.
         self.stream_bf16 = False
+        # True: behind a stream's first frame every hop of a call runs in ONE launch (csrc/hop.hip), where it covers the model
+        self.use_hop_kernel = True
+        # True: after a stream's first frame the fused hop computes only the new rows of every layer; False: whole windows
+        self.stream_incremental = True
+        # fewest streams for which the fused hop is taken over the cached one
+        self.fused_min_streams = 1
 
-        # streaming state
+        # streaming: timing counters here, everything else in ``stream`` (network/streaming.py)
         self.total_time = 0
         self.cat_time = 0
         self.frames = 0                 # frames denoised since reset_time_per_frame(): only for time_per_frame
-        self._std_frames = 0            # frames of the CURRENT stream: denominator of the running input std
-        self.input_std = 0
-        self.pending = torch.zeros(self.channels_input, 0, dtype=self.dtype, device=device)
         self.frame_length = self.valid_length(1)
-        self.inference_params = None
-        self.encoder_decoder_state = {}
+        self.stream = streaming.Stream(torch.zeros(self.channels_input, 0, dtype=self.dtype, device=device))
 
     def __getstate__(self):
-        state = self.__dict__.copy()
+        state = self.__dict__.copy()        # (``stream`` leaves out what it cannot carry itself)
         state.pop("_pack_plans", None)      # device-side caches of packed weights are rebuilt on demand
-        state.pop("_plist", None)
-        state.pop("_wv_call", None)
-        state.pop("_hop_graph", None)       # captured hipGraph of the streaming hop
         state.pop("_hop_plan", None)        # packed weights / plan of the one-launch hop
-        state.pop("_hop_kernel_why", None)
         state.pop("_stream_pools", None)    # (weak references to the stream pools of this model)
-        if state.pop("_hop_state", None) is not None:
-            # a live stream of the one-launch hop keeps its state in the plan's device blocks, which are not pickled: the
-            # copy starts a fresh stream (what is left in the per-layer fields is the first frame's state, stale by now)
-            state["pending"] = state["pending"][:, :0].clone()
-            state.update(inference_params=None, encoder_decoder_state={}, input_std=0, _std_frames=0)
         return state
 
     # ------------------------------------------------------------------ geometry
@@ -452,17 +442,7 @@ class CleanUMamba(nn.Module):
     def invalidate_packed_weights(self):
         """Drop the cached GEMM-layout copies of the conv weights (rebuilt on the next forward)."""
         self.__dict__.pop("_pack_plans", None)
-        self.__dict__.pop("_hop_graph", None)
-        self.__dict__.pop("_hop_plan", None)
-        self.__dict__.pop("_hop_kernel_why", None)      # (shapes may have changed: ask again)
-        self.__dict__.pop("_plist", None)
-        self.__dict__.pop("_wv_call", None)
-        hs = self.__dict__.get("_hop_state")
-        if hs is not None:                              # a live stream of the one-launch hop holds its own weight blob:
-            hs["plan_weights"] = None                   # re-pack it on the next call (``param.data`` writes are invisible
-                                                        # to _weights_version)
-        for pool in self.__dict__.get("_stream_pools", ()):
-            pool.invalidate_packed_weights()            # (so do the stream pools)
+        self.stream.drop_caches(self)                   # (and the hop plan, the hop graph, the stream pools' blobs)
 
     # ----------------------------------------------------------------- streaming
     def reset_time_per_frame(self):
@@ -481,21 +461,9 @@ class CleanUMamba(nn.Module):
                 for i, layer in enumerate(self.tsfm_Mamba_layers)}
 
     def reset_stream(self):
-        """Forget all streaming state (pending samples, conv tails, Mamba states)."""
+        """Forget all streaming state (pending samples, conv tails, Mamba states): a fresh stream state replaces it."""
         dev = self.tsfm_conv1.weight.device
-        self.pending = torch.zeros(self.channels_input, 0, dtype=self.dtype, device=dev)
-        self.inference_params = None
-        self.encoder_decoder_state = {}
-        self.input_std = 0
-        self._std_frames = 0
-        self.__dict__.pop("_hop_graph", None)    # it captured the addresses of the dropped state buffers
-        self.__dict__.pop("_hop_state", None)    # state blocks of the one-launch hop (csrc/hop.hip)
-
-    @torch.no_grad()
-    def flush(self):
-        """Emit the samples still pending: pad one frame of zeros, run it through the SAME stream
-        state (so the decoder overlap of the tail is kept), then reset the stream."""
-        return self.flush_batch()
+        self.stream.state = streaming.StreamState(torch.zeros(self.channels_input, 0, dtype=self.dtype, device=dev))
 
     @torch.no_grad()
     def feed(self, noisy_input):
@@ -503,9 +471,8 @@ class CleanUMamba(nn.Module):
         (interface of src/network/CleanUMamba.py:370-418)."""
         if noisy_input.dim() != 2:
             raise ValueError("input should be two dimensional.")
-        C, _ = noisy_input.shape
-        if C != 1:
-            raise ValueError(f"Expected 1 channel, got {C}")
+        if noisy_input.shape[0] != 1:
+            raise ValueError(f"Expected 1 channel, got {noisy_input.shape[0]}")
         return self.feed_batch(noisy_input)
 
     @torch.no_grad()
@@ -514,99 +481,12 @@ class CleanUMamba(nn.Module):
         signal, tail included.  ``forward`` zero-pads the signal to ``valid_length`` and its last
         ``frame_length - total_stride`` output samples come from the transposed convs' overhang of the LAST real
         frame -- no later frame exists.  So flush (1) pads the stream with exactly the zeros ``forward`` would add
-        and runs the hops of the frames that exist, then (2) drains the decoder (``_drain``): the per-layer overlap
-        tails and the not-yet-consumed encoder rows are pushed through the remaining decoder layers with no new
-        frame.  (The reference's flush() feeds one whole frame of zeros after clearing the decoder state,
-        src/network/CleanUMamba.py:358-368 -- SURVEY fact 9: ~70 % error on the tail.)"""
-        S, pending_length = self.pending.shape[0], self.pending.shape[1]
-        dev = self.pending.device
-        consumed = getattr(self, "_std_frames", 0) * self.total_stride
-        if consumed + pending_length == 0:
-            return torch.zeros(S, 0, device=dev)
-        target = self.valid_length(consumed + pending_length)
-        pad = torch.zeros(S, target - consumed - pending_length, device=dev, dtype=self.pending.dtype)
-        head = self.feed_batch(pad)      # the frames forward() has: they count as timed frames like any other
-        if S == 0:
-            self.reset_stream()
-            return head.new_zeros(0, pending_length)
-        out = torch.cat([head, self._drain().to(head.dtype)], 1)[:, :pending_length]
-        self.reset_stream()              # the next clip starts a fresh stream: its running std starts over too
-        return out
+        and runs the hops of the frames that exist, then (2) drains the decoder (``streaming.drain``): the per-layer
+        overlap tails and the not-yet-consumed encoder rows are pushed through the remaining decoder layers with no new
+        frame.  (The reference's flush(), src/network/CleanUMamba.py:358-368, loses the tail: SURVEY fact 9.)"""
+        return streaming.flush_batch(self)
 
-    def _drain(self, rows=None, std=None):
-        """Output samples behind the last hop, (S, frame_length - total_stride): what ``forward`` produces there.
-        Decoder layer j still holds 2 overhang rows of its transposed conv (``dec{j}``, bias excluded) and encoder
-        layer i holds ``2^(E-i) - 2`` output rows no hop has consumed as skips yet; layer j maps its
-        ``2^(j+1) - 2`` trailing input rows to ``2^(j+2) - 2`` trailing output rows.
-        ``rows`` / ``std``: drain these streams instead of the model's own (a stream pool's closing slots: the layout of
-        hopplan.HopPlan.export_rows, and their running std, (S, 1), with normalize_input)."""
-        if rows is None:
-            hs = self.__dict__.get("_hop_state")
-            if hs is not None:                                  # the one-launch hop owns the state: bring it back
-                self.encoder_decoder_state = hs["plan"].export_state(self, hs["state"])
-            state = self.encoder_decoder_state
-            S, dev = self.pending.shape[0], self.pending.device
-            std = self.input_std
-        else:
-            state = rows
-            S, dev = rows["enc0"].shape[0], rows["enc0"].device
-        E = self.encoder_n_layers
-
-        rows_layout = state["enc0"].dim() == 2                 # fused hop: 2-D row buffers; cached hop: (S, C, T)
-
-        def trailing_skip(i):
-            t = state[f"enc{i}"]
-            hop = self.total_stride // self.stride ** (i + 1)
-            if not rows_layout:                                # cached path: (S, C, rows not yet consumed)
-                return t.float()
-            C = self.encoder[i][2].weight.shape[0] // 2        # fused path: row buffer of the frame's whole window
-            T = self.frame_length
-            for _ in range(i + 1):
-                T = (T - self.kernel_size) // self.stride + 1
-            return cs.from_rows(t, cs.Geo(S, T, C))[..., hop:].float()
-
-        def tail(j):
-            t = state[f"dec{j}"]
-            if rows_layout:                                    # fused path: (S, 2, Cp) channels-last
-                return t.transpose(1, 2)[:, :self.decoder[j][2].weight.shape[1]].float()
-            return t.float()                                   # cached path: (S, C, 2)
-
-        from ..mamba_ssm.modules.mamba_simple import _proj       # cum_gemm_nt on padded operands: any channel count
-        if dev.type == "cuda":
-            # the drain's GEMM operands come out of the model's pack plan: re-pack if a parameter changed since the last
-            # per-layer hop (the one-launch hop packs its own blob and never touches the plan)
-            self._activate_pack_plan(torch.float32)
-
-        def linear_ct(w2d, x):
-            """(O, C) x (S, C, T) -> (S, O, T) on the library's GEMM (a handful of columns per stream: rows = S * T)."""
-            return _proj(x.transpose(1, 2).contiguous(), w2d.contiguous()).transpose(1, 2)
-
-        def conv_t(g, conv):
-            """ConvTranspose1d on a handful of columns as one GEMM per tap + K strided adds (the few-column shapes of the
-            drain are not worth a MIOpen solver search, and small transposed convs abort in MIOpen on some boxes)."""
-            w, K, S = conv.weight.float(), self.kernel_size, self.stride           # (Cin, Cout, K)
-            T = g.shape[-1]
-            out = conv.bias.float().view(1, -1, 1).repeat(g.shape[0], 1, (T - 1) * S + K)
-            for k in range(K):
-                out[..., k:k + (T - 1) * S + 1:S] += linear_ct(w[:, :, k].t(), g)
-            return out
-
-        x = None
-        for j, dec in enumerate(self.decoder):
-            if j == 0:
-                y = tail(0) + dec[2].bias.float().view(1, -1, 1)
-            else:
-                x = x + trailing_skip(E - 1 - j)[..., :x.shape[-1]]
-                pre = linear_ct(dec[0].weight.float().squeeze(-1), x) + dec[0].bias.float().view(1, -1, 1)
-                y = conv_t(dec[1](pre), dec[2])
-                y[..., :self.stride] += tail(j)
-            if j != E - 1:
-                y = torch.relu(y)
-            x = y
-        out = x[:, 0]
-        if self.normalize_input:
-            out = out * std
-        return out
+    flush = flush_batch     # (one stream or many: interface of src/network/CleanUMamba.py:358-368)
 
     @torch.no_grad()
     def feed_batch(self, noisy_input):
@@ -616,106 +496,7 @@ class CleanUMamba(nn.Module):
         src/network/CleanUMamba.py:375-381)."""
         if noisy_input.dim() != 2:
             raise ValueError("input should be two dimensional: (streams, samples)")
-        S = noisy_input.shape[0]
-        if self.pending.shape[0] != S or self.pending.device != noisy_input.device:
-            if self.pending.shape[1] != 0 or self.inference_params is not None:
-                if self.pending.shape[0] != S:
-                    raise ValueError(f"stream count changed from {self.pending.shape[0]} to {S}; call reset_stream()")
-            self.pending = torch.zeros(S, 0, dtype=noisy_input.dtype, device=noisy_input.device)
-        if self.inference_params is None:
-            self.inference_params = InferenceParams(max_seqlen=1, max_batch_size=S,
-                                                    key_value_memory_dict=self.allocate_inference_cache(S, 1),
-                                                    seqlen_offset=1)
-        begin = time.time()
-        total_stride = self.total_stride
-        self.pending = torch.cat([self.pending, noisy_input], dim=1)
-        denoised_frames = []
-        self.__dict__["_wv_call"] = None            # weights cannot change inside one call: checked on its first hop only
-        while self.pending.shape[1] >= self.frame_length:
-            if S == 0:                                  # no stream: only the bookkeeping of the hops that would have run
-                n_hops = (self.pending.shape[1] - self.frame_length) // total_stride + 1
-                self.frames += n_hops
-                self._std_frames = getattr(self, "_std_frames", 0) + n_hops
-                denoised_frames.append(self.pending.new_zeros(0, n_hops * total_stride))
-                self.pending = self.pending[:, n_hops * total_stride:]
-                break
-            hs = self._hop_kernel_state()
-            if hs is not None:
-                # every remaining hop of this call in ONE launch (csrc/hop.hip): a workgroup per stream walks them
-                n_hops = (self.pending.shape[1] - self.frame_length) // total_stride + 1
-                out = torch.empty(S, n_hops * total_stride, dtype=torch.float32, device=self.pending.device)
-                hs["plan"].run(hs["state"], self.pending, out, n_hops)
-                self.frames += n_hops
-                self._std_frames += n_hops
-                if self.normalize_input:
-                    self.input_std = hs["state"][:, 0:1]         # the kernel keeps the running std in the state block
-                denoised_frames.append(out)
-                self.pending = self.pending[:, n_hops * total_stride:]
-                break
-            self.frames += 1
-            self._std_frames = getattr(self, "_std_frames", 0) + 1
-            frame = self.pending[:, :self.frame_length]
-            if self.normalize_input:
-                # running mean of the per-frame std, per stream (src/network/CleanUMamba.py:399-401).  The mean runs
-                # over the frames of THIS stream (the reference shares one counter with time_per_frame and never
-                # resets either; a stream here ends at flush(), so the counter of its running mean ends there too)
-                n = self._std_frames
-                self.input_std = (frame.std(dim=1, keepdim=True) + 1e-3) / n + (1 - 1 / n) * self.input_std
-                frame = frame / self.input_std
-            out = self._hop(frame)[:, :total_stride]
-            if self.normalize_input:
-                out = out * self.input_std
-            denoised_frames.append(out)
-            self.pending = self.pending[:, total_stride:]
-        self.total_time += time.time() - begin
-        if denoised_frames:
-            return torch.cat(denoised_frames, 1)
-        return torch.zeros(S, 0, device=noisy_input.device)
-
-    def _hop_kernel_state(self):
-        """{"plan", "state"} once the one-launch hop (csrc/hop.hip) can take this stream's hops, else None: it needs a
-        model the plan supports (hopplan.unsupported_reason), f32 streams on the GPU, and the state the per-layer path
-        leaves after the FIRST frame of the streams (whole windows, no history), which is converted here once."""
-        hs = self.__dict__.get("_hop_state")
-        if hs is not None:
-            wv = self.__dict__.get("_wv_call")
-            if wv is None:
-                wv = self.__dict__["_wv_call"] = self._weights_version()
-            if hs["plan_weights"] != wv:                    # weights changed under a live stream: re-pack them
-                try:
-                    hs["plan"], hs["plan_weights"] = hopplan.HopPlan(self), wv
-                except ValueError as exc:                   # (same guard as at creation; here the stream state already
-                    # lives in the old plan's layout, which the per-layer hop cannot take over mid-stream)
-                    raise RuntimeError("the weights changed under a live stream into a model the one-launch hop cannot "
-                                       f"run ({exc}); flush() / reset_stream() before changing them") from exc
-            return hs
-        if not getattr(self, "use_hop_kernel", True) or getattr(self, "stream_bf16", False) \
-                or not getattr(self, "stream_incremental", True):
-            return None
-        state = self.encoder_decoder_state
-        if not state or "enc0" not in state or state["enc0"].dim() != 2 or not self.pending.is_cuda \
-                or self.pending.dtype != torch.float32 or self.pending.stride(1) != 1:
-            return None
-        why = self.__dict__.get("_hop_kernel_why")
-        if why is None:
-            why = self.__dict__["_hop_kernel_why"] = hopplan.unsupported_reason(self) or ""
-        if why:
-            return None
-        wv = self._weights_version()
-        self.__dict__["_wv_call"] = wv
-        cached = self.__dict__.get("_hop_plan")
-        if cached is None or cached[0] != wv:
-            try:
-                cached = (wv, hopplan.HopPlan(self))
-            except ValueError as exc:                       # e.g. LDS budget: stay on the per-layer path
-                self.__dict__["_hop_kernel_why"] = str(exc)
-                return None
-            self.__dict__["_hop_plan"] = cached
-        plan = cached[1]
-        hs = {"plan": plan, "plan_weights": wv, "state": plan.import_state(self, self.pending.shape[0])}
-        self.__dict__["_hop_state"] = hs
-        self.__dict__.pop("_hop_graph", None)
-        return hs
+        return streaming.feed_batch(self, noisy_input)
 
     def stream_pool(self, capacity):
         """A pool of ``capacity`` stream slots on this model (network/streampool.py): streams that join, feed any number of
@@ -730,234 +511,21 @@ class CleanUMamba(nn.Module):
     @property
     def hop_kernel_status(self):
         """"active" while the one-launch hop owns the stream state, else why not ("off", "first frame pending", reason)."""
-        if self.__dict__.get("_hop_state") is not None:
+        if self.stream.state.kernel is not None:
             return "active"
-        if not getattr(self, "use_hop_kernel", True):
+        if not streaming.switch(self, "use_hop_kernel"):
             return "off"
-        return self.__dict__.get("_hop_kernel_why") or "first frame pending"
+        return self.stream.why or "first frame pending"
 
     @property
     def hop_graph_status(self):
         """"off" (disabled), "pending" (no hop captured yet), "captured", or "failed: <error>" (hops run eagerly)."""
-        if not getattr(self, "use_hop_graph", False):
+        if not streaming.switch(self, "use_hop_graph"):
             return "off"
-        hg = self.__dict__.get("_hop_graph")
+        hg = self.stream.state.graph
         if hg is None:
             return "pending"
-        return "failed: " + hg["error"] if hg.get("failed") else "captured"
-
-    def _weights_version(self):
-        # in-place updates of any parameter (optimizer steps, load_state_dict) bump these counters.  The walk over the
-        # module tree costs ~60 us, a whole streaming hop of one stream ~450: the parameter list is cached (and keyed
-        # by the identity of the Parameter objects, which pruning / load_pruned_state_dict replace).
-        plist, age = self.__dict__.get("_plist", (None, 0))
-        if plist is None or age >= 64:              # re-walk now and then: foreign code may swap Parameter objects
-            plist, age = list(self.parameters()), 0
-        self.__dict__["_plist"] = (plist, age + 1)
-        # ... and the one non-parameter input of the compiled hop plan: a plan made with normalize_input off has no
-        # running-std op, and was silently reused after the flag was switched on (found by the config-5-size test)
-        return (sum(p._version for p in plist), bool(self.normalize_input))
-
-    def _hop(self, frame):
-        """Eager first hop (it creates the state buffers), hipGraph replay afterwards."""
-        denoise = self._denoise_frame
-        if frame.is_cuda and getattr(self, "use_fused_stream", True) and getattr(self, "use_fused_convs", True) \
-                and cs.supported(self) \
-                and frame.shape[1] == self.valid_length(1) and frame.dtype == torch.float32 \
-                and frame.shape[0] >= getattr(self, "fused_min_streams", 1):
-            # (single streams too: 0.45 ms per hop against 0.52 ms on the cached path)
-            denoise = self._denoise_frame_fused
-        if not (getattr(self, "use_hop_graph", False) and frame.is_cuda and self.encoder_decoder_state):
-            return denoise(frame)
-        hg = self.__dict__.get("_hop_graph")
-        wv = self.__dict__.get("_wv_call")
-        if wv is None:
-            wv = self.__dict__["_wv_call"] = self._weights_version()
-        if hg is not None and not hg.get("failed") and hg.get("weights") != wv:
-            hg = None          # the graph replays kernels on the weight copies of its capture: capture again
-        if hg is None:
-            hg = {"failed": False}
-            try:
-                static_in = frame.clone()
-                stream = torch.cuda.Stream(device=frame.device)
-                stream.wait_stream(torch.cuda.current_stream())
-                with torch.cuda.stream(stream):      # warm-up on a side stream, as graph capture requires
-                    saved = {k: v.clone() for k, v in self.encoder_decoder_state.items()}
-                    cache = {k: tuple(t.clone() for t in v)
-                             for k, v in self.inference_params.key_value_memory_dict.items()}
-                    denoise(static_in, True)
-                    # undo the warm-up's state changes
-                    for k, v in saved.items():
-                        self.encoder_decoder_state[k].copy_(v)
-                    for k, v in cache.items():
-                        for dst, src in zip(self.inference_params.key_value_memory_dict[k], v):
-                            dst.copy_(src)
-                torch.cuda.current_stream().wait_stream(stream)
-                graph = torch.cuda.CUDAGraph()
-                with torch.cuda.graph(graph):
-                    static_out = denoise(static_in, True)
-                # capture does not execute: state is untouched
-                hg.update(graph=graph, static_in=static_in, static_out=static_out, shape=tuple(frame.shape),
-                          weights=wv)
-            except Exception as exc:                 # noqa: BLE001 - capture is an optimisation; stay eager
-                hg = {"failed": True, "error": repr(exc)}
-                warnings.warn(f"CleanUMamba: hipGraph capture of the streaming hop failed ({exc!r}); this stream "
-                              "runs its hops eagerly (2-4x slower).  See model.hop_graph_status.")
-            self.__dict__["_hop_graph"] = hg
-        if hg.get("failed") or hg["shape"] != tuple(frame.shape):
-            return denoise(frame)
-        hg["static_in"].copy_(frame)
-        hg["graph"].replay()
-        return hg["static_out"].clone()
-
-    def _denoise_frame_fused(self, frame, inplace=True):
-        assert inplace, "the fused hop always updates its stream state in place"
-        with cs.small_m_gemms():
-            return self._denoise_frame_fused_impl(frame)
-
-    def _denoise_frame_fused_impl(self, frame, state=None, inference_params=None):
-        """One hop on the fused GEMM kernels, same arithmetic as _denoise_frame.  Every encoder layer keeps a persistent
-        window of its output (the decoder's skips read its oldest rows); the first hop of a stream computes the
-        windows whole (S independent clips of valid_length(1) samples), later hops compute only the hop's new rows
-        from the newest rows of the window below (cum_stream_tail_rows) and append them (cum_stream_window_update),
-        so older activations keep the input scaling of the hop that produced them, as with the reference's per-layer
-        caches (``stream_incremental = False`` recomputes the windows every hop); a decoder layer is
-        1x1+GLU GEMM, transposed-conv GEMM and one overlap-add kernel (cum_stream_overlap_add) that also applies
-        ReLU, adds the skip and keeps the tail for the next hop.
-        ``state`` / ``inference_params``: run on these streams instead of the model's own (a stream pool's first frames)."""
-        S, E, dev = frame.shape[0], self.encoder_n_layers, frame.device
-        dt = torch.bfloat16 if getattr(self, "stream_bf16", False) else torch.float32
-        self._activate_pack_plan(dt)
-        geo = cs.Geo(S, frame.shape[1], self.encoder[0][0].weight.shape[1])
-        if state is None:
-            state, inference_params = self.encoder_decoder_state, self.inference_params
-        lib = hip.lib()
-        # After the first hop of a stream only the hop's new rows of every layer are computed: layer i emits
-        # n = total_stride >> (i + 1) rows from the 2 n + 2 newest rows of its input (2 carried + 2 n new ones).
-        incremental = state.get("enc0") is not None and getattr(self, "stream_incremental", True)
-        buf = None if incremental else cs.to_rows(frame.unsqueeze(1), geo, dt)
-        dc = hip.dtype_code(dt)
-        enc_geos, outs, n_new = [], [], self.total_stride
-        for i, enc in enumerate(self.encoder):
-            T1 = (geo.T - self.kernel_size) // self.stride + 1
-            g_mid = cs.Geo(S, T1, enc[0].weight.shape[0])
-            g_out = cs.Geo(S, T1, enc[2].weight.shape[0] // 2)
-            n_new //= self.stride
-            window = state.get(f"enc{i}")
-            if incremental:
-                t_in = self.stride * n_new + self.kernel_size - self.stride
-                g_cin = cs.Geo(S, t_in, geo.C)
-                xin = state.get(f"encin{i}")
-                if xin is None:                   # persistent: its framing rows are zeroed once
-                    xin = state[f"encin{i}"] = g_cin.new(dt, dev, zero=True)
-                if i == 0:
-                    g_cin.rows(xin)[:, :t_in, :1] = frame[:, frame.shape[1] - t_in:].unsqueeze(-1).to(dt)
-                # (deeper layers: the window update of the layer below has already written xin)
-                g_cm, g_co = cs.Geo(S, n_new, g_mid.C), cs.Geo(S, n_new, g_out.C)
-                y1 = cs._conv_relu_fwd(xin, enc[0].weight, enc[0].bias, g_cin, g_cm)
-                fresh, _ = cs._glu_fwd(y1, enc[2].weight, enc[2].bias, g_cm, g_co, False)
-                nxt = state.get(f"encin{i + 1}")   # the next layer's compact input: 2 carried rows + the new ones
-                with torch.cuda.device(dev):        # in place, one launch (windows are far below 8192 kept rows)
-                    hip.check(lib.cum_stream_window_update(dc, S, g_out.T, n_new, g_out.Cp, hip.ptr(window[1:]),
-                                                           hip.ptr(fresh[1:]), g_out.P, g_co.P, g_out.T - n_new,
-                                                           None, None if nxt is None else hip.ptr(nxt[1:]),
-                                                           n_new + 4, hip.stream_ptr()))
-            else:
-                y1 = cs._conv_relu_fwd(buf, enc[0].weight, enc[0].bias, geo, g_mid)
-                fresh, _ = cs._glu_fwd(y1, enc[2].weight, enc[2].bias, g_mid, g_out, False)
-                # the layer's window keeps older rows as the hop that produced them left them (per-layer caches of
-                # the reference, :425-447): only the n_new newest rows of the recomputed window are taken over
-                if window is None:
-                    window = state[f"enc{i}"] = fresh
-                    # compact input of the incremental hops; allocated here so that the captured hop allocates nothing
-                    t_in = self.stride * n_new + self.kernel_size - self.stride
-                    state[f"encin{i}"] = cs.Geo(S, t_in, geo.C).new(dt, dev, zero=True)
-                else:
-                    with torch.cuda.device(dev):
-                        hip.check(lib.cum_stream_window_update(dc, S, g_out.T, n_new, g_out.Cp, hip.ptr(window[1:]),
-                                                               hip.ptr(fresh[1:]), g_out.P, g_out.P, 0, None, None, 0,
-                                                               hip.stream_ptr()))
-            enc_geos.append((geo, g_mid, g_out))
-            outs.append(window)
-            buf, geo = window, g_out
-        x, _ = self._bottleneck(cs.from_rows(outs[-1], geo).float(), inference_params=inference_params,
-                                pointwise_as_linear=True)                                                     # (S, C, 1)
-        L = x.shape[-1]
-        x = x + cs.from_rows(outs[-1], geo)[..., :L].float()
-        g_in = cs.Geo(S, L, x.shape[1])
-        ubuf = cs.to_rows(x, g_in, dt)
-        for j, dec in enumerate(self.decoder):
-            last = j == E - 1
-            g_glu = cs.Geo(S, L, dec[0].weight.shape[0] // 2)
-            g_ct = cs.Geo(S, 2 * L + 2, dec[2].weight.shape[1])
-            gbuf, _ = cs._glu_fwd(ubuf, dec[0].weight, dec[0].bias, g_in, g_glu, False)
-            ybuf, _ = cs._convt_fwd(gbuf, dec[2].weight, dec[2].bias, None, g_glu, g_ct, False)
-            tail = state.get(f"dec{j}")
-            if tail is None:                       # first hop of the stream: nothing to overlap with
-                tail = state[f"dec{j}"] = torch.zeros(S, 2, g_ct.Cp, dtype=dt, device=dev)
-            g_next = cs.Geo(S, 2 * L, g_ct.C)
-            # persistent between hops (the kernel rewrites every data row, the framing rows stay zero) -- except the
-            # last layer's, which is handed to the caller
-            nbuf = None if last else state.get(f"decbuf{j}")
-            if nbuf is None or nbuf.dtype != dt:
-                nbuf = g_next.new(dt, dev, zero=True)
-                if not last:
-                    state[f"decbuf{j}"] = nbuf
-            skip, skip_pitch = None, 0
-            if not last:
-                sbuf, g_skip = outs[E - 2 - j], enc_geos[E - 2 - j][2]
-                assert g_skip.C == g_ct.C and g_skip.T >= 2 * L
-                skip, skip_pitch = sbuf[1:], g_skip.P
-            with torch.cuda.device(dev):
-                hip.check(lib.cum_stream_overlap_add(
-                    hip.dtype_code(dt), S, 2 * L, g_ct.Cp, g_ct.C, hip.ptr(ybuf[1:]), g_ct.P, hip.ptr(tail),
-                    hip.ptr(dec[2].bias.float()), hip.ptr(skip), skip_pitch, hip.ptr(nbuf[1:]), g_next.P,
-                    int(not last), hip.stream_ptr()))
-            ubuf, g_in, L = nbuf, g_next, 2 * L
-        return cs.from_rows(ubuf, g_in)[:, 0].float()
-
-    def _denoise_frame(self, frame, inplace=False):
-        """One hop: frame (S, frame_length) -> (S, >= total_stride) samples.  Encoder outputs that overlap
-        the previous frame are cached per layer; the decoder keeps the last ``stride`` samples of every
-        transposed conv for overlap-add with the next frame."""
-        x = frame.unsqueeze(1)
-        state = self.encoder_decoder_state
-        skip_connections = []
-        hop = self.total_stride
-        for i, encode in enumerate(self.encoder):
-            hop //= self.stride                      # new outputs of this layer per frame
-            prev = state.get(f"enc{i}")
-            if prev is not None:
-                length = x.shape[2]
-                n_new = (length - self.kernel_size) // self.stride + 1 - prev.shape[-1]
-                x = x[..., length - self.kernel_size - self.stride * (n_new - 1):]
-            x = encode(x)
-            if prev is not None:
-                x = torch.cat([prev, x], -1)
-            if inplace:
-                prev.copy_(x[..., hop:])             # static buffer (hipGraph replay reads it next hop)
-            else:
-                state[f"enc{i}"] = x[..., hop:].clone()
-            skip_connections.append(x)
-
-        x, _ = self._bottleneck(x, inference_params=self.inference_params)
-
-        for i, upsampling_block in enumerate(self.decoder):
-            skip_i = skip_connections[-1 - i]        # deepest first, as in forward()
-            x = x + skip_i[..., :x.shape[-1]]
-            x = upsampling_block[2](upsampling_block[1](upsampling_block[0](x)))
-            prev = state.get(f"dec{i}")
-            tail = x[..., -self.stride:] - upsampling_block[2].bias.view(-1, 1)
-            x = x[..., :-self.stride]
-            if prev is not None:
-                x = torch.cat([x[..., :self.stride] + prev, x[..., self.stride:]], -1)
-            if inplace:
-                prev.copy_(tail)
-            else:
-                state[f"dec{i}"] = tail
-            if i != self.encoder_n_layers - 1:
-                x = upsampling_block[3](x)
-        return x[:, 0]
+        return "failed: " + hg["error"] if hg["failed"] else "captured"
 
     # ------------------------------------------------------------ pruned loading
     def load_pruned_state_dict(self, pruned_state_dict):

@@ -414,16 +414,12 @@ class HopPlan:
             + b.mixer.out_proj.weight.numel() + 3 * b.mixer.A_log.numel() for b in model.tsfm_Mamba_layers)
 
     # ------------------------------------------------------------------ state
-    def import_state(self, model, S, state=None, inference_params=None, input_std=None, frames=None, into=None,
-                     at=None):
-        """State blocks [S, state_stride] from the per-layer path's state right after the first frame of the streams.
-        ``state`` / ``inference_params`` / ``input_std`` / ``frames``: these streams' instead of the model's own (a stream
-        pool's first frames); ``into`` / ``at``: also written to rows ``at`` (device int64) of the block ``into``."""
+    def import_state(self, state, into=None, at=None):
+        """State blocks [S, state_stride] from ``state`` (a streaming.StreamState: per-layer buffers, Mamba states, running
+        std and frame count) right after the first frame of its streams on the fused per-layer path.
+        ``into`` / ``at``: also written to rows ``at`` (device int64) of the block ``into``."""
+        S, old = state.params.max_batch_size, state.layers
         st = torch.zeros(S, self.state_stride, dtype=torch.float32, device=self.device)
-        if state is None:
-            state, inference_params = model.encoder_decoder_state, model.inference_params
-            input_std, frames = model.input_std, model._std_frames
-        old = state
         if old["enc0"].dim() != 2:
             raise RuntimeError("import_state: the first frame must have run on the fused per-layer path")
         T = self.frame_len
@@ -438,20 +434,20 @@ class HopPlan:
         for j, d in enumerate(self.decs):
             tail = st[:, d["tail"]:d["tail"] + 2 * d["cq"]].view(S, 2, d["cq"])
             tail[:, :, :d["cout"]] = old[f"dec{j}"][:, :, :d["cout"]].float()
-        kv = inference_params.key_value_memory_dict
+        kv = state.params.key_value_memory_dict
         for k, b in enumerate(self.blks):
             conv_state, ssm_state = kv[k]
             st[:, b["conv_state"]:b["conv_state"] + b["di"] * b["W"]] = conv_state.reshape(S, -1).float()
             st[:, b["ssm_state"]:b["ssm_state"] + b["di"] * b["N"]] = ssm_state.reshape(S, -1).float()
         if self.hdr["normalize"]:
-            st[:, 0] = input_std.reshape(S).float()
-            st[:, 1] = float(frames)
+            st[:, 0] = state.input_std.reshape(S).float()
+            st[:, 1] = float(state.frames)
         if into is not None:
             into.index_copy_(0, at, st)
         return st
 
     def export_rows(self, st):
-        """The per-layer path's view of the encoder / decoder state of the blocks ``st`` (the layout ``_drain`` reads:
+        """The per-layer path's view of the encoder / decoder state of the blocks ``st`` (the layout ``streaming.drain`` reads:
         unconsumed encoder rows (S, C, 2 n - 2), decoder tails (S, C, 2)); every row at its own ring phase."""
         S = st.shape[0]
         phase = st[:, self.hdr["phase_off"]].long().view(S, 1)
@@ -467,10 +463,10 @@ class HopPlan:
             out[f"dec{j}"] = tail[:, :, :d["cout"]].transpose(1, 2).contiguous()
         return out
 
-    def export_state(self, model, st):
-        """``export_rows``, plus the Mamba states (into the model's inference cache)."""
+    def export_state(self, state, st):
+        """``export_rows``, plus the Mamba states (into the InferenceParams of the streaming.StreamState ``state``)."""
         out = self.export_rows(st)
-        kv = model.inference_params.key_value_memory_dict
+        kv = state.params.key_value_memory_dict
         for k, b in enumerate(self.blks):
             conv_state, ssm_state = kv[k]
             conv_state.copy_(st[:, b["conv_state"]:b["conv_state"] + b["di"] * b["W"]].view_as(conv_state))

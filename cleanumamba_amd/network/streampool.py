@@ -28,7 +28,7 @@ import torch
 from .. import hip
 from . import convstack as cs
 from . import hopplan
-from ..mamba_ssm.utils.generation import InferenceParams
+from . import streaming
 
 _REC = 8        # int32 per record of both tables (csrc/hop.hip: kHopItemInts, kStageRecInts)
 
@@ -76,12 +76,7 @@ class StreamPool:
         if capacity < 1:
             raise ValueError("stream pool: capacity must be >= 1")
         self.model, self.capacity = model, capacity
-        self._wv = model._weights_version()
-        self._stale = False
-        self.plan = hopplan.HopPlan(model)
-        self.hop, self.frame_len, self.device = self.plan.hop, self.plan.frame_len, self.plan.device
-        self.state = torch.zeros(capacity, self.plan.state_stride, dtype=torch.float32, device=self.device)
-        self.hist = torch.zeros(capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32, device=self.device)
+        self._adopt(hopplan.HopPlan(model))
         self._open = np.zeros(capacity, dtype=bool)
         self._pend = np.zeros(capacity, dtype=np.int64)       # samples in hist[slot]
         self._frames = np.zeros(capacity, dtype=np.int64)     # frames run (the first one included)
@@ -124,12 +119,15 @@ class StreamPool:
         except ValueError:
             self._stale = True
             return
-        self.plan, self._wv, self._stale = plan, self.model._weights_version(), False
-        self.hop, self.frame_len = plan.hop, plan.frame_len
-        self.state = torch.zeros(self.capacity, plan.state_stride, dtype=torch.float32, device=self.device)
-        self.hist = torch.zeros(self.capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32,
-                                device=self.device)
+        self._adopt(plan)
         self.reset()
+
+    def _adopt(self, plan):
+        """Take ``plan`` (of the model's current weights) and size zeroed state blocks to it."""
+        self.plan, self._wv, self._stale = plan, streaming.weights_version(self.model), False
+        self.hop, self.frame_len, self.device = plan.hop, plan.frame_len, plan.device
+        self.state = torch.zeros(self.capacity, plan.state_stride, dtype=torch.float32, device=self.device)
+        self.hist = torch.zeros(self.capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32, device=self.device)
 
     def invalidate_packed_weights(self):
         """Re-pack the weight blob on the next call (``CleanUMamba.invalidate_packed_weights`` calls this)."""
@@ -184,7 +182,7 @@ class StreamPool:
             idx = self._index(a[live])
             st = self.state.index_select(0, idx)
             std = st[:, 0:1] if self.plan.hdr["normalize"] else None
-            tail = self.model._drain(rows=self.plan.export_rows(st), std=std)
+            tail = streaming.drain(self.model, self.plan.export_rows(st), std)
             for j, i in enumerate(live):
                 outs[i] = torch.cat([heads[i], tail[j].to(heads[i].dtype)])[:int(pend[i])]
         if a.size:
@@ -203,7 +201,7 @@ class StreamPool:
         return torch.from_numpy(a.astype(np.int64)).pin_memory().to(self.device, non_blocking=True)
 
     def _refresh_weights(self):
-        wv = self.model._weights_version()
+        wv = streaming.weights_version(self.model)
         if wv == self._wv and not self._stale:
             return
         try:
@@ -275,19 +273,8 @@ class StreamPool:
     def _first_frames(self, frame, dst, slot_idx):
         """The first frame of the slots in ``slot_idx`` (k, frame_len) on the per-layer fused path, in a private streaming
         context, as ``feed_batch`` runs a stream's first frame; their state rows go into the pool's block."""
-        model, k = self.model, frame.shape[0]
-        params = InferenceParams(max_seqlen=1, max_batch_size=k, key_value_memory_dict=model.allocate_inference_cache(k, 1),
-                                 seqlen_offset=1)
-        state, std = {}, None
-        if self.plan.hdr["normalize"]:
-            # (CleanUMamba.feed_batch: the running mean of the per-frame std after ONE frame)
-            std = frame.std(dim=1, keepdim=True) + 1e-3
-            frame = frame / std
-        with cs.small_m_gemms():
-            y = model._denoise_frame_fused_impl(frame, state=state, inference_params=params)[:, :self.hop]
-        if std is not None:
-            y = y * std
-        dst.copy_(y)
-        self.plan.import_state(model, k, state=state, inference_params=params, input_std=std, frames=1, into=self.state,
-                               at=slot_idx)
+        state = streaming.StreamState()
+        state.params = streaming.new_params(self.model, frame.shape[0])
+        dst.copy_(streaming.first_frame(self.model, state, frame, streaming.fused_hop))
+        self.plan.import_state(state, into=self.state, at=slot_idx)
 

@@ -328,9 +328,8 @@ def refuse_live_streams(models, who, doing):
     """Raise if a model has a live ``feed`` stream or a stream pool with open slots: their state has the current widths
     and weights, which pruning (or a calibration trial) changes."""
     for m in models:
-        pending = getattr(m, "pending", None)
-        if m.__dict__.get("_hop_state") is not None or getattr(m, "encoder_decoder_state", None) or \
-                (pending is not None and pending.numel() > 0):
+        stream = getattr(m, "stream", None)
+        if stream is not None and stream.live:
             raise RuntimeError(f"{who}: the model has a live stream whose state has the old widths; flush() or "
                                f"reset_stream() before {doing}")
         for pool in m.__dict__.get("_stream_pools", ()):

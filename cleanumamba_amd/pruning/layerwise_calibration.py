@@ -294,10 +294,8 @@ def _drop_stream_caches(models):
     """Caches the version counters do not reach: the hop plan / graph and the stream pools' weight blobs (no stream is
     live: checked first).  Pack plans and -exp(A_log) follow the counters TrialMask bumps."""
     for m in models:
-        for key in ("_hop_plan", "_hop_graph", "_wv_call"):
-            m.__dict__.pop(key, None)
-        for pool in list(m.__dict__.get("_stream_pools", ())):
-            pool.invalidate_packed_weights()
+        if getattr(m, "stream", None) is not None:
+            m.stream.drop_caches(m)
 
 
 def _zero_grads(model):

@@ -33,7 +33,8 @@ def run(net, kernel, per_call, first_frame_alone):
     while i < L:
         chunks.append(net.feed_batch(x[:, i:i + per_call * hop]))
         i += per_call * hop
-    stds = net.input_std.flatten().tolist() if torch.is_tensor(net.input_std) else net.input_std
+    std = net.stream.state.input_std
+    stds = std.flatten().tolist() if torch.is_tensor(std) else std
     chunks.append(net.flush_batch())
     return torch.cat(chunks, 1), stds
 

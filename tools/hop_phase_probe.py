@@ -31,7 +31,7 @@ with torch.no_grad():
 assert net.hop_kernel_status == "active"
 lib = hip.lib()
 lib.cum_stream_hop_probe_read.restype = ctypes.c_int
-plan = net.__dict__["_hop_plan"][1]
+plan = net.__dict__["_hop_plan"][1]         # (weights version, HopPlan): network/streaming.py keeps it under this key
 n = len(plan.ops)
 buf = (ctypes.c_ulonglong * (n + 1))()
 assert lib.cum_stream_hop_probe_read(buf, n + 1) == 0
