@@ -20,6 +20,10 @@
 //   up > 3 (the 160/441-type ratios, tables of tens of KB): neighbouring outputs use different rows; every lane reads
 //     its own row in place through L2, 16 bytes per load.
 // Results are gathered in LDS and leave as whole coalesced rows.
+#include <string.h>
+
+#include <vector>
+
 #include "common.h"
 
 namespace cum {
@@ -43,6 +47,73 @@ struct RsArgs {
 static inline int64_t rs_span_cap(int64_t up, int64_t down, int64_t K) {
   const int64_t dq = ((up - 1) + (int64_t)(RS_TILE - 1) * down) / up;
   return (K + dq + 16 + 7) / 8 * 8;
+}
+
+// The chains of one tile: outputs o = 0 .. nt - 1, output o = sum_{j < K} x0[dq(o) - j] table[r(o)][j] with
+// c = r0 + o down, dq = c / up, r = c mod up, into ys[o].  x0: LDS, x[n_hi] of the tile's first output.  UP: the up factor
+// on the scalar-tap route (1, 2, 3), 0 for any other.  Both entries' kernels run these, hence the same bits.
+template <int UP>
+__device__ __forceinline__ void rs_tile_chains(const float *__restrict__ x0, const float *__restrict__ table,
+                                               float *__restrict__ ys, const int r0, const int nt, const int up,
+                                               const int down, const int K, const int kp) {
+  if constexpr (UP > 0) {
+    constexpr int PER = RS_TILE / UP;                       // outputs of one phase class
+    constexpr int V = (PER + RS_THREADS - 1) / RS_THREADS;  // ... a lane carries of them
+#pragma unroll 1
+    for (int k = 0; k < UP; ++k) {
+      // outputs o = UP v + k: c = c0 + o down, so r = (r0 + k down) mod UP for all of them and n_hi = q0 + v down + dk
+      const int ck = r0 + k * down, dk = ck / UP, rk = ck - dk * UP;
+      const float *__restrict__ hrow = table + rk * kp;   // wave-uniform: scalar loads
+      const float *xp[V];
+      float acc[V];
+#pragma unroll
+      for (int q = 0; q < V; ++q) {
+        int v = (int)threadIdx.x + q * RS_THREADS;
+        v = v < PER ? v : PER - 1;                          // (a lane without a q-th output recomputes the class's last)
+        xp[q] = x0 + dk + v * down;
+        acc[q] = 0.f;
+      }
+      int j = 0;
+      for (; j + 8 <= K; j += 8) {
+        float h[8];
+#pragma unroll
+        for (int u = 0; u < 8; ++u) h[u] = hrow[j + u];
+#pragma unroll
+        for (int u = 0; u < 8; ++u)
+#pragma unroll
+          for (int q = 0; q < V; ++q) acc[q] = __builtin_fmaf(xp[q][-j - u], h[u], acc[q]);
+      }
+      for (; j < K; ++j) {
+        const float h = hrow[j];
+#pragma unroll
+        for (int q = 0; q < V; ++q) acc[q] = __builtin_fmaf(xp[q][-j], h, acc[q]);
+      }
+#pragma unroll
+      for (int q = 0; q < V; ++q) {
+        const int v = (int)threadIdx.x + q * RS_THREADS;
+        if (v < PER) ys[UP * v + k] = acc[q];               // (slots at or behind nt are filled and never stored)
+      }
+    }
+  } else {
+    for (int o = threadIdx.x; o < nt; o += RS_THREADS) {
+      const int cc = r0 + o * down;
+      const int dq = cc / up;
+      const int r = cc - dq * up;
+      const float *__restrict__ hrow = table + r * kp;
+      const float *__restrict__ xp = x0 + dq;
+      float acc = 0.f;
+      int j = 0;
+      for (; j + 4 <= K; j += 4) {
+        const rs_float4 h = *reinterpret_cast<const rs_float4 *>(hrow + j);
+        acc = __builtin_fmaf(xp[-j], h[0], acc);
+        acc = __builtin_fmaf(xp[-j - 1], h[1], acc);
+        acc = __builtin_fmaf(xp[-j - 2], h[2], acc);
+        acc = __builtin_fmaf(xp[-j - 3], h[3], acc);
+      }
+      for (; j < K; ++j) acc = __builtin_fmaf(xp[-j], hrow[j], acc);
+      ys[o] = acc;
+    }
+  }
 }
 
 // x: rows of S; origin: [batch][2] = absolute input position of x_b[0], absolute output position of y_b[0] (or null);
@@ -110,64 +181,7 @@ __global__ __launch_bounds__(RS_THREADS) void resample_ragged_kernel(const S *__
   }
   __syncthreads();
   const float *__restrict__ x0 = xs + (a.K - 1) + off;      // x[n_hi] of the tile's first output; output o: x0[dq(o)]
-  if constexpr (UP > 0) {
-    constexpr int PER = RS_TILE / UP;                       // outputs of one phase class
-    constexpr int V = (PER + RS_THREADS - 1) / RS_THREADS;  // ... a lane carries of them
-#pragma unroll 1
-    for (int k = 0; k < UP; ++k) {
-      // outputs o = UP v + k: c = c0 + o down, so r = (r0 + k down) mod UP for all of them and n_hi = q0 + v down + dk
-      const int ck = r0 + k * a.down, dk = ck / UP, rk = ck - dk * UP;
-      const float *__restrict__ hrow = table + rk * a.kp;   // wave-uniform: scalar loads
-      const float *xp[V];
-      float acc[V];
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        int v = (int)threadIdx.x + q * RS_THREADS;
-        v = v < PER ? v : PER - 1;                          // (a lane without a q-th output recomputes the class's last)
-        xp[q] = x0 + dk + v * a.down;
-        acc[q] = 0.f;
-      }
-      int j = 0;
-      for (; j + 8 <= a.K; j += 8) {
-        float h[8];
-#pragma unroll
-        for (int u = 0; u < 8; ++u) h[u] = hrow[j + u];
-#pragma unroll
-        for (int u = 0; u < 8; ++u)
-#pragma unroll
-          for (int q = 0; q < V; ++q) acc[q] = __builtin_fmaf(xp[q][-j - u], h[u], acc[q]);
-      }
-      for (; j < a.K; ++j) {
-        const float h = hrow[j];
-#pragma unroll
-        for (int q = 0; q < V; ++q) acc[q] = __builtin_fmaf(xp[q][-j], h, acc[q]);
-      }
-#pragma unroll
-      for (int q = 0; q < V; ++q) {
-        const int v = (int)threadIdx.x + q * RS_THREADS;
-        if (v < PER) ys[UP * v + k] = acc[q];               // (slots at or behind nt are filled and never stored)
-      }
-    }
-  } else {
-    for (int o = threadIdx.x; o < nt; o += RS_THREADS) {
-      const int cc = r0 + o * a.down;
-      const int dq = cc / a.up;
-      const int r = cc - dq * a.up;
-      const float *__restrict__ hrow = table + r * a.kp;
-      const float *__restrict__ xp = x0 + dq;
-      float acc = 0.f;
-      int j = 0;
-      for (; j + 4 <= a.K; j += 4) {
-        const rs_float4 h = *reinterpret_cast<const rs_float4 *>(hrow + j);
-        acc = __builtin_fmaf(xp[-j], h[0], acc);
-        acc = __builtin_fmaf(xp[-j - 1], h[1], acc);
-        acc = __builtin_fmaf(xp[-j - 2], h[2], acc);
-        acc = __builtin_fmaf(xp[-j - 3], h[3], acc);
-      }
-      for (; j < a.K; ++j) acc = __builtin_fmaf(xp[-j], hrow[j], acc);
-      ys[o] = acc;
-    }
-  }
+  rs_tile_chains<UP>(x0, table, ys, r0, nt, a.up, a.down, a.K, a.kp);
   __syncthreads();
   float *__restrict__ dst = y + (int64_t)b * a.out_pitch + t0;
   for (int o = threadIdx.x; o < nt; o += RS_THREADS) dst[o] = ys[o];
@@ -186,6 +200,81 @@ static void rs_launch(const void *x, const int32_t *len, const int64_t *origin, 
     hipLaunchKernelGGL((resample_ragged_kernel<S, 3>), g, t, lds, st, xr, len, origin, table, y, a);
   else
     hipLaunchKernelGGL((resample_ragged_kernel<S, 0>), g, t, lds, st, xr, len, origin, table, y, a);
+}
+
+// ---- slots: streams of different rates at different positions in one launch (cum_resample_slots) --------------------
+// What the stream pool converts with (network/streampool.py): every slot keeps, per direction, the last
+// inputs an unfinished output may still read.  hist: [capacity][2][hist_pitch] f32 -- TWO rows per slot; a record reads
+// row `parity` and writes the next history to row `1 - parity`, so the workgroups of a record (one per tile of its
+// outputs) never read what one of them writes, in whatever order they run.  The signal a record sees is
+// hist[slot][parity][0, n_hist) ++ x[x_row][0, n_new), its first sample at absolute position in0.
+//
+// Plan p = 8 int32 {up, down, n_taps, K, table_pitch, table_offset, 0, 0}: the polyphase table of the pair starts
+//   table_offset floats into `tables`.
+// Record r = 16 int32 {slot, plan, n_hist, x_row, n_new, n_out, y_row, ends, keep, parity, y_col, 0, in0 lo, in0 hi,
+//   out0 lo, out0 hi}:  y[y_row][y_col + o] = output out0 + o of the signal, o < n_out, and
+//   hist[slot][1 - parity][0, keep) = the last `keep` samples of the signal.
+constexpr int kRsRecInts = 16, kRsPlanInts = 8;
+
+__global__ __launch_bounds__(RS_THREADS) void resample_slots_kernel(const int32_t *__restrict__ recs,
+                                                                   const int32_t *__restrict__ plans,
+                                                                   const float *__restrict__ tables, float *hist,
+                                                                   const int64_t hist_pitch, const float *__restrict__ x,
+                                                                   const int64_t x_pitch, float *__restrict__ y,
+                                                                   const int64_t y_pitch, const int span_cap) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  const int32_t *__restrict__ rec = recs + (int64_t)blockIdx.y * kRsRecInts;      // workgroup-uniform, as all below
+  const int slot = rec[0], n_hist = rec[2], n_new = rec[4], n_out = rec[5], keep = rec[8], parity = rec[9];
+  const int tiles = (n_out + RS_TILE - 1) / RS_TILE;
+  const int tile = blockIdx.x, last = tiles > 0 ? tiles - 1 : 0;
+  if (tile > last) return;
+  const int32_t *__restrict__ pl = plans + (int64_t)rec[1] * kRsPlanInts;
+  const int up = pl[0], down = pl[1], H = (pl[2] - 1) / 2, K = pl[3], kp = pl[4];
+  const float *__restrict__ table = tables + pl[5];
+  const int64_t in0 = *reinterpret_cast<const int64_t *>(rec + 12), out0 = *reinterpret_cast<const int64_t *>(rec + 14);
+  const float *hold = hist + ((int64_t)slot * 2 + parity) * hist_pitch;
+  float *hnew = hist + ((int64_t)slot * 2 + (parity ^ 1)) * hist_pitch;
+  const float *__restrict__ xr = x + (int64_t)rec[3] * x_pitch;
+  const int n = n_hist + n_new;                              // samples of the signal this record holds
+
+  if (tile < tiles) {
+    const int t0 = tile * RS_TILE;
+    const int nt = n_out - t0 < RS_TILE ? n_out - t0 : RS_TILE;
+    const int64_t c0 = (out0 + t0) * down + H;               // >= 0
+    const int64_t q0 = c0 / up;
+    const int r0 = (int)(c0 - q0 * up);
+    const int64_t rel_first = q0 - (K - 1) - in0;            // index in the signal of the oldest sample the tile reads
+    const int dq_last = (r0 + (nt - 1) * down) / up;
+    int need = K + dq_last;                                  // LDS floats the tile reads: [0, need)
+    need = need > span_cap ? span_cap : need;                // (never: span_cap is sized for it)
+    float *__restrict__ xs = rs_lds;
+    float *__restrict__ ys = rs_lds + span_cap;              // the tile's RS_TILE results
+    for (int i = threadIdx.x; i < need; i += RS_THREADS) {
+      const int64_t s = rel_first + i;
+      float v = 0.f;                                         // before the signal, behind what has arrived: zero
+      if (s >= 0 && s < n) v = s < n_hist ? hold[s] : xr[s - n_hist];
+      xs[i] = v;
+    }
+    __syncthreads();
+    const float *__restrict__ x0 = xs + (K - 1);             // x[n_hi] of the tile's first output
+    if (up == 1)
+      rs_tile_chains<1>(x0, table, ys, r0, nt, up, down, K, kp);
+    else if (up == 2)
+      rs_tile_chains<2>(x0, table, ys, r0, nt, up, down, K, kp);
+    else if (up == 3)
+      rs_tile_chains<3>(x0, table, ys, r0, nt, up, down, K, kp);
+    else
+      rs_tile_chains<0>(x0, table, ys, r0, nt, up, down, K, kp);
+    __syncthreads();
+    float *__restrict__ dst = y + (int64_t)rec[6] * y_pitch + rec[10] + t0;
+    for (int o = threadIdx.x; o < nt; o += RS_THREADS) dst[o] = ys[o];
+  }
+  if (tile == last) {
+    for (int t = threadIdx.x; t < keep; t += RS_THREADS) {
+      const int s = n - keep + t;
+      hnew[t] = s < n_hist ? hold[s] : xr[s - n_hist];
+    }
+  }
 }
 
 }  // namespace cum
@@ -229,6 +318,88 @@ extern "C" int cum_resample_ragged(int32_t src_i16, const void *x, int32_t batch
     rs_launch<int16_t>(x, len, origin, table, y, a, g, lds, (hipStream_t)stream);
   else
     rs_launch<float>(x, len, origin, table, y, a, g, lds, (hipStream_t)stream);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_resample_slots(float *hist, int64_t hist_pitch, int32_t capacity, const int32_t *plans_host,
+                                  const int32_t *plans, int32_t n_plans, const float *tables, int64_t table_floats,
+                                  const int32_t *recs_host, const int32_t *recs, int32_t n_recs, const float *x,
+                                  int32_t x_rows, int64_t x_pitch, float *y, int32_t y_rows, int64_t y_pitch,
+                                  void *stream) {
+  CUM_REQUIRE(capacity >= 1 && n_plans >= 1 && n_recs >= 0 && n_recs <= 65535,
+              "resample_slots: capacity and n_plans must be at least 1, n_recs in [0, 65535]");
+  CUM_REQUIRE(hist_pitch >= 0 && table_floats >= 0 && x_rows >= 0 && x_pitch >= 0 && y_rows >= 0 && y_pitch >= 0,
+              "resample_slots: negative pitch or row count");
+  CUM_REQUIRE(hist != nullptr && plans_host != nullptr && plans != nullptr && tables != nullptr &&
+                  recs_host != nullptr && recs != nullptr && y != nullptr && (x != nullptr || x_rows == 0),
+              "resample_slots: null pointer");
+  CUM_REQUIRE((reinterpret_cast<uintptr_t>(tables) & 15) == 0, "resample_slots: tables must be 16-byte aligned");
+  CUM_REQUIRE((reinterpret_cast<uintptr_t>(recs) & 7) == 0 && (reinterpret_cast<uintptr_t>(recs_host) & 7) == 0 &&
+                  (reinterpret_cast<uintptr_t>(plans) & 3) == 0 && (reinterpret_cast<uintptr_t>(plans_host) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(hist) & 3) == 0 && (reinterpret_cast<uintptr_t>(x) & 3) == 0 &&
+                  (reinterpret_cast<uintptr_t>(y) & 3) == 0,
+              "resample_slots: hist, plans, recs, x or y is misaligned (records 8 bytes, the rest 4)");
+  int64_t span = 0;
+  for (int32_t i = 0; i < n_plans; ++i) {
+    const int32_t *p = plans_host + (int64_t)i * kRsPlanInts;
+    const int32_t up = p[0], down = p[1], n_taps = p[2], K = p[3], kp = p[4], off = p[5];
+    CUM_REQUIRE(up >= 1 && down >= 1, "resample_slots: up and down must be at least 1");
+    CUM_REQUIRE(up <= 1024 && down <= 1024, "resample_slots: up and down must be at most 1024 (reduce the ratio)");
+    CUM_REQUIRE(n_taps >= 1 && (n_taps & 1) == 1, "resample_slots: the tap count must be odd (taps h[0 .. 2H])");
+    CUM_REQUIRE(K >= 1 && (int64_t)K * up >= n_taps, "resample_slots: K * up is smaller than the tap count");
+    CUM_REQUIRE(kp >= K && kp % 4 == 0, "resample_slots: table_pitch must be a multiple of 4 floats and at least K");
+    CUM_REQUIRE(off >= 0 && off % 4 == 0 && (int64_t)off + (int64_t)up * kp <= table_floats,
+                "resample_slots: a plan's table does not lie in the blob at a multiple of 4 floats");
+    const int64_t s = rs_span_cap(up, down, K);
+    CUM_REQUIRE(s <= RS_LDS_SPAN_FLOATS,
+                "resample_slots: the input span of one tile (tile * down / up + K samples) does not fit in LDS");
+    span = s > span ? s : span;
+  }
+  if (n_recs == 0) return CUM_OK;
+  std::vector<uint8_t> named((size_t)capacity, 0);
+  int32_t tiles = 1;
+  for (int32_t i = 0; i < n_recs; ++i) {
+    const int32_t *r = recs_host + (int64_t)i * kRsRecInts;
+    const int32_t slot = r[0], plan = r[1], n_hist = r[2], x_row = r[3], n_new = r[4], n_out = r[5], y_row = r[6];
+    const int32_t ends = r[7], keep = r[8], parity = r[9], y_col = r[10];
+    int64_t in0, out0;
+    memcpy(&in0, r + 12, sizeof in0);
+    memcpy(&out0, r + 14, sizeof out0);
+    CUM_REQUIRE(slot >= 0 && slot < capacity, "resample_slots: a record names a slot outside the pool (slot < capacity)");
+    CUM_REQUIRE(!named[slot], "resample_slots: a slot is named twice");
+    named[slot] = 1;
+    CUM_REQUIRE(plan >= 0 && plan < n_plans, "resample_slots: a record names a plan outside the table");
+    CUM_REQUIRE(parity == 0 || parity == 1, "resample_slots: parity must be 0 or 1");
+    CUM_REQUIRE(n_hist >= 0 && n_hist <= hist_pitch, "resample_slots: a history count does not fit the history row");
+    CUM_REQUIRE(n_new >= 0 && n_new <= x_pitch && (n_new == 0 || (x_row >= 0 && x_row < x_rows)),
+                "resample_slots: a chunk does not fit the rows of x");
+    CUM_REQUIRE(keep >= 0 && keep <= hist_pitch && keep <= (int64_t)n_hist + n_new,
+                "resample_slots: the history to keep does not fit the history row or exceeds the samples held");
+    CUM_REQUIRE(n_out >= 0 && y_col >= 0 && (int64_t)y_col + n_out <= y_pitch &&
+                    (n_out == 0 || (y_row >= 0 && y_row < y_rows)),
+                "resample_slots: the outputs do not fit the rows of y");
+    CUM_REQUIRE(in0 >= 0 && out0 >= 0 && in0 <= (INT64_MAX >> 12) && out0 <= (INT64_MAX >> 12),
+                "resample_slots: a position is negative or beyond 2^51");
+    // the outputs asked for must exist: all of the signal's when it ends here, else those no later sample can change
+    const int32_t *p = plans_host + (int64_t)plan * kRsPlanInts;
+    const int64_t up = p[0], down = p[1], H = (p[2] - 1) / 2, K = p[3];
+    const int64_t total = in0 + n_hist + n_new;
+    const int64_t all = (total * up + down - 1) / down;
+    int64_t fin = total * up - H;
+    fin = fin <= 0 ? 0 : (fin + down - 1) / down;
+    CUM_REQUIRE(out0 + n_out <= (ends ? all : (fin < all ? fin : all)),
+                "resample_slots: more outputs than the samples received make final");
+    // ... and the history must reach back to the oldest sample the first of them reads
+    CUM_REQUIRE(n_out == 0 || in0 == 0 || (out0 * down + H) / up - (K - 1) >= in0,
+                "resample_slots: the history starts behind the oldest sample the first output reads");
+    const int32_t t = (n_out + RS_TILE - 1) / RS_TILE;
+    tiles = t > tiles ? t : tiles;
+  }
+  const dim3 g((unsigned)tiles, (unsigned)n_recs);
+  const size_t lds = sizeof(float) * (size_t)(span + RS_TILE);
+  hipLaunchKernelGGL(resample_slots_kernel, g, dim3(RS_THREADS), lds, (hipStream_t)stream, recs, plans, tables, hist,
+                     hist_pitch, x, x_pitch, y, y_pitch, (int)span);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

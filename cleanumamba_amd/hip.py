@@ -208,6 +208,8 @@ SIGNATURES = {
     "cum_resample_tile": (c_i32, []),
     "cum_resample_ragged": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, _P, c_i32, c_i32, c_i32, c_i32, c_i32, _P, c_i32,
                                     _P, c_i64, c_i64, _P]),
+    "cum_resample_slots": (c_i32, [_P, c_i64, c_i32, _P, _P, c_i32, _P, c_i64, _P, _P, c_i32, _P, c_i32, c_i64, _P, c_i32,
+                                   c_i64, _P]),
 }
 
 _lib = None

@@ -498,13 +498,14 @@ class CleanUMamba(nn.Module):
             raise ValueError("input should be two dimensional: (streams, samples)")
         return streaming.feed_batch(self, noisy_input)
 
-    def stream_pool(self, capacity):
+    def stream_pool(self, capacity, model_rate=16000):
         """A pool of ``capacity`` stream slots on this model (network/streampool.py): streams that join, feed any number of
         samples and leave independently, every call's hops in one launch of the one-launch hop.  The pool keeps its own
         state; ``feed`` / ``feed_batch`` / ``flush`` of the model are not affected.  Models the one-launch hop declines
-        (hopplan.unsupported_reason: Mamba2, above hopplan.MAX_PARAMS, non-f32) raise ValueError."""
+        (hopplan.unsupported_reason: Mamba2, above hopplan.MAX_PARAMS, non-f32) raise ValueError.  ``model_rate``: the
+        sample rate the model works at; ``pool.open(rate=...)`` gives a slot that is fed and answers at its own rate."""
         from .streampool import StreamPool
-        pool = StreamPool(self, capacity)
+        pool = StreamPool(self, capacity, model_rate)
         self.__dict__.setdefault("_stream_pools", weakref.WeakSet()).add(pool)
         return pool
 

@@ -17,7 +17,13 @@ number of samples each, and every slot opens and closes on its own.  Per call:
 
 ``close`` gives each slot what ``flush`` gives a lone stream: zeros up to the slot's own ``valid_length``, its remaining
 hops, the decoder drain from its state rows (each at its own ring phase), then the rows are zeroed and the slot id can be
-reused.  Reference semantics: CleanUMamba.feed / flush, src/network/CleanUMamba.py:358-418, as ``feed`` / ``flush`` of
+reused.
+
+A slot can work at its own sample rate (``open(rate=...)``): the host keeps, per slot and direction, what a
+``StreamResampler`` keeps (``resample.stream_step``), the device the inputs its unfinished outputs still read
+(``rs_hist``), and a call that names such a slot converts all of them in ONE launch in front of step 2 and ONE behind
+step 4 (``cum_resample_slots``), bit-identical to a ``StreamResampler`` per slot and direction.  A call that names none
+runs steps 1 - 4 exactly as before.  Reference semantics: CleanUMamba.feed / flush, src/network/CleanUMamba.py:358-418, as ``feed`` / ``flush`` of
 this package implement them.
 """
 import collections
@@ -26,11 +32,13 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..util import resample as rs
 from . import convstack as cs
 from . import hopplan
 from . import streaming
 
 _REC = 8        # int32 per record of both tables (csrc/hop.hip: kHopItemInts, kStageRecInts)
+_RS_REC, _RS_PLAN = 16, 8   # int32 per record / plan of the conversion (csrc/resample.hip: kRsRecInts, kRsPlanInts)
 
 Schedule = collections.namedtuple("Schedule", "first n_hops offset consumed remainder")
 
@@ -65,7 +73,8 @@ class StreamPool:
     ``hopplan.MAX_PARAMS`` parameters, f32): every slot re-reads the weight blob per hop, and a slot's whole state lives in
     one row of the kernel's state block.  Others raise ``ValueError``."""
 
-    def __init__(self, model, capacity):
+    def __init__(self, model, capacity, model_rate=16000):
+        self.model_rate = rs._rate(model_rate, "model_rate")
         why = hopplan.unsupported_reason(model)
         if why is not None:
             raise ValueError(f"stream pool: {why}")
@@ -76,10 +85,19 @@ class StreamPool:
         if capacity < 1:
             raise ValueError("stream pool: capacity must be >= 1")
         self.model, self.capacity = model, capacity
+        # conversion of rated slots (one plan pair per rate the pool has seen)
+        self._rs_plans, self._rs_ids = [], {}                 # Plans: [2 k] rate -> model, [2 k + 1] model -> rate
+        self._rs_plan_host = self._rs_plan_dev = self._rs_tables = self.rs_hist = None
         self._adopt(hopplan.HopPlan(model))
         self._open = np.zeros(capacity, dtype=bool)
         self._pend = np.zeros(capacity, dtype=np.int64)       # samples in hist[slot]
         self._frames = np.zeros(capacity, dtype=np.int64)     # frames run (the first one included)
+        self._rate = np.zeros(capacity, dtype=np.int64)       # 0: the slot works at the model's rate
+        self._rs_par = np.zeros((capacity, 2, 5), dtype=np.int64)   # per direction (in, out): plan id, up, down, H, K
+        self._rs_pos = np.zeros((capacity, 2, 3), dtype=np.int64)   # ... received, emitted, where the history starts
+        self._rs_parity = np.zeros((capacity, 2), dtype=np.int64)   # ... the row of rs_hist that holds the history
+        self._fed = np.zeros(capacity, dtype=np.int64)        # samples a rated slot was fed / has returned, at its rate
+        self._given = np.zeros(capacity, dtype=np.int64)
 
     # ------------------------------------------------------------------ slots
     @property
@@ -88,26 +106,95 @@ class StreamPool:
         return [int(s) for s in np.flatnonzero(self._open)]
 
     def pending(self, slots):
-        """Samples each slot holds that no hop has consumed yet."""
+        """Samples each slot holds that no hop has consumed yet: samples at the MODEL's rate, also for a rated slot
+        (what its in-conversion still holds back is not counted)."""
         return [int(self._pend[s]) for s in self._slots(slots)]
 
-    def open(self, n=1):
-        """Open ``n`` slots (the lowest free ids); returns their ids.  Each starts a fresh stream."""
+    def rate(self, slots):
+        """The sample rate each slot is fed and answers at (``model_rate`` for an unrated slot)."""
+        return [int(self._rate[s]) or self.model_rate for s in self._slots(slots)]
+
+    def open(self, n=1, rate=None):
+        """Open ``n`` slots (the lowest free ids); returns their ids.  Each starts a fresh stream.  ``rate``: the sample
+        rate the slots are fed and answer at; None or ``model_rate`` gives slots at the model's rate.  Any other must be
+        a positive integer both conversions exist for (reduced factors up to 1024, a tile's input span within the
+        kernel's LDS): ValueError otherwise, before anything else happens."""
+        rate = self._check_rate(rate)
         n = int(n)
         free = np.flatnonzero(~self._open)
         if n < 0 or n > free.size:
             raise ValueError(f"stream pool: {n} slots asked for, {free.size} of {self.capacity} free")
         got = free[:n]
+        if rate and n:
+            k = self._register(rate)
+            for d in (0, 1):
+                p = self._rs_plans[k + d]
+                self._rs_par[got, d] = (k + d, p.up, p.down, p.H, p.K)
+        self._rate[got] = rate
         self._open[got] = True
         return [int(s) for s in got]
+
+    def _check_rate(self, rate):
+        """0 for a slot at the model's rate, else the rate: both of its plans exist and fit the kernel."""
+        if rate is None:
+            return 0
+        r = rs._rate(rate, "the rate of a pool slot")
+        if r == self.model_rate:
+            return 0
+        for pair in ((r, self.model_rate), (self.model_rate, r)):
+            try:
+                p = rs.plan(*pair)
+            except ValueError as exc:
+                raise ValueError(f"stream pool: rate {r}: {exc}") from exc
+            if rs.tile_span(p.up, p.down, p.K) > rs.LDS_SPAN_FLOATS:
+                raise ValueError(f"stream pool: rate {r}: {pair[0]} -> {pair[1]} reduces to {p.up}/{p.down}, whose input "
+                                 f"span per tile ({rs.tile_span(p.up, p.down, p.K)} samples) does not fit the kernel's LDS")
+        return r
+
+    def _register(self, rate):
+        """The id of ``rate``'s plan pair (in: id, out: id + 1); a rate the pool has not seen extends the plan table and
+        the table blob on the device, and the history rows if its filters are longer."""
+        if rate in self._rs_ids:
+            return self._rs_ids[rate]
+        k = len(self._rs_plans)
+        self._rs_plans += [rs.plan(rate, self.model_rate), rs.plan(self.model_rate, rate)]
+        self._rs_ids[rate] = k
+        self._rs_upload()
+        return k
+
+    def _rs_upload(self):
+        plans = self._rs_plans
+        if not plans:
+            return
+        ints = np.zeros((len(plans), _RS_PLAN), dtype=np.int32)
+        tabs, off = [], 0
+        for i, p in enumerate(plans):
+            ints[i, :6] = (p.up, p.down, len(p.taps), p.K, p.pitch, off)
+            tabs.append(p.host_table().reshape(-1))
+            off += p.up * p.pitch
+        self._rs_plan_host = torch.from_numpy(ints)
+        self._rs_plan_dev = self._rs_plan_host.to(self.device)
+        self._rs_tables = torch.cat(tabs).to(self.device)
+        pitch = hopplan._rup(max(max(rs.history_bound(p.K) for p in plans), 1), 4)
+        old = self.rs_hist
+        if old is None or old.shape[3] < pitch or old.device != self.device:
+            # [direction][slot][parity][pitch]: the inputs a slot's unfinished outputs may still read, two rows each
+            self.rs_hist = torch.zeros(2, self.capacity, 2, pitch, dtype=torch.float32, device=self.device)
+            if old is not None and old.device == self.device:
+                self.rs_hist[..., :old.shape[3]] = old
 
     def reset(self):
         """Close every slot without output; all state is zeroed."""
         self.state.zero_()
         self.hist.zero_()
+        if self.rs_hist is not None:
+            self.rs_hist.zero_()
         self._open[:] = False
         self._pend[:] = 0
         self._frames[:] = 0
+        self._rate[:] = 0
+        self._rs_par[:], self._rs_pos[:], self._rs_parity[:] = 0, 0, 0
+        self._fed[:], self._given[:] = 0, 0
 
     def relayout(self):
         """The model's widths changed (pruning) while no slot is open: take the new plan and size the state blocks to it.
@@ -128,6 +215,7 @@ class StreamPool:
         self.hop, self.frame_len, self.device = plan.hop, plan.frame_len, plan.device
         self.state = torch.zeros(self.capacity, plan.state_stride, dtype=torch.float32, device=self.device)
         self.hist = torch.zeros(self.capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32, device=self.device)
+        self._rs_upload()                   # (the conversion tables follow the model's device)
 
     def invalidate_packed_weights(self):
         """Re-pack the weight blob on the next call (``CleanUMamba.invalidate_packed_weights`` calls this)."""
@@ -148,7 +236,9 @@ class StreamPool:
     @torch.no_grad()
     def feed(self, slots, x):
         """New samples of the named slots: ``x`` (len(slots), L) f32 on the pool's GPU, or a list of 1-D tensors (one per
-        slot, any lengths).  Returns one 1-D tensor per slot, a multiple of ``total_stride`` long: views of one buffer."""
+        slot, any lengths).  Returns one 1-D tensor per slot, a multiple of ``total_stride`` long: views of one buffer.
+        A rated slot's chunk is at the slot's rate, and so is what it gets back: the samples that became final, any
+        number of them (none while the chunks are shorter than the filters' delay)."""
         a = self._slots(slots)
         if isinstance(x, (list, tuple)):
             if len(x) != a.size or any(t.dim() != 1 for t in x):
@@ -163,13 +253,53 @@ class StreamPool:
                 x = x.contiguous()
         if x is not None and (x.dtype != torch.float32 or x.device != self.device):
             raise ValueError(f"stream pool: samples must be f32 on {self.device}")
-        return self._run(a, x, lengths)
+        rated = self._rate[a] > 0
+        if not rated.any():
+            return self._run(a, x, lengths)
+        return self._feed_rated(a, x, lengths, rated)
 
     @torch.no_grad()
     def close(self, slots):
         """End the named slots' streams: what ``flush`` gives a lone stream (its pending samples padded with the zeros
-        ``forward`` adds, the remaining hops, the decoder's drain), one 1-D tensor per slot.  The slots are free again."""
+        ``forward`` adds, the remaining hops, the decoder's drain), one 1-D tensor per slot.  The slots are free again.
+
+        A rated slot: its in-conversion ends (outputs through ``out_length(received)``), what that gives is fed, the
+        model's close follows, and all of it with the end of the signal goes through the out-conversion, cropped so that
+        everything the slot returned adds up to exactly the samples it was fed.  Its conversion state is zeroed."""
         a = self._slots(slots)
+        rated = self._rate[a] > 0
+        if not rated.any():
+            return self._close_model(a)
+        if self.device.type != "cuda":
+            raise RuntimeError("stream pool: the model is not on a GPU")
+        n, ri = a.size, np.flatnonzero(rated)
+        sr, none = a[ri], np.zeros(ri.size, dtype=np.int64)
+        count, base = self._rs_step(0, sr, none, True)
+        mlen = np.zeros(n, dtype=np.int64)
+        mlen[ri] = count
+        xm = torch.empty(n, hopplan._rup(max(int(mlen.max()), 1), 4), dtype=torch.float32, device=self.device)
+        self._rs_launch(0, sr, none, count, base, True, None, ri, xm, ri)
+        heads = self._run(a, xm, mlen)
+        outs = self._close_model(a)
+        rows = [torch.cat([heads[i], outs[i]]) for i in ri]
+        olen = np.asarray([r.numel() for r in rows], dtype=np.int64)
+        count, base = self._rs_step(1, sr, olen, True)
+        if int(count.max()) > 0:
+            src = torch.nn.utils.rnn.pad_sequence(rows, batch_first=True) if int(olen.max()) else None
+            z = torch.empty(ri.size, int(count.max()), dtype=torch.float32, device=self.device)
+            self._rs_launch(1, sr, olen, count, base, True, src, np.arange(ri.size), z, np.arange(ri.size))
+        # a round trip never shortens a signal: the slot gets back exactly what it was fed
+        crop = np.clip(self._fed[sr] - self._given[sr], 0, count)
+        for j, i in enumerate(ri):
+            outs[i] = z[j, :int(crop[j])] if crop[j] else torch.zeros(0, dtype=torch.float32, device=self.device)
+        self.rs_hist.index_fill_(1, self._index(sr), 0.0)
+        self._rate[sr] = 0
+        self._rs_par[sr], self._rs_pos[sr], self._rs_parity[sr] = 0, 0, 0
+        self._fed[sr], self._given[sr] = 0, 0
+        return outs
+
+    def _close_model(self, a):
+        """``close`` at the model's rate."""
         hop = self.hop
         pend, frames = self._pend[a].copy(), self._frames[a].copy()
         total = frames * hop + pend
@@ -213,12 +343,98 @@ class StreamPool:
             raise RuntimeError("stream pool: the model's shapes changed under live slots")
         self.plan, self._wv, self._stale = plan, wv, False
 
+    # ------------------------------------------------------------------ rated slots
+    def _rs_step(self, d, s, lens, ends):
+        """What ``lens`` new samples (and, with ``ends``, the end of the signal) make of direction ``d`` of slots ``s``:
+        (outputs that become final, where the history starts afterwards).  Host arithmetic only."""
+        pos, par = self._rs_pos[s, d], self._rs_par[s, d]
+        return rs.stream_step(pos[:, 0], pos[:, 1], pos[:, 2], lens, par[:, 1], par[:, 2], par[:, 3], par[:, 4], ends)
+
+    def _rs_launch(self, d, s, lens, count, base, ends, src, src_rows, dst, dst_rows):
+        """Direction ``d`` of slots ``s`` in ONE launch of cum_resample_slots, whatever their rates: slot s[j] takes
+        src[src_rows[j]][:lens[j]] behind its history and writes its ``count[j]`` new outputs to dst[dst_rows[j]]; the
+        history from ``base[j]`` on goes to the slot's other row.  Slots that neither get a sample nor give one are left
+        out (nothing of theirs changes)."""
+        pos = self._rs_pos[s, d]
+        got = pos[:, 0] + lens
+        self._rs_pos[s, d] = np.stack([got, pos[:, 1] + count, base], 1)
+        act = np.flatnonzero((lens > 0) | (count > 0))
+        if act.size == 0:
+            return
+        sa = s[act]
+        rec = np.zeros((act.size, _RS_REC), dtype=np.int32)
+        rec[:, 0], rec[:, 1], rec[:, 2] = sa, self._rs_par[sa, d, 0], pos[act, 0] - pos[act, 2]
+        rec[:, 3], rec[:, 4], rec[:, 5], rec[:, 6] = src_rows[act], lens[act], count[act], dst_rows[act]
+        rec[:, 7], rec[:, 8], rec[:, 9] = int(bool(ends)), got[act] - base[act], self._rs_parity[sa, d]
+        wide = rec.view(np.int64)                        # ints 12-13: the history's position, 14-15: the first output's
+        wide[:, 6], wide[:, 7] = pos[act, 2], pos[act, 1]
+        self._rs_parity[sa, d] ^= 1
+        host = torch.from_numpy(rec).pin_memory()
+        drec = host.to(self.device, non_blocking=True)
+        hist = self.rs_hist[d]
+        rows, pitch = (0, 0) if src is None else (src.shape[0], max(src.stride(0), src.shape[1]))
+        with torch.cuda.device(self.device):
+            hip.check(hip.lib().cum_resample_slots(
+                hip.ptr(hist), hist.stride(1), self.capacity, hip.ptr(self._rs_plan_host), hip.ptr(self._rs_plan_dev),
+                len(self._rs_plans), hip.ptr(self._rs_tables), self._rs_tables.numel(), hip.ptr(host), hip.ptr(drec),
+                act.size, None if rows == 0 else hip.ptr(src), rows, pitch, hip.ptr(dst), dst.shape[0],
+                max(dst.stride(0), dst.shape[1]), hip.stream_ptr()))
+
+    def _feed_rated(self, a, x, lengths, rated):
+        """``feed`` of a call that names rated slots: their chunks become model-rate chunks in one launch (the others'
+        are copied beside them), the call runs as any other, and what it gives the rated slots goes back to their rates
+        in one launch."""
+        if self.device.type != "cuda":
+            raise RuntimeError("stream pool: the model is not on a GPU")
+        n, ri, ui = a.size, np.flatnonzero(rated), np.flatnonzero(~rated)
+        sr = a[ri]
+        empty = torch.zeros(0, dtype=torch.float32, device=self.device)
+        self._fed[sr] += lengths[ri]
+        count, base = self._rs_step(0, sr, lengths[ri], False)
+        mlen = lengths.copy()
+        mlen[ri] = count
+        xm = torch.empty(n, hopplan._rup(max(int(mlen.max()), 1), 4), dtype=torch.float32, device=self.device)
+        wu = int(lengths[ui].max()) if ui.size else 0
+        if wu:
+            idx = self._index(ui)
+            xm[:, :wu].index_copy_(0, idx, x[:, :wu].index_select(0, idx))
+        self._rs_launch(0, sr, lengths[ri], count, base, False, x, ri, xm, ri)
+        res = self._hops(a, xm, mlen)
+        outs = [empty] * n
+        olen = np.zeros(ri.size, dtype=np.int64)
+        if res is not None:
+            out, row, width = res
+            for i in ui:
+                outs[i] = out[row[i], :width[i]]
+            olen = width[ri]
+        count, base = self._rs_step(1, sr, olen, False)
+        if res is not None and int(olen.max()) > 0:
+            z = torch.empty(ri.size, max(int(count.max()), 1), dtype=torch.float32, device=self.device)
+            self._rs_launch(1, sr, olen, count, base, False, out, row[ri], z, np.arange(ri.size))
+            for j, i in enumerate(ri):
+                outs[i] = z[j, :count[j]]
+        self._given[sr] += count
+        return outs
+
+    # ------------------------------------------------------------------ the call at the model's rate
     def _run(self, a, x, lengths):
+        res = self._hops(a, x, lengths)
+        if res is None:
+            # nothing arrives: no slot reaches a frame (pending < frame_len), nothing changes
+            return [torch.zeros(0, dtype=torch.float32, device=self.device) for _ in range(a.size)]
+        out, row, width = res
+        if (width == width[0]).all():
+            rows = out.unbind(0)
+            return [rows[r] for r in row]
+        return [out[r, :w] for r, w in zip(row, width)]
+
+    def _hops(self, a, x, lengths):
+        """The staging launch, the first-frame cohort and the slotted hop of one call.  -> (out, row, width): slot a[i]'s
+        output is out[row[i], :width[i]]; None when no sample arrives."""
         n = a.size
         hop, F = self.hop, self.frame_len
         if n == 0 or int(lengths.sum()) == 0:
-            # nothing arrives: no slot reaches a frame (pending < frame_len), nothing changes
-            return [torch.zeros(0, dtype=torch.float32, device=self.device) for _ in range(n)]
+            return None
         if self.device.type != "cuda":
             raise RuntimeError("stream pool: the model is not on a GPU")
         self._refresh_weights()
@@ -264,11 +480,7 @@ class StreamPool:
                     hip.ptr(out), out.stride(0), p.lds_bytes, hip.stream_ptr()))
         self._pend[a] = sch.remainder
         self._frames[a] += sch.first + sch.n_hops
-        width = sch.consumed
-        if (width == width[0]).all():
-            rows = out.unbind(0)
-            return [rows[r] for r in row]
-        return [out[r, :w] for r, w in zip(row, width)]
+        return out, row, sch.consumed
 
     def _first_frames(self, frame, dst, slot_idx):
         """The first frame of the slots in ``slot_idx`` (k, frame_len) on the per-layer fused path, in a private streaming

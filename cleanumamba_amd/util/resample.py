@@ -14,6 +14,9 @@ samples only, which is what makes a clip's result independent of its batch and a
   plan             (rate_in, rate_out) -> Plan: up, down, H, K, the f64 taps; ``plan.table(device)`` the polyphase table
   out_length       ceil(L up / down) (pure)
   final_outputs    outputs that no later input can change (pure)
+  stream_step      one push of a stream: outputs now final, history to keep (pure; StreamResampler and the stream pool's
+                   rated slots, network/streampool.py); history_bound, tile_span: what sizes the pool's rows, what the
+                   kernels' LDS admits
   resample_ragged  a ragged batch in one launch
   StreamResampler  push / finish over signals of any length, bit-identical to ``resample_ragged`` on the whole signal
 
@@ -22,12 +25,15 @@ There is no CPU or PyTorch implementation: a tensor that is not on the GPU raise
 import math
 import numbers
 
+import numpy as np
 import torch
 
 from .. import hip
 from .metrics import resample_taps
 
 MAX_FACTOR = 1024
+RS_TILE = 768                # outputs of one workgroup (csrc/resample.hip: RS_TILE = cum_resample_tile())
+LDS_SPAN_FLOATS = 12288      # ... and the longest input span it stages (RS_LDS_SPAN_FLOATS)
 PCM_SCALE = 1.0 / 32768.0
 _PLANS = {}
 
@@ -42,6 +48,37 @@ def final_outputs(received, up, down, H):
     floor((m down + H) / up), so it is final when m down + H < received up -- max(0, ceil((received up - H) / down)),
     capped at ``out_length(received)``."""
     return min(max(0, -(-(int(received) * int(up) - int(H)) // int(down))), out_length(received, up, down))
+
+
+def stream_step(received, emitted, base, n, up, down, H, K, ends=False):
+    """The bookkeeping of one push of ``n`` samples (or, with ``ends``, of the signal's end) into a stream that has
+    ``received`` inputs, has ``emitted`` outputs and keeps its inputs from absolute position ``base`` on.  Returns
+    ``(count, base')``: the outputs that become final -- through ``final_outputs(received + n)``, through
+    ``out_length(received + n)`` at the end -- and where the history must start afterwards: at the oldest sample the next
+    output reads, its n_hi = ((emitted + count) down + H) // up less the K - 1 taps behind it (never before ``base``,
+    never behind the samples received).  Pure integer arithmetic; scalars or numpy int64 arrays of one entry per stream."""
+    received = received + n
+    if isinstance(received, np.ndarray):
+        all_ = -(-received * up // down)
+        final = np.where(ends, all_, np.minimum(np.maximum(0, -(-(received * up - H) // down)), all_))
+        count = final - emitted
+        return count, np.minimum(np.maximum(((emitted + count) * down + H) // up - (K - 1), base), received)
+    final = out_length(received, up, down) if ends else final_outputs(received, up, down, H)
+    count = final - emitted
+    return count, min(max(((emitted + count) * down + H) // up - (K - 1), base), received)
+
+
+def history_bound(K):
+    """The most inputs a stream keeps between pushes: output m = final_outputs(received) is the first with
+    (m down + H) // up >= received, so the history starts at or after received - (K - 1) -- K - 1 samples, whatever the
+    cuts.  (Before the first final output the stream holds all it received: at most H // up <= K - 1.)"""
+    return int(K) - 1
+
+
+def tile_span(up, down, K):
+    """Floats of LDS one workgroup's input span needs (csrc/resample.hip: rs_span_cap); the kernels take a pair only if
+    this is at most ``LDS_SPAN_FLOATS``."""
+    return (int(K) + ((int(up) - 1) + (RS_TILE - 1) * int(down)) // int(up) + 16 + 7) // 8 * 8
 
 
 class Plan:
@@ -206,9 +243,8 @@ class StreamResampler:
             self.emitted = self.received
             return new.to(x.device)
         buf = torch.cat([self.hist, new], 1)
-        out = self._emit(buf, final_outputs(self.received, p.up, p.down, p.H) - self.emitted, False)
-        # the oldest sample the next output reads: its n_hi less the K - 1 taps behind it
-        keep = min(max((self.emitted * p.down + p.H) // p.up - (p.K - 1), self.base), self.received)
+        count, keep = stream_step(self.received - x.shape[1], self.emitted, self.base, x.shape[1], p.up, p.down, p.H, p.K)
+        out = self._emit(buf, count, False)
         self.hist = buf[:, keep - self.base:].clone()
         self.base = keep
         return out.to(x.device)

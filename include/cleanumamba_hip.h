@@ -890,6 +890,35 @@ int cum_resample_ragged(int32_t src_i16, const void *x, int32_t batch, int64_t l
                         const int64_t *origin, int32_t ends, int32_t up, int32_t down, int32_t n_taps, int32_t K,
                         const float *table, int32_t table_pitch, float *y, int64_t out_pitch, int64_t max_out,
                         void *stream);
+/* cum_resample_slots: the same chains (bit for bit) for streams of different rate pairs at different positions, in one
+ *   launch over a record table -- what converts the stream pool's slots (network/streampool.py).
+ *   hist: [capacity][2][hist_pitch] f32, the inputs a slot's unfinished outputs may still read, TWO rows per slot: a
+ *   record reads row `parity` and writes the next history to row 1 - parity, so the workgroups of a record (one per
+ *   cum_resample_tile outputs) never read what one of them writes.  The signal a record sees is
+ *   hist[slot][parity][0, n_hist) ++ x[x_row][0, n_new), its first sample at absolute position in0.
+ *   Plan p = 8 int32 {up, down, n_taps, K, table_pitch, table_offset, 0, 0}: the pair's polyphase table (as for
+ *     cum_resample_ragged) starts table_offset floats (a multiple of 4) into `tables` (table_floats long, 16-byte
+ *     aligned).  up <= 3 takes the scalar-tap route, any other the per-lane row route, per record.
+ *   Record r = 16 int32 {slot, plan, n_hist, x_row, n_new, n_out, y_row, ends, keep, parity, y_col, 0,
+ *     in0 (int64 in ints 12-13), out0 (int64 in ints 14-15)}:
+ *       y[y_row][y_col + o] = output out0 + o of the signal, o < n_out (inputs before position 0 and behind the
+ *         samples held enter as zeros);
+ *       hist[slot][1 - parity][0, keep) = the last `keep` samples of the signal.
+ *     Nothing is read behind n_hist / n_new, nothing is written behind n_out / keep.  A record with n_out = 0 only
+ *     moves the history.
+ *   plans / recs: device tables; plans_host / recs_host: the same in host memory, checked before the launch.  x, y:
+ *   f32 rows x_pitch / y_pitch apart, x_rows / y_rows of them (x may be NULL with x_rows = 0).  No workspace, no atomics.
+ *   CUM_EINVAL before any launch: a null or misaligned pointer (tables 16 bytes, records 8, the rest 4), capacity or
+ *   n_plans < 1, n_recs outside [0, 65535], a negative pitch or row count, plan fields outside the limits of
+ *   cum_resample_ragged (the LDS span included) or a table outside the blob, a slot outside [0, capacity), a slot named
+ *   twice, a plan id outside [0, n_plans), parity not 0 / 1, n_hist or keep above hist_pitch, keep above
+ *   n_hist + n_new, a chunk or outputs that do not fit the rows of x / y, a negative position, out0 + n_out beyond the
+ *   outputs the samples make final (ends = 0) or the signal has (ends != 0), or a history that starts behind the oldest
+ *   sample the first output reads.  n_recs = 0 returns CUM_OK after the plan checks, without a launch. */
+int cum_resample_slots(float *hist, int64_t hist_pitch, int32_t capacity, const int32_t *plans_host, const int32_t *plans,
+                       int32_t n_plans, const float *tables, int64_t table_floats, const int32_t *recs_host,
+                       const int32_t *recs, int32_t n_recs, const float *x, int32_t x_rows, int64_t x_pitch, float *y,
+                       int32_t y_rows, int64_t y_pitch, void *stream);
 
 #ifdef __cplusplus
 }
