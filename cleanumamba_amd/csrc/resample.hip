@@ -277,6 +277,126 @@ __global__ __launch_bounds__(RS_THREADS) void resample_slots_kernel(const int32_
   }
 }
 
+// ---- feeder: the train step's float batch from int16 windows at any mix of rates (cum_pcm_batch_resample_f32) --------
+// What training/feeder.py assembles a rated batch with: cum_pcm_batch_f32's layout -- row b the clean
+// clip, row batch + b the noisy clip, `pitch` int16 apart -- but a row holds the window of its file, at the file's rate,
+// that the crop reads, and leaves as the model-rate crop in the step's input buffers.
+//
+// Record b = 16 int32 {plan, n_src, M, N, 0 x 8, in0 (int64 in ints 12-13), out0 (int64 in ints 14-15)}, one per PAIR:
+//   plan: index into `plans` (the cum_resample_slots layout), -1 = the pair is at the model rate (up = down = K = 1,
+//   H = 0, the tap 1: y[m] = x[m]);  n_src: samples staged in both rows, absolute positions [in0, in0 + n_src) of a
+//   file of N samples with M = ceil(N up / down) outputs;  out[t] = y[(out0 + t) mod M], t < len.
+// A workgroup owns RS_TILE outputs m = out0 + t0 + o of one row, computes each ONCE and stores it to every t = t0 + o + k M
+// below len, so a tiled clip repeats bit for bit.
+constexpr int kRsFeedRecInts = 16;
+constexpr int RS_COPY_SPAN = RS_TILE + 8;    // LDS floats a tile of a model-rate row stages (its outputs + chunk slack)
+
+// ys[0, n) -> dst[0, n) by the whole workgroup: 16-byte stores from dst's first 16-byte boundary on, elements around them
+__device__ __forceinline__ void rs_store_run(float *__restrict__ dst, const float *__restrict__ ys, const int n) {
+  int head = (int)((4 - ((reinterpret_cast<uintptr_t>(dst) >> 2) & 3)) & 3);
+  head = head < n ? head : n;
+  if ((int)threadIdx.x < head) dst[threadIdx.x] = ys[threadIdx.x];
+  const int nv = (n - head) >> 2;
+  for (int v = threadIdx.x; v < nv; v += RS_THREADS) {
+    const int o = head + 4 * v;
+    *reinterpret_cast<rs_float4 *>(dst + o) = rs_float4{ys[o], ys[o + 1], ys[o + 2], ys[o + 3]};
+  }
+  for (int o = head + 4 * nv + (int)threadIdx.x; o < n; o += RS_THREADS) dst[o] = ys[o];
+}
+
+// grid: (tiles of len, 2 * batch rows)
+__global__ __launch_bounds__(RS_THREADS) void pcm_batch_resample_kernel(
+    const int16_t *__restrict__ pcm, const int64_t pitch, const int32_t *__restrict__ recs,
+    const int32_t *__restrict__ plans, const int n_plans, const float *__restrict__ tables, const int batch,
+    const int64_t len, float *__restrict__ clean, const int64_t clean_sb, float *__restrict__ noisy,
+    const int64_t noisy_sb, const int span_cap) {
+  extern __shared__ __attribute__((aligned(16))) float rs_lds[];
+  constexpr int E = 8;                                       // samples of one 16-byte chunk
+  const int r = blockIdx.y;
+  const int b = r < batch ? r : r - batch;
+  const int32_t *__restrict__ rec = recs + (int64_t)b * kRsFeedRecInts;          // workgroup-uniform, as all below
+  const int plan = rec[0];
+  if (plan < -1 || plan >= n_plans) return;
+  // a bad table can never index outside a row: n in [0, pitch], M >= 1, positions in [0, 2^51], out0 < M
+  constexpr int64_t kPosMax = INT64_MAX >> 12;
+  int64_t n = rec[1], M = rec[2];
+  n = n < 0 ? 0 : (n > pitch ? pitch : n);
+  M = M < 1 ? 1 : M;
+  int64_t in0 = *reinterpret_cast<const int64_t *>(rec + 12), out0 = *reinterpret_cast<const int64_t *>(rec + 14);
+  in0 = in0 < 0 ? 0 : (in0 > kPosMax ? kPosMax : in0);
+  out0 = out0 < 0 ? 0 : (out0 > M - 1 ? M - 1 : out0);
+  const int64_t cnt = M - out0 < len ? M - out0 : len;       // distinct outputs the row needs: y[out0, out0 + cnt)
+  const int64_t t0 = (int64_t)blockIdx.x * RS_TILE;
+  if (t0 >= cnt) return;
+  int nt = cnt - t0 < RS_TILE ? (int)(cnt - t0) : RS_TILE;
+
+  int up = 1, down = 1, H = 0, K = 1, kp = 4;
+  const float *__restrict__ table = tables;
+  if (plan >= 0) {
+    const int32_t *__restrict__ pl = plans + (int64_t)plan * kRsPlanInts;
+    up = pl[0], down = pl[1], H = (pl[2] - 1) / 2, K = pl[3], kp = pl[4];
+    table = tables + pl[5];
+  }
+  const int64_t c0 = (out0 + t0) * down + H;                 // >= 0
+  const int64_t q0 = c0 / up;
+  const int r0 = (int)(c0 - q0 * up);
+  const int64_t rel_first = q0 - (K - 1) - in0;              // row index of the oldest sample the first output reads
+  const int64_t rel_base = (rel_first >= 0 ? rel_first / E : -((-rel_first + E - 1) / E)) * E;   // floor to a chunk
+  const int off = (int)(rel_first - rel_base);               // in [0, E)
+  const int dq_last = (r0 + (nt - 1) * down) / up;
+  int need = K + dq_last + off;                              // LDS floats the tile reads: [0, need)
+  need = need > span_cap ? span_cap : need;                  // (never: span_cap is sized for it)
+
+  float *__restrict__ xs = rs_lds;
+  float *ys = rs_lds + span_cap;                             // the tile's RS_TILE results
+  const int16_t *__restrict__ row = pcm + (int64_t)r * pitch;                    // 16-byte aligned: pitch % 8 == 0
+  for (int c = threadIdx.x; c * E < need; c += RS_THREADS) {
+    const int64_t s0 = rel_base + (int64_t)c * E;            // a multiple of E: the chunk is 16-byte aligned
+    float v[E];
+    if (s0 >= 0 && s0 + E <= n) {
+      const rs_short8 s = *reinterpret_cast<const rs_short8 *>(row + s0);
+#pragma unroll
+      for (int j = 0; j < E; ++j) v[j] = (float)s[j] * kRsPcm;
+    } else {
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        float s = 0.f;                                       // before the window, behind its n_src samples: zero
+        if (s0 + j >= 0 && s0 + j < n) s = (float)row[s0 + j] * kRsPcm;
+        v[j] = s;
+      }
+    }
+    *reinterpret_cast<rs_float4 *>(xs + c * E) = rs_float4{v[0], v[1], v[2], v[3]};
+    *reinterpret_cast<rs_float4 *>(xs + c * E + 4) = rs_float4{v[4], v[5], v[6], v[7]};
+  }
+  __syncthreads();
+  const float *__restrict__ x0 = xs + (K - 1) + off;         // x[n_hi] of the tile's first output; output o: x0[dq(o)]
+  if (plan < 0) {
+    ys = xs + off;                                           // the model rate: output o IS staged sample o (exact)
+  } else {
+    if (up == 1)
+      rs_tile_chains<1>(x0, table, ys, r0, nt, up, down, K, kp);
+    else if (up == 2)
+      rs_tile_chains<2>(x0, table, ys, r0, nt, up, down, K, kp);
+    else if (up == 3)
+      rs_tile_chains<3>(x0, table, ys, r0, nt, up, down, K, kp);
+    else
+      rs_tile_chains<0>(x0, table, ys, r0, nt, up, down, K, kp);
+    __syncthreads();
+  }
+  // a file that fits the tile and is repeated: lay whole periods side by side first, so the replicas leave in runs of
+  // up to RS_TILE, not of M (copies: the bits of a period are those of the first)
+  int64_t period = M;
+  if (cnt < len && nt == M && 2 * nt <= RS_TILE) {
+    const int wide = RS_TILE / nt * nt;
+    for (int o = nt + threadIdx.x; o < wide; o += RS_THREADS) ys[o] = ys[o % nt];
+    __syncthreads();
+    nt = wide, period = wide;
+  }
+  float *__restrict__ dst = r < batch ? clean + (int64_t)b * clean_sb : noisy + (int64_t)b * noisy_sb;
+  for (int64_t tb = t0; tb < len; tb += period)
+    rs_store_run(dst + tb, ys, len - tb < nt ? (int)(len - tb) : nt);
+}
+
 }  // namespace cum
 
 using namespace cum;
@@ -400,6 +520,77 @@ extern "C" int cum_resample_slots(float *hist, int64_t hist_pitch, int32_t capac
   const size_t lds = sizeof(float) * (size_t)(span + RS_TILE);
   hipLaunchKernelGGL(resample_slots_kernel, g, dim3(RS_THREADS), lds, (hipStream_t)stream, recs, plans, tables, hist,
                      hist_pitch, x, x_pitch, y, y_pitch, (int)span);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_pcm_batch_resample_f32(const int16_t *pcm, int64_t pitch, const int32_t *recs_host, const int32_t *recs,
+                                          int32_t batch, const int32_t *plans_host, const int32_t *plans, int32_t n_plans,
+                                          const float *tables, int64_t table_floats, int64_t len, float *clean,
+                                          int64_t clean_sb, float *noisy, int64_t noisy_sb, void *stream) {
+  CUM_REQUIRE(batch >= 1, "pcm_batch_resample: batch must be at least 1");
+  CUM_REQUIRE(batch <= 32767, "pcm_batch_resample: batch must be at most 32767 (2 * batch rows on the grid's y axis)");
+  CUM_REQUIRE(len >= 1 && len <= (int64_t)RS_TILE * INT32_MAX, "pcm_batch_resample: len must be in [1, tile * 2^31)");
+  CUM_REQUIRE(pitch >= 0 && pitch % 8 == 0, "pcm_batch_resample: pitch must be a multiple of 8 samples (16-byte rows)");
+  CUM_REQUIRE(clean_sb >= len && noisy_sb >= len, "pcm_batch_resample: clean_sb and noisy_sb must be at least len");
+  CUM_REQUIRE(n_plans >= 0 && table_floats >= 0, "pcm_batch_resample: negative plan count or table size");
+  CUM_REQUIRE(pcm && recs_host && recs && clean && noisy, "pcm_batch_resample: null pointer");
+  CUM_REQUIRE(n_plans == 0 || (plans_host && plans && tables), "pcm_batch_resample: null plan table or tap tables");
+  CUM_REQUIRE(((reinterpret_cast<uintptr_t>(pcm) | reinterpret_cast<uintptr_t>(clean) | reinterpret_cast<uintptr_t>(noisy) |
+                reinterpret_cast<uintptr_t>(tables)) & 15) == 0,
+              "pcm_batch_resample: pcm, clean, noisy and tables must be 16-byte aligned");
+  CUM_REQUIRE((reinterpret_cast<uintptr_t>(recs) & 7) == 0 && (reinterpret_cast<uintptr_t>(recs_host) & 7) == 0 &&
+                  (reinterpret_cast<uintptr_t>(plans) & 3) == 0 && (reinterpret_cast<uintptr_t>(plans_host) & 3) == 0,
+              "pcm_batch_resample: recs or plans is misaligned (records 8 bytes, plans 4)");
+  int64_t span = RS_COPY_SPAN;
+  for (int32_t i = 0; i < n_plans; ++i) {
+    const int32_t *p = plans_host + (int64_t)i * kRsPlanInts;
+    const int32_t up = p[0], down = p[1], n_taps = p[2], K = p[3], kp = p[4], off = p[5];
+    CUM_REQUIRE(up >= 1 && down >= 1, "pcm_batch_resample: up and down must be at least 1");
+    CUM_REQUIRE(up <= 1024 && down <= 1024, "pcm_batch_resample: up and down must be at most 1024 (reduce the ratio)");
+    CUM_REQUIRE(n_taps >= 1 && (n_taps & 1) == 1, "pcm_batch_resample: the tap count must be odd (taps h[0 .. 2H])");
+    CUM_REQUIRE(K >= 1 && (int64_t)K * up >= n_taps, "pcm_batch_resample: K * up is smaller than the tap count");
+    CUM_REQUIRE(kp >= K && kp % 4 == 0, "pcm_batch_resample: table_pitch must be a multiple of 4 floats and at least K");
+    CUM_REQUIRE(off >= 0 && off % 4 == 0 && (int64_t)off + (int64_t)up * kp <= table_floats,
+                "pcm_batch_resample: a plan's table does not lie in the blob at a multiple of 4 floats");
+    const int64_t s = rs_span_cap(up, down, K);
+    CUM_REQUIRE(s <= RS_LDS_SPAN_FLOATS,
+                "pcm_batch_resample: the input span of one tile (tile * down / up + K samples) does not fit in LDS");
+    span = s > span ? s : span;
+  }
+  for (int32_t i = 0; i < batch; ++i) {
+    const int32_t *r = recs_host + (int64_t)i * kRsFeedRecInts;
+    const int32_t plan = r[0];
+    const int64_t n_src = r[1], M = r[2], N = r[3];
+    int64_t in0, out0;
+    memcpy(&in0, r + 12, sizeof in0);
+    memcpy(&out0, r + 14, sizeof out0);
+    CUM_REQUIRE(plan >= -1 && plan < n_plans, "pcm_batch_resample: a record names a plan outside the table");
+    CUM_REQUIRE(n_src >= 0 && n_src <= pitch, "pcm_batch_resample: pitch is smaller than a record's n_src");
+    CUM_REQUIRE(in0 >= 0 && out0 >= 0 && in0 <= (INT64_MAX >> 12) && out0 <= (INT64_MAX >> 12),
+                "pcm_batch_resample: a position is negative or beyond 2^51");
+    int64_t up = 1, down = 1, H = 0, K = 1;
+    if (plan >= 0) {
+      const int32_t *p = plans_host + (int64_t)plan * kRsPlanInts;
+      up = p[0], down = p[1], H = (p[2] - 1) / 2, K = p[3];
+    }
+    CUM_REQUIRE(M >= 1 && N >= 1 && M == (N * up + down - 1) / down,
+                "pcm_batch_resample: M must be at least 1 and the output count of the file's N samples");
+    CUM_REQUIRE(out0 == 0 || out0 + len <= M, "pcm_batch_resample: out0 + len exceeds M for a crop that does not start at 0");
+    CUM_REQUIRE(in0 + n_src <= N, "pcm_batch_resample: a window runs past the end of its file");
+    // the window must hold every sample the distinct outputs y[out0, out0 + cnt) read (what lies outside the file is zero)
+    const int64_t cnt = M - out0 < len ? M - out0 : len;
+    const int64_t first = (out0 * down + H) / up - (K - 1);
+    int64_t last = ((out0 + cnt - 1) * down + H) / up;
+    last = last < N - 1 ? last : N - 1;
+    CUM_REQUIRE(in0 == 0 || in0 <= first,
+                "pcm_batch_resample: a window starts behind the oldest sample its first output reads");
+    CUM_REQUIRE(in0 + n_src - 1 >= last, "pcm_batch_resample: a window ends before the newest sample its last output reads");
+  }
+  const dim3 g((unsigned)cdiv64(len, RS_TILE), (unsigned)(2 * batch));
+  const size_t lds = sizeof(float) * (size_t)(span + RS_TILE);
+  hipLaunchKernelGGL(pcm_batch_resample_kernel, g, dim3(RS_THREADS), lds, (hipStream_t)stream, pcm, pitch, recs, plans,
+                     (int)n_plans, tables, (int)batch, len, clean, clean_sb, noisy, noisy_sb, (int)span);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

@@ -210,6 +210,8 @@ SIGNATURES = {
                                     _P, c_i64, c_i64, _P]),
     "cum_resample_slots": (c_i32, [_P, c_i64, c_i32, _P, _P, c_i32, _P, c_i64, _P, _P, c_i32, _P, c_i32, c_i64, _P, c_i32,
                                    c_i64, _P]),
+    "cum_pcm_batch_resample_f32": (c_i32, [_P, c_i64, _P, _P, c_i32, _P, _P, c_i32, _P, c_i64, c_i64, _P, c_i64, _P, c_i64,
+                                           _P]),
 }
 
 _lib = None

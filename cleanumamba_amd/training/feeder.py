@@ -22,8 +22,19 @@ Every call into the GPU runtime is made on the consumer's thread (inside ``next(
 files.  A worker can therefore never disturb a hipGraph capture that the consumer's thread has open, and the consumer
 never calls ``next()`` while it captures.
 
+``BatchFeeder(..., sample_rate=16000)`` -- a RATED feeder -- takes pairs at any sample rate (VCTK-DEMAND and full-band
+DNS ship at 48 kHz; the reference feeds such a pair to the 16 kHz model as if it were 16 kHz, src/util/dataset.py:110-115).
+The crop is drawn in model-rate samples; the workers read the file-rate window its outputs read (util/resample.py:
+``crop_window``), still int16, into rows sized by ``window_bound``; one record per pair -- plan, window, position --
+travels in the slot's tail in the same single upload; and ``into()`` launches cum_pcm_batch_resample_f32
+(csrc/resample.hip) instead: the polyphase chains of DESIGN.md 7g from the int16 windows straight into the step's input
+buffers, bit-identical to ``resample_ragged`` on the whole file, sliced.  Pairs at the model rate pass through it with
+cum_pcm_batch_f32's arithmetic, so an all-16 kHz dataset gives the unrated feeder's plan and batches.  Without
+``sample_rate`` no header rate is read and nothing here changes.
+
 ``device="cpu"`` keeps the same pipeline without pinning or streams and does the kernel's arithmetic with torch on the
-host, so the loop runs anywhere.
+host, so the loop runs anywhere -- a rated feeder too, as long as every pair is at the model rate: there is no CPU
+resampler (util/resample.py), so any other rate is a ValueError at construction.
 """
 import ctypes
 import inspect
@@ -34,9 +45,11 @@ import numpy as np
 import torch
 
 from .. import hip
+from ..util import resample as rs
 
 SAMPLE_RATE = 16000
 PCM_SCALE = 1.0 / 32768.0
+_REC, _PLAN = 16, 8          # int32 per record / plan of a rated batch (csrc/resample.hip: kRsFeedRecInts, kRsPlanInts)
 
 
 def _round_up(n, m):
@@ -44,12 +57,13 @@ def _round_up(n, m):
 
 
 class _Slot:
-    """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths, as one int16 tensor so
-    that it moves in one copy."""
+    """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths -- in a rated feeder by
+    ``batch`` records of 16 int32 -- as one int16 tensor so that it moves in one copy."""
 
-    def __init__(self, batch, pitch, device, pin):
+    def __init__(self, batch, pitch, device, pin, tail_ints=1):
         self.batch, self.pitch = batch, pitch
-        self.flat = torch.zeros(2 * batch * pitch + 2 * batch, dtype=torch.int16, device=device, pin_memory=pin)
+        self.flat = torch.zeros(2 * batch * pitch + 2 * tail_ints * batch, dtype=torch.int16, device=device,
+                                pin_memory=pin)
         self.seq = -1                # the batch this block holds
         self.uploaded = None         # event after the upload (device blocks on a GPU)
         self.released = []           # events after the assembling kernels that read this block
@@ -61,12 +75,17 @@ class _Slot:
     def src_len(self):
         return self.flat[2 * self.batch * self.pitch:].view(torch.int32)
 
+    def records(self):
+        """(batch, 16) int32 view of a rated slot's tail (8-byte aligned: a row is 16 bytes times a whole number)."""
+        return self.flat[2 * self.batch * self.pitch:].view(torch.int32).view(self.batch, _REC)
+
 
 class _Pending:
     """A batch on its way through the staging slots."""
 
-    def __init__(self, seq, epoch, entries):
+    def __init__(self, seq, epoch, entries, windows=None, records=None):
         self.seq, self.epoch, self.entries = seq, epoch, entries
+        self.windows, self.records = windows, records        # a rated feeder's: [(m0, M, rate)], (nb, 16) int32 on the host
         self.todo = len(entries)     # rows not read yet
         self.error = None
 
@@ -74,12 +93,15 @@ class _Pending:
 class PcmBatch:
     """What ``BatchFeeder.next()`` returns: the int16 crops of one batch on the feeder's device.
 
-    fileids: [(clean path, noisy path)] per clip;  entries: the plan's (index, start, count) per clip;  epoch;
-    shape: the (B, 1, L) of the float tensors it assembles."""
+    fileids: [(clean path, noisy path)] per clip;  entries: the plan's (index, start, count) per clip -- the samples read
+    from the files;  epoch;  shape: the (B, 1, L) of the float tensors it assembles;  windows (a rated feeder's, else
+    None): [(m0, M, rate)] per clip -- the clip is outputs [m0, m0 + L) of its file's M model-rate samples, or, with
+    M <= L, all of them repeated."""
 
-    def __init__(self, feeder, seq, epoch, entries, slot):
+    def __init__(self, feeder, seq, epoch, entries, slot, windows=None, records=None):
         self._feeder, self._seq, self._slot = feeder, seq, slot
         self.epoch, self.entries = epoch, entries
+        self.windows, self._records = windows, records
         files = getattr(feeder.dataset, "files", None)
         self.fileids = [tuple(files[i]) if files is not None else i for i, _, _ in entries]
         self.device = feeder.device
@@ -107,7 +129,8 @@ class PcmBatch:
                 raise ValueError(f"PcmBatch.into: {name} must have unit stride along time")
             strides.append(t.stride(0) if nb > 1 else length)
         if self.device.type == "cpu":
-            rows, n = slot.rows(nb), slot.src_len()[:nb].to(torch.int64).clamp(1, length)
+            n = slot.src_len()[:nb] if self._records is None else slot.records()[:nb, 1]     # (rated: all at the model rate)
+            rows, n = slot.rows(nb), n.to(torch.int64).clamp(1, length)
             idx = torch.arange(length)[None, :] % n[:, None]
             for t, sb, src in ((clean, strides[0], rows[0]), (noisy, strides[1], rows[1])):
                 out = torch.as_strided(t, (nb, length), (sb, 1))
@@ -116,9 +139,17 @@ class PcmBatch:
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream()
             stream.wait_event(slot.uploaded)
-            hip.check(hip.lib().cum_pcm_batch_f32(hip.ptr(slot.flat), slot.pitch, hip.ptr(slot.src_len()), nb, length,
-                                                  hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
-                                                  ctypes.c_void_p(stream.cuda_stream)))
+            if self._records is None:
+                hip.check(hip.lib().cum_pcm_batch_f32(hip.ptr(slot.flat), slot.pitch, hip.ptr(slot.src_len()), nb, length,
+                                                      hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
+                                                      ctypes.c_void_p(stream.cuda_stream)))
+            else:
+                f = self._feeder
+                hip.check(hip.lib().cum_pcm_batch_resample_f32(
+                    hip.ptr(slot.flat), slot.pitch, hip.ptr(self._records), hip.ptr(slot.records()), nb,
+                    hip.ptr(f._rs_plan_host), hip.ptr(f._rs_plan_dev), len(f._rs_plans), hip.ptr(f._rs_tables),
+                    0 if f._rs_tables is None else f._rs_tables.numel(), length, hip.ptr(clean), strides[0],
+                    hip.ptr(noisy), strides[1], ctypes.c_void_p(stream.cuda_stream)))
             done = torch.cuda.Event()
             done.record(stream)
             slot.released.append(done)       # the next upload into this block waits for it (on the device)
@@ -136,10 +167,14 @@ class BatchFeeder:
     """``for batch in BatchFeeder(dataset, 16, "cuda:0"): loss, gn = step(batch)`` -- one pass of the loop is one epoch,
     the next ``for`` continues with the next epoch; the workers prefetch across the boundary.
 
-    dataset: anything with ``__len__``, ``pair_length(n)``, ``read_pcm(n, start, count)`` and (for the batch's
-      ``fileids``) ``files``: util/dataset.CleanNoisyPairDataset.
-    crop_length: samples per clip of the batch; default ``int(dataset.crop_length_sec * 16000)``.  A longer clip gives a
-      random window, a shorter one is uploaded whole and repeated on the device.
+    dataset: anything with ``__len__``, ``pair_length(n)``, ``read_pcm(n, start, count)``, (for the batch's ``fileids``)
+      ``files`` and (for a rated feeder) ``pair_rate(n)``: util/dataset.CleanNoisyPairDataset.
+    crop_length: samples per clip of the batch, at the model's rate; default ``int(dataset.crop_length_sec * 16000)``.  A
+      longer clip gives a random window, a shorter one is uploaded whole and repeated on the device.
+    sample_rate: None -- no header rate is read, every file is taken as it is; or the model's rate (16000): every pair's
+      rate is read once here and a pair at another rate is converted on the device while the batch is assembled.  A
+      rate the resampler does not take (util/resample.py: factors above 1024, a tile span beyond the kernels' LDS) is a
+      ValueError naming the file, as is, on the CPU, any rate but the model's.
     depth: staging slots, and the number of further ``next()`` calls a batch stays usable for.
     workers: reader threads (at most; never more than the rows in flight).  Reading is I/O and memcpy, which release the
       interpreter lock; a handful saturates the page cache, and the count is deliberately not taken from the machine's
@@ -148,7 +183,7 @@ class BatchFeeder:
     timeout_s: the longest ``next()`` waits for the readers or an upload before it raises TimeoutError."""
 
     def __init__(self, dataset, batch_size, device, crop_length=None, shuffle=True, seed=0, drop_last=True, depth=2,
-                 workers=4, rank=0, world=1, timeout_s=60):
+                 workers=4, rank=0, world=1, timeout_s=60, sample_rate=None):
         self.dataset = dataset
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -171,14 +206,19 @@ class BatchFeeder:
                              f"{self.batch_size}")
         self._read_into = "out" in inspect.signature(dataset.read_pcm).parameters
 
-        self.pitch = _round_up(self.crop_length, 8)
         gpu = self.device.type == "cuda"
         if gpu:
             hip.lib()                                   # a missing library is an error now, not at the first batch
-        self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu) for _ in range(self.depth)]
+        self.sample_rate = None if sample_rate is None else rs._rate(sample_rate, "sample_rate")
+        need = self.crop_length
+        if self.sample_rate is not None:
+            need = self._read_rates(gpu)
+        self.pitch = _round_up(need, 8)
+        tail = 1 if self.sample_rate is None else _REC
+        self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu, tail) for _ in range(self.depth)]
         self._stage_np = [s.flat.numpy() for s in self._stage]
         # one device block more than staging slots: batch k + 1 is uploaded while k and the depth - 1 before it are live
-        self._dev = [_Slot(self.batch_size, self.pitch, self.device, False) for _ in range(self.depth + 1)]
+        self._dev = [_Slot(self.batch_size, self.pitch, self.device, False, tail) for _ in range(self.depth + 1)]
         self._stream = torch.cuda.Stream(self.device) if gpu else None
 
         self._cv = threading.Condition()
@@ -199,6 +239,63 @@ class BatchFeeder:
         for t in self._threads:
             t.start()
 
+    # ------------------------------------------------------------------ rates
+    def _read_rates(self, gpu):
+        """Every pair's rate, the plans of those that differ from the model's and their tables as one device blob.
+        Returns the longest source window a crop can read, in samples."""
+        files = getattr(self.dataset, "files", None)
+        self._rates = [int(self.dataset.pair_rate(i)) for i in range(len(self.dataset))]
+        self._rs_plans, self._rs_ids = [], {self.sample_rate: -1}
+        need = self.crop_length                         # a pair at the model rate: the crop itself
+        for i, rate in enumerate(self._rates):
+            if rate in self._rs_ids:
+                continue
+            name = " / ".join(files[i]) if files is not None else f"pair {i}"
+            if not gpu:
+                raise ValueError(f"BatchFeeder: {name} is at {rate} Hz, not the model's {self.sample_rate}; converting "
+                                 "needs the GPU (there is no CPU resampler)")
+            try:
+                p = rs.plan(rate, self.sample_rate)
+            except ValueError as exc:
+                raise ValueError(f"BatchFeeder: {name} is at {rate} Hz: {exc}") from exc
+            if max(p.up, p.down) > rs.MAX_FACTOR or rs.tile_span(p.up, p.down, p.K) > rs.LDS_SPAN_FLOATS:
+                raise ValueError(f"BatchFeeder: {name} is at {rate} Hz: {rate} -> {self.sample_rate} reduces to "
+                                 f"{p.up}/{p.down}, whose input span per tile ({rs.tile_span(p.up, p.down, p.K)} samples) "
+                                 "does not fit the kernel's LDS")
+            self._rs_ids[rate] = len(self._rs_plans)
+            self._rs_plans.append(p)
+            need = max(need, rs.window_bound(self.crop_length, p.up, p.down, p.K))
+        self._rs_plan_host = self._rs_plan_dev = self._rs_tables = None
+        if self._rs_plans:
+            ints = torch.zeros(len(self._rs_plans), _PLAN, dtype=torch.int32)
+            tabs, off = [], 0
+            for i, p in enumerate(self._rs_plans):
+                ints[i, :6] = torch.tensor([p.up, p.down, len(p.taps), p.K, p.pitch, off], dtype=torch.int32)
+                tabs.append(p.host_table().reshape(-1))
+                off += p.up * p.pitch
+            self._rs_plan_host = ints
+            self._rs_plan_dev = ints.to(self.device)
+            self._rs_tables = torch.cat(tabs).to(self.device)
+        return need
+
+    def _factors(self, rate):
+        """up, down, H, K of ``rate`` -> the model's rate (1, 1, 0, 1 for the model's rate itself: y[m] = x[m])."""
+        k = self._rs_ids[rate]
+        if k < 0:
+            return 1, 1, 0, 1
+        p = self._rs_plans[k]
+        return p.up, p.down, p.H, p.K
+
+    def _records(self, entries, windows):
+        """The (nb, 16) int32 record table of one batch (include/cleanumamba_hip.h: cum_pcm_batch_resample_f32)."""
+        recs = torch.zeros(len(entries), _REC, dtype=torch.int32)
+        pos = recs.view(torch.int64)                    # in0: ints 12-13, out0: ints 14-15
+        for r, ((index, start, count), (m0, M, rate)) in enumerate(zip(entries, windows)):
+            recs[r, :4] = torch.tensor([self._rs_ids[rate], count, M, int(self.dataset.pair_length(index))],
+                                       dtype=torch.int32)
+            pos[r, 6], pos[r, 7] = start, m0
+        return recs
+
     # ------------------------------------------------------------------ plan
     def __len__(self):
         """Batches per epoch (of this rank)."""
@@ -207,25 +304,44 @@ class BatchFeeder:
         return -(-self.per_rank // self.batch_size)
 
     def plan(self, epoch):
-        """[[(index, start, count)] per batch] of ``epoch`` for this rank: a function of (seed, epoch, rank, world, the
-        clips' lengths) alone.  The crop start of a clip is drawn for every position of the permutation, so a rank's
-        draws do not depend on the other ranks' clip lengths."""
+        """[[(index, start, count)] per batch] of ``epoch`` for this rank -- the samples the workers read: a function of
+        (seed, epoch, rank, world, the clips' lengths and, in a rated feeder, rates) alone.  The crop start of a clip is
+        drawn for every position of the permutation, so a rank's draws do not depend on the other ranks' clip lengths.
+        A rated feeder draws the crop in model-rate samples -- a file of M = ceil(N up / down) of them gives outputs
+        [m0, m0 + crop_length), m0 = min(int(u (M - crop_length + 1)), M - crop_length), or all M when M <= crop_length
+        -- and plans ``resample.crop_window`` of it; at the model rate that is the unrated plan."""
+        return self._plan_full(epoch)[0]
+
+    def _plan_full(self, epoch):
+        """(the plan, [[(m0, M, rate)] per batch] or None)."""
         n = len(self.dataset)
         rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch)]))
         perm = rng.permutation(n) if self.shuffle else np.arange(n)
         u = rng.random(n)
-        entries = []
+        entries, windows = [], []
         for pos in range(self.rank, n, self.world)[:self.per_rank]:
             index = int(perm[pos])
             length = int(self.dataset.pair_length(index))
             if length < 1:
                 raise ValueError(f"pair {index} of the dataset is empty")
-            if length <= self.crop_length:
+            if self.sample_rate is not None:
+                rate = self._rates[index]
+                up, down, H, K = self._factors(rate)
+                M = rs.out_length(length, up, down)
+                m0, count = 0, M
+                if M > self.crop_length:
+                    room = M - self.crop_length
+                    m0, count = min(int(u[pos] * (room + 1)), room), self.crop_length
+                entries.append((index,) + rs.crop_window(length, up, down, H, K, m0, count))
+                windows.append((m0, M, rate))
+            elif length <= self.crop_length:
                 entries.append((index, 0, length))
             else:
                 room = length - self.crop_length
                 entries.append((index, min(int(u[pos] * (room + 1)), room), self.crop_length))
-        return [entries[i:i + self.batch_size] for i in range(0, len(self) * self.batch_size, self.batch_size)]
+        cuts = range(0, len(self) * self.batch_size, self.batch_size)
+        return ([entries[i:i + self.batch_size] for i in cuts],
+                [windows[i:i + self.batch_size] for i in cuts] if self.sample_rate is not None else None)
 
     # ------------------------------------------------------------------ workers
     def _take_row(self):
@@ -238,15 +354,25 @@ class BatchFeeder:
         plan = self._plan_cache.get(epoch)
         if plan is None:
             try:
-                plan = self.plan(epoch)
+                plan = self._plan_full(epoch)
             except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
                 self._failure = exc
                 self._cv.notify_all()
                 return None
             self._plan_cache = {epoch: plan}
+        plan, windows = plan
         pend = self._pending.get(self._next_seq)
         if pend is None:
-            pend = self._pending[self._next_seq] = _Pending(self._next_seq, epoch, plan[b])
+            if windows is None:
+                pend = _Pending(self._next_seq, epoch, plan[b])
+            else:
+                try:
+                    pend = _Pending(self._next_seq, epoch, plan[b], windows[b], self._records(plan[b], windows[b]))
+                except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
+                    self._failure = exc
+                    self._cv.notify_all()
+                    return None
+            self._pending[self._next_seq] = pend
         taken, row = row, row + 1
         if row == len(plan[b]):
             row, b, self._next_seq = 0, b + 1, self._next_seq + 1
@@ -282,7 +408,8 @@ class BatchFeeder:
                         if src.dtype != np.int16 or src.shape != (count,):
                             raise ValueError(f"read_pcm returned {src.dtype} {src.shape}, not int16 ({count},)")
                         dst[:count] = src
-                flat[2 * self.batch_size * self.pitch:].view(np.int32)[r] = count
+                if pend.records is None:                # (a rated batch's tail is its record table: _upload writes it)
+                    flat[2 * self.batch_size * self.pitch:].view(np.int32)[r] = count
             except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next() with the file's name
                 files = getattr(self.dataset, "files", None)
                 name = " / ".join(files[index]) if files is not None else f"pair {index}"
@@ -299,6 +426,8 @@ class BatchFeeder:
     def _upload(self, pend):
         """Issue the upload of a fully staged batch into its device block (consumer's thread)."""
         stage, dev = self._stage[pend.seq % self.depth], self._dev[pend.seq % (self.depth + 1)]
+        if pend.records is not None:
+            stage.records()[:len(pend.entries)] = pend.records
         if self._stream is None:
             dev.flat.copy_(stage.flat)
         else:
@@ -366,7 +495,7 @@ class BatchFeeder:
                                        f"{self.timeout_s:g} s")
                 time.sleep(1e-3)
         self.wait_upload_s += time.monotonic() - t1
-        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev)
+        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev, pend.windows, pend.records)
         with self._cv:
             del self._pending[seq]
             self._returned = seq + 1                    # frees staging slot seq % depth; batch seq - depth goes stale

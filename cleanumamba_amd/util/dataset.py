@@ -7,8 +7,9 @@ Differences on the host side:
     the crop and keeps them int16 until the last moment; the reference decodes the whole of both files to float to keep
     a third of them.  Every other encoding (float32, 24-bit, several channels: channel 0 is taken, as the reference's
     noisy-only dataset does) goes through ``scipy.io.wavfile`` and is scaled as util/denoise_eval._read_float scales.
-  * ``pair_length(n)`` and ``read_pcm(n, start, count)`` expose the header and a raw int16 range of a pair: the fast
-    route of training/feeder.py, which leaves scaling and tiling to the device (csrc/pcm.hip).
+  * ``pair_length(n)``, ``pair_rate(n)`` and ``read_pcm(n, start, count)`` expose the header and a raw int16 range of a
+    pair: the fast route of training/feeder.py, which leaves scaling, tiling and -- with ``sample_rate`` -- the conversion
+    to the model's rate to the device (csrc/pcm.hip, csrc/resample.hip).
   * the file-count assertions look at the directories the chosen layout reads (the reference always counts
     ``training_set``, also for ``subset="testing"``).
 The reference's import-time ``random.seed(0) / torch.manual_seed(0) / np.random.seed(0)`` is not repeated: importing a
@@ -205,6 +206,12 @@ class CleanNoisyPairDataset(Dataset):
     def pair_length(self, n):
         """Samples per channel of pair n, from the headers."""
         return self.pair_info(n)[0].frames
+
+    def pair_rate(self, n):
+        """Sample rate of pair n, from the headers.  A pair whose files disagree is an AssertionError naming both."""
+        clean, noisy = self.pair_info(n)
+        assert clean.rate == noisy.rate, f"Sample rate mismatch in {self.files[n]}, {clean.rate} vs {noisy.rate}"
+        return clean.rate
 
     def read_pcm(self, n, start, count, out=None):
         """Samples [start, start + count) of both files of pair n as two int16 arrays, reading nothing else.  ``out``: a

@@ -10,6 +10,9 @@ The test set layouts are the reference's: DNS (``clean/clean_fileid_{i}.wav`` an
   * every clip is scored in one batched call on the GPU (cleanumamba_amd.util.python_eval.eval_waveforms); PESQ and
     the composites built on it are NaN unless the ``pesq`` package is installed.
   * ``metrics`` is accepted and, as in the reference, not used.
+  * ``resample=True`` takes a test set that is not at 16 kHz (VCTK-DEMAND and full-band DNS ship at 48 kHz): both files
+    of such a pair are converted on the GPU (util/resample.py) before anything else, and the pair is denoised and scored
+    at 16 kHz.  Without it such a pair is denoised as if it were 16 kHz and the metrics refuse its rate, as before.
 """
 import os
 
@@ -19,6 +22,7 @@ from scipy.io import wavfile
 
 from .python_eval import eval_waveforms
 
+MODEL_RATE = 16000
 KEYS = ("pesq_wb", "pesq_nb", "stoi", "CSIG", "CBAK", "COVL", "wss_dist", "segSNR", "llr_mean", "count")
 
 
@@ -33,6 +37,20 @@ def _read_float(path):
         x = x.astype(np.float32)
     x = x.reshape(x.shape[0], -1).T if x.ndim == 2 else x[None]
     return rate, torch.from_numpy(np.ascontiguousarray(x))
+
+
+def _to_model_rate(path, rate, device):
+    """Channel rows of ``path`` at MODEL_RATE: (channels, M) float32 on the host, through ``resample_ragged`` -- from the
+    int16 samples themselves where the file is 16-bit PCM, from ``_read_float``'s floats otherwise."""
+    from .resample import resample_ragged
+    _, x = wavfile.read(path)
+    if x.dtype == np.int16:
+        rows = torch.from_numpy(np.ascontiguousarray(x.reshape(x.shape[0], -1).T if x.ndim == 2 else x[None]))
+    else:
+        rows = _read_float(path)[1]
+    rows = rows.contiguous().reshape(-1).reshape(rows.shape)     # (a numpy ``x[None]`` row comes with stride 0)
+    y, lens = resample_ragged(rows.to(device), [rows.shape[1]] * rows.shape[0], rate, MODEL_RATE)
+    return y[:, :lens[0]].cpu()
 
 
 def _pairs(testset_path, validation, VCTK_DEMAND, test_factor):
@@ -60,9 +78,12 @@ def _pairs(testset_path, validation, VCTK_DEMAND, test_factor):
 
 
 def validate(net, testset_path, quantize_audio_input=False, network_processor=None, validation=True, VCTK_DEMAND=False,
-             metrics=("pesq_wb", "pesq_nb", "stoi", "DNSMOS"), test_factor=1.0, crop=None, batch_size=16):
+             metrics=("pesq_wb", "pesq_nb", "stoi", "DNSMOS"), test_factor=1.0, crop=None, batch_size=16, resample=False):
     """Denoise the test set with ``net`` and return the reference's dict of length-weighted sums ('Test/pesq_wb', ...,
-    'Test/llr_mean') plus 'Test/count', the total length; divide by 'Test/count' for the means."""
+    'Test/llr_mean') plus 'Test/count', the total length; divide by 'Test/count' for the means.
+
+    resample: convert a pair whose header rate is not 16000 first, on the GPU: noisy from its samples to float32, clean
+    likewise and back to int16 as ``(y * 32768).round().clamp(-32768, 32767)``; ``crop`` then counts seconds at 16 kHz."""
     result = {"Test/" + k: 0 for k in KEYS}
     device, half = torch.device("cuda"), False
     for p in getattr(net, "parameters", lambda: iter(()))():
@@ -72,7 +93,12 @@ def validate(net, testset_path, quantize_audio_input=False, network_processor=No
     clips = []                                    # (rate, clean int16, noisy (1, L) float32)
     for c, nz in _pairs(testset_path, validation, VCTK_DEMAND, test_factor):
         rate, clean = wavfile.read(c)
-        _, noisy = _read_float(nz)
+        if resample and rate != MODEL_RATE:
+            noisy = _to_model_rate(nz, rate, device)
+            clean = (_to_model_rate(c, rate, device)[0] * 32768).round().clamp(-32768, 32767).to(torch.int16).numpy()
+            rate = MODEL_RATE
+        else:
+            _, noisy = _read_float(nz)
         clips.append((rate, clean, noisy))
 
     def prepare(x):

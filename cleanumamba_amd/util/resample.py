@@ -17,6 +17,8 @@ samples only, which is what makes a clip's result independent of its batch and a
   stream_step      one push of a stream: outputs now final, history to keep (pure; StreamResampler and the stream pool's
                    rated slots, network/streampool.py); history_bound, tile_span: what sizes the pool's rows, what the
                    kernels' LDS admits
+  crop_window      the source samples that outputs [m0, m0 + count) of a file read; window_bound: the longest such range
+                   (pure; what a rated training/feeder.py stages for cum_pcm_batch_resample_f32)
   resample_ragged  a ragged batch in one launch
   StreamResampler  push / finish over signals of any length, bit-identical to ``resample_ragged`` on the whole signal
 
@@ -79,6 +81,22 @@ def tile_span(up, down, K):
     """Floats of LDS one workgroup's input span needs (csrc/resample.hip: rs_span_cap); the kernels take a pair only if
     this is at most ``LDS_SPAN_FLOATS``."""
     return (int(K) + ((int(up) - 1) + (RS_TILE - 1) * int(down)) // int(up) + 16 + 7) // 8 * 8
+
+
+def crop_window(N, up, down, H, K, m0, count):
+    """(n_lo, n_cnt): the samples [n_lo, n_lo + n_cnt) of an N-sample file that its outputs [m0, m0 + count) read -- from
+    the oldest tap of the first, (m0 down + H) // up - (K - 1), to the n_hi of the last, both cut to the file.  Every other
+    sample may be anything (or absent): the outputs' sums over the window alone are the sums over the whole file."""
+    N, up, down, H, K, m0, count = (int(v) for v in (N, up, down, H, K, m0, count))
+    n_hi = min(((m0 + count - 1) * down + H) // up, N - 1)
+    n_lo = min(max((m0 * down + H) // up - (K - 1), 0), n_hi)
+    return n_lo, n_hi - n_lo + 1
+
+
+def window_bound(count, up, down, K):
+    """The longest ``crop_window`` of ``count`` outputs, whatever the file and the position: the n_hi of the last output
+    is at most ceil((count - 1) down / up) behind that of the first, which has K - 1 taps before it."""
+    return ((int(count) - 1) * int(down) + int(up) - 1) // int(up) + int(K)
 
 
 class Plan:

@@ -919,6 +919,33 @@ int cum_resample_slots(float *hist, int64_t hist_pitch, int32_t capacity, const 
                        int32_t n_plans, const float *tables, int64_t table_floats, const int32_t *recs_host,
                        const int32_t *recs, int32_t n_recs, const float *x, int32_t x_rows, int64_t x_pitch, float *y,
                        int32_t y_rows, int64_t y_pitch, void *stream);
+/* cum_pcm_batch_resample_f32: cum_pcm_batch_f32 for pairs at any mix of sample rates (training/feeder.py with
+ *   sample_rate): one launch from the int16 source windows of a batch to the model-rate float crops of
+ *   both signals, with the chains of cum_resample_ragged bit for bit (the kernels inline one device function).
+ *   pcm: 2 * batch rows `pitch` int16 apart, row b the clean clip, row batch + b the noisy clip of pair b.
+ *   Plans and `tables`: as for cum_resample_slots (n_plans may be 0: plans and tables may then be NULL).
+ *   Record b = 16 int32 {plan, n_src, M, N, 0 x 8, in0 (int64 in ints 12-13), out0 (int64 in ints 14-15)}, one per pair:
+ *     both rows hold samples [in0, in0 + n_src) of a file of N samples, a sample being pcm x 2^-15; y is the conversion
+ *     of the whole file under `plan` (what lies outside the file is zero), M = ceil(N up / down) outputs long; plan -1:
+ *     the pair is at the model rate, y[m] = pcm[m - in0] 2^-15 (cum_pcm_batch_f32's arithmetic, exact) and M = N.
+ *       clean[b clean_sb + t] = y_clean[(out0 + t) mod M],  noisy[b noisy_sb + t] = y_noisy[(out0 + t) mod M],  t < len
+ *     with out0 + len <= M (a crop) or out0 = 0 (a file of M <= len outputs repeated to fill the crop).  Every output is
+ *     computed once; the repeats are copies.  16-byte loads of whole aligned chunks inside the window, 16-byte stores
+ *     from a row's first 16-byte boundary on.  Nothing is read behind n_src, nothing is written behind len.  The kernel
+ *     clamps n_src into [0, pitch], M to >= 1 and the positions into [0, 2^51] (out0 below M), and skips a record whose
+ *     plan id is outside the table, so a bad device table never indexes outside a row.
+ *   recs / plans: device tables; recs_host / plans_host: the same in host memory, checked before the launch.  No
+ *   workspace, no atomics; LDS 4 (span + cum_resample_tile) bytes, span the largest tile span of the plans.
+ *   CUM_EINVAL before any launch: a null or misaligned pointer (pcm, clean, noisy, tables 16 bytes; records 8; plans 4),
+ *   batch outside [1, 32767], len < 1, pitch not a multiple of 8 or below a record's n_src, clean_sb or noisy_sb below
+ *   len, a plan id outside [-1, n_plans), plan fields outside the limits of cum_resample_ragged (the LDS span included)
+ *   or a table outside the blob, M < 1 or not ceil(N up / down), out0 + len > M with out0 != 0, a negative position, a
+ *   window that runs past its file, that starts behind the oldest sample its first output reads (unless it starts the
+ *   file) or ends before the newest sample its last output reads (unless it ends the file). */
+int cum_pcm_batch_resample_f32(const int16_t *pcm, int64_t pitch, const int32_t *recs_host, const int32_t *recs,
+                               int32_t batch, const int32_t *plans_host, const int32_t *plans, int32_t n_plans,
+                               const float *tables, int64_t table_floats, int64_t len, float *clean, int64_t clean_sb,
+                               float *noisy, int64_t noisy_sb, void *stream);
 
 #ifdef __cplusplus
 }
