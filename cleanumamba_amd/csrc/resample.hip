@@ -20,7 +20,7 @@
 //   up > 3 (the 160/441-type ratios, tables of tens of KB): neighbouring outputs use different rows; every lane reads
 //     its own row in place through L2, 16 bytes per load.
 // Results are gathered in LDS and leave as whole coalesced rows.
-#include <string.h>
+#include <stdio.h>
 
 #include <vector>
 
@@ -47,6 +47,86 @@ struct RsArgs {
 static inline int64_t rs_span_cap(int64_t up, int64_t down, int64_t K) {
   const int64_t dq = ((up - 1) + (int64_t)(RS_TILE - 1) * down) / up;
   return (K + dq + 16 + 7) / 8 * 8;
+}
+
+// The int32 fields of a plan row and of the slots and feeder records, as include/cleanumamba_hip.h describes them
+enum RsPlanField { kPlUp, kPlDown, kPlTaps, kPlK, kPlPitch, kPlOffset, kRsPlanInts = 8 };
+enum RsSlotField { kSlSlot, kSlPlan, kSlNHist, kSlXRow, kSlNNew, kSlNOut, kSlYRow, kSlEnds, kSlKeep, kSlParity, kSlYCol };
+enum RsFeedField { kFdPlan, kFdNSrc, kFdM, kFdN };
+enum { kRsRecIn0 = 12, kRsRecOut0 = 14, kRsRecInts = 16 };   // both records: the int64 positions, the size
+constexpr int64_t kRsPosMax = INT64_MAX >> 12;               // 2^51: the largest position a record may carry
+
+// an int64 position of a record (records are 8-byte aligned, on the host as on the device)
+__host__ __device__ __forceinline__ int64_t rs_pos(const int32_t *rec, const int field) {
+  int64_t v;
+  __builtin_memcpy(&v, __builtin_assume_aligned(rec + field, 8), sizeof v);
+  return v;
+}
+
+// outputs of `total` samples: all at the signal's end, else the final ones (early returns: the ragged kernels' SGPRs)
+__host__ __device__ inline int64_t rs_final_outputs(int64_t total, int64_t up, int64_t down, int64_t H, bool ends) {
+  const int64_t all = (total * up + down - 1) / down;
+  if (ends) return all;
+  const int64_t part = total * up - H;
+  if (part <= 0) return 0;
+  const int64_t fin = (part + down - 1) / down;
+  return fin < all ? fin : all;
+}
+
+// position of the oldest sample output out0 reads: its n_hi less the K - 1 taps behind it
+__host__ __device__ inline int64_t rs_first_tap(int64_t out0, int64_t up, int64_t down, int64_t H, int64_t K) {
+  return (out0 * down + H) / up - (K - 1);
+}
+
+// The input span of one tile: outputs m0 .. m0 + nt - 1 of a signal whose staged row starts at absolute position in0.
+//   r0: c mod up of the first output;  rel_base: row index of the first staged sample, the oldest sample the first output
+//   reads floored to a chunk of E samples;  off: what the flooring added, in [0, E);  need: LDS floats the tile reads.
+struct RsTile { int r0, off, need; int64_t rel_base; };
+template <int E>
+__device__ __forceinline__ RsTile rs_tile_geometry(const int64_t m0, const int nt, const int64_t in0, const int up,
+                                                   const int down, const int H, const int K, const int span_cap) {
+  RsTile t;
+  const int64_t c0 = m0 * down + H;                         // >= 0
+  t.r0 = (int)(c0 - c0 / up * up);
+  const int64_t rel_first = rs_first_tap(m0, up, down, H, K) - in0;
+  t.rel_base = (rel_first >= 0 ? rel_first / E : -((-rel_first + E - 1) / E)) * E;   // floor to a chunk
+  t.off = (int)(rel_first - t.rel_base);
+  const int need = K + (t.r0 + (nt - 1) * down) / up + t.off;
+  t.need = need > span_cap ? span_cap : need;               // (never: span_cap is sized for it)
+  return t;
+}
+
+// Stage row[rel_base, rel_base + need) as f32 in xs, 16 bytes per load where the chunk lies inside [0, n) and the row is
+// 16-byte aligned (`wide`); before the signal and behind its n samples: zero.  int16 is scaled by 2^-15.
+template <typename S>
+__device__ __forceinline__ void rs_stage_span(float *__restrict__ xs, const S *__restrict__ row, const int64_t n,
+                                              const int64_t rel_base, const int need, const bool wide) {
+  constexpr int E = sizeof(S) == 2 ? 8 : 4;                 // samples of one 16-byte chunk
+  for (int c = threadIdx.x; c * E < need; c += RS_THREADS) {
+    const int64_t s0 = rel_base + (int64_t)c * E;           // a multiple of E: the chunk is 16-byte aligned when the row is
+    float v[E];
+    if (wide && s0 >= 0 && s0 + E <= n) {
+      if constexpr (sizeof(S) == 2) {
+        const rs_short8 s = *reinterpret_cast<const rs_short8 *>(row + s0);
+#pragma unroll
+        for (int j = 0; j < 8; ++j) v[j] = (float)s[j] * kRsPcm;
+      } else {
+        const rs_float4 s = *reinterpret_cast<const rs_float4 *>(row + s0);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) v[j] = s[j];
+      }
+    } else {
+#pragma unroll
+      for (int j = 0; j < E; ++j) {
+        float s = 0.f;
+        if (s0 + j >= 0 && s0 + j < n) s = sizeof(S) == 2 ? (float)row[s0 + j] * kRsPcm : (float)row[s0 + j];
+        v[j] = s;
+      }
+    }
+#pragma unroll
+    for (int j = 0; j < E; j += 4)
+      *reinterpret_cast<rs_float4 *>(xs + c * E + j) = rs_float4{v[j], v[j + 1], v[j + 2], v[j + 3]};
+  }
 }
 
 // The chains of one tile: outputs o = 0 .. nt - 1, output o = sum_{j < K} x0[dq(o) - j] table[r(o)][j] with
@@ -116,6 +196,20 @@ __device__ __forceinline__ void rs_tile_chains(const float *__restrict__ x0, con
   }
 }
 
+// ... with the route taken from `up` on the device (workgroup-uniform): for kernels whose workgroups differ in their pair
+__device__ __forceinline__ void rs_tile_chains_any(const float *__restrict__ x0, const float *__restrict__ table,
+                                                   float *__restrict__ ys, const int r0, const int nt, const int up,
+                                                   const int down, const int K, const int kp) {
+  if (up == 1)
+    rs_tile_chains<1>(x0, table, ys, r0, nt, up, down, K, kp);
+  else if (up == 2)
+    rs_tile_chains<2>(x0, table, ys, r0, nt, up, down, K, kp);
+  else if (up == 3)
+    rs_tile_chains<3>(x0, table, ys, r0, nt, up, down, K, kp);
+  else
+    rs_tile_chains<0>(x0, table, ys, r0, nt, up, down, K, kp);
+}
+
 // x: rows of S; origin: [batch][2] = absolute input position of x_b[0], absolute output position of y_b[0] (or null);
 // UP: the up factor on the scalar-tap route (1, 2, 3), 0 for any other.
 template <typename S, int UP>
@@ -124,64 +218,23 @@ __global__ __launch_bounds__(RS_THREADS) void resample_ragged_kernel(const S *__
                                                                     const float *__restrict__ table, float *__restrict__ y,
                                                                     const RsArgs a) {
   extern __shared__ __attribute__((aligned(16))) float rs_lds[];
-  constexpr int E = sizeof(S) == 2 ? 8 : 4;                 // samples of one 16-byte chunk
   const int b = blockIdx.y;
   int64_t n = len[b];
   n = n < 0 ? 0 : (n > a.lmax ? a.lmax : n);
   const int64_t in0 = origin ? origin[2 * b] : 0, out0 = origin ? origin[2 * b + 1] : 0;
-  // outputs this clip has: all of the signal's when it ends here, else those no later sample can change
-  const int64_t total = in0 + n;
-  const int64_t all = (total * a.up + a.down - 1) / a.down;
-  int64_t fin = total * a.up - a.H;
-  fin = fin <= 0 ? 0 : (fin + a.down - 1) / a.down;
-  int64_t n_out = (a.ends ? all : (fin < all ? fin : all)) - out0;
+  int64_t n_out = rs_final_outputs(in0 + n, a.up, a.down, a.H, a.ends) - out0;
   n_out = n_out < 0 ? 0 : (n_out > a.max_out ? a.max_out : n_out);
   const int64_t t0 = (int64_t)blockIdx.x * RS_TILE;
   if (t0 >= n_out) return;
   const int nt = n_out - t0 < RS_TILE ? (int)(n_out - t0) : RS_TILE;
-
-  const int64_t c0 = (out0 + t0) * a.down + a.H;            // >= 0
-  const int64_t q0 = c0 / a.up;
-  const int r0 = (int)(c0 - q0 * a.up);
-  const int64_t rel_first = q0 - (a.K - 1) - in0;           // row index of the oldest sample the first output reads
-  const int64_t rel_base = (rel_first >= 0 ? rel_first / E : -((-rel_first + E - 1) / E)) * E;   // floor to a chunk
-  const int off = (int)(rel_first - rel_base);              // in [0, E)
-  const int dq_last = (r0 + (nt - 1) * a.down) / a.up;
-  int need = a.K + dq_last + off;                           // LDS floats the tile reads: [0, need)
-  need = need > a.span_cap ? a.span_cap : need;             // (never: span_cap is sized for it)
-
+  const RsTile t = rs_tile_geometry<sizeof(S) == 2 ? 8 : 4>(out0 + t0, nt, in0, a.up, a.down, a.H, a.K, a.span_cap);
   float *__restrict__ xs = rs_lds;
   float *__restrict__ ys = rs_lds + a.span_cap;             // the tile's RS_TILE results
   const S *__restrict__ row = x + (int64_t)b * a.in_pitch;
-  const bool wide = (reinterpret_cast<uintptr_t>(row) & 15) == 0;
-  for (int c = threadIdx.x; c * E < need; c += RS_THREADS) {
-    const int64_t s0 = rel_base + (int64_t)c * E;           // a multiple of E: the chunk is 16-byte aligned when the row is
-    float v[E];
-    if (wide && s0 >= 0 && s0 + E <= n) {
-      if constexpr (sizeof(S) == 2) {
-        const rs_short8 s = *reinterpret_cast<const rs_short8 *>(row + s0);
-#pragma unroll
-        for (int j = 0; j < 8; ++j) v[j] = (float)s[j] * kRsPcm;
-      } else {
-        const rs_float4 s = *reinterpret_cast<const rs_float4 *>(row + s0);
-#pragma unroll
-        for (int j = 0; j < 4; ++j) v[j] = s[j];
-      }
-    } else {
-#pragma unroll
-      for (int j = 0; j < E; ++j) {
-        float s = 0.f;                                      // before the signal, behind the clip's length: zero
-        if (s0 + j >= 0 && s0 + j < n) s = sizeof(S) == 2 ? (float)row[s0 + j] * kRsPcm : (float)row[s0 + j];
-        v[j] = s;
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < E; j += 4)
-      *reinterpret_cast<rs_float4 *>(xs + c * E + j) = rs_float4{v[j], v[j + 1], v[j + 2], v[j + 3]};
-  }
+  rs_stage_span(xs, row, n, t.rel_base, t.need, (reinterpret_cast<uintptr_t>(row) & 15) == 0);
   __syncthreads();
-  const float *__restrict__ x0 = xs + (a.K - 1) + off;      // x[n_hi] of the tile's first output; output o: x0[dq(o)]
-  rs_tile_chains<UP>(x0, table, ys, r0, nt, a.up, a.down, a.K, a.kp);
+  const float *__restrict__ x0 = xs + (a.K - 1) + t.off;    // x[n_hi] of the tile's first output; output o: x0[dq(o)]
+  rs_tile_chains<UP>(x0, table, ys, t.r0, nt, a.up, a.down, a.K, a.kp);
   __syncthreads();
   float *__restrict__ dst = y + (int64_t)b * a.out_pitch + t0;
   for (int o = threadIdx.x; o < nt; o += RS_THREADS) dst[o] = ys[o];
@@ -207,15 +260,8 @@ static void rs_launch(const void *x, const int32_t *len, const int64_t *origin, 
 // inputs an unfinished output may still read.  hist: [capacity][2][hist_pitch] f32 -- TWO rows per slot; a record reads
 // row `parity` and writes the next history to row `1 - parity`, so the workgroups of a record (one per tile of its
 // outputs) never read what one of them writes, in whatever order they run.  The signal a record sees is
-// hist[slot][parity][0, n_hist) ++ x[x_row][0, n_new), its first sample at absolute position in0.
-//
-// Plan p = 8 int32 {up, down, n_taps, K, table_pitch, table_offset, 0, 0}: the polyphase table of the pair starts
-//   table_offset floats into `tables`.
-// Record r = 16 int32 {slot, plan, n_hist, x_row, n_new, n_out, y_row, ends, keep, parity, y_col, 0, in0 lo, in0 hi,
-//   out0 lo, out0 hi}:  y[y_row][y_col + o] = output out0 + o of the signal, o < n_out, and
-//   hist[slot][1 - parity][0, keep) = the last `keep` samples of the signal.
-constexpr int kRsRecInts = 16, kRsPlanInts = 8;
-
+// hist[slot][parity][0, n_hist) ++ x[x_row][0, n_new), its first sample at absolute position in0.  Plan rows
+// (RsPlanField) and records (RsSlotField): include/cleanumamba_hip.h, cum_resample_slots.
 __global__ __launch_bounds__(RS_THREADS) void resample_slots_kernel(const int32_t *__restrict__ recs,
                                                                    const int32_t *__restrict__ plans,
                                                                    const float *__restrict__ tables, float *hist,
@@ -224,49 +270,36 @@ __global__ __launch_bounds__(RS_THREADS) void resample_slots_kernel(const int32_
                                                                    const int64_t y_pitch, const int span_cap) {
   extern __shared__ __attribute__((aligned(16))) float rs_lds[];
   const int32_t *__restrict__ rec = recs + (int64_t)blockIdx.y * kRsRecInts;      // workgroup-uniform, as all below
-  const int slot = rec[0], n_hist = rec[2], n_new = rec[4], n_out = rec[5], keep = rec[8], parity = rec[9];
+  const int slot = rec[kSlSlot], n_hist = rec[kSlNHist], n_new = rec[kSlNNew], n_out = rec[kSlNOut];
+  const int keep = rec[kSlKeep], parity = rec[kSlParity];
   const int tiles = (n_out + RS_TILE - 1) / RS_TILE;
   const int tile = blockIdx.x, last = tiles > 0 ? tiles - 1 : 0;
   if (tile > last) return;
-  const int32_t *__restrict__ pl = plans + (int64_t)rec[1] * kRsPlanInts;
-  const int up = pl[0], down = pl[1], H = (pl[2] - 1) / 2, K = pl[3], kp = pl[4];
-  const float *__restrict__ table = tables + pl[5];
-  const int64_t in0 = *reinterpret_cast<const int64_t *>(rec + 12), out0 = *reinterpret_cast<const int64_t *>(rec + 14);
+  const int32_t *__restrict__ pl = plans + (int64_t)rec[kSlPlan] * kRsPlanInts;
+  const int up = pl[kPlUp], down = pl[kPlDown], H = (pl[kPlTaps] - 1) / 2, K = pl[kPlK], kp = pl[kPlPitch];
+  const float *__restrict__ table = tables + pl[kPlOffset];
+  const int64_t in0 = rs_pos(rec, kRsRecIn0), out0 = rs_pos(rec, kRsRecOut0);
   const float *hold = hist + ((int64_t)slot * 2 + parity) * hist_pitch;
   float *hnew = hist + ((int64_t)slot * 2 + (parity ^ 1)) * hist_pitch;
-  const float *__restrict__ xr = x + (int64_t)rec[3] * x_pitch;
+  const float *__restrict__ xr = x + (int64_t)rec[kSlXRow] * x_pitch;
   const int n = n_hist + n_new;                              // samples of the signal this record holds
 
   if (tile < tiles) {
     const int t0 = tile * RS_TILE;
     const int nt = n_out - t0 < RS_TILE ? n_out - t0 : RS_TILE;
-    const int64_t c0 = (out0 + t0) * down + H;               // >= 0
-    const int64_t q0 = c0 / up;
-    const int r0 = (int)(c0 - q0 * up);
-    const int64_t rel_first = q0 - (K - 1) - in0;            // index in the signal of the oldest sample the tile reads
-    const int dq_last = (r0 + (nt - 1) * down) / up;
-    int need = K + dq_last;                                  // LDS floats the tile reads: [0, need)
-    need = need > span_cap ? span_cap : need;                // (never: span_cap is sized for it)
+    const RsTile t = rs_tile_geometry<1>(out0 + t0, nt, in0, up, down, H, K, span_cap);   // no chunks: off = 0
     float *__restrict__ xs = rs_lds;
     float *__restrict__ ys = rs_lds + span_cap;              // the tile's RS_TILE results
-    for (int i = threadIdx.x; i < need; i += RS_THREADS) {
-      const int64_t s = rel_first + i;
+    for (int i = threadIdx.x; i < t.need; i += RS_THREADS) {
+      const int64_t s = t.rel_base + i;
       float v = 0.f;                                         // before the signal, behind what has arrived: zero
       if (s >= 0 && s < n) v = s < n_hist ? hold[s] : xr[s - n_hist];
       xs[i] = v;
     }
     __syncthreads();
-    const float *__restrict__ x0 = xs + (K - 1);             // x[n_hi] of the tile's first output
-    if (up == 1)
-      rs_tile_chains<1>(x0, table, ys, r0, nt, up, down, K, kp);
-    else if (up == 2)
-      rs_tile_chains<2>(x0, table, ys, r0, nt, up, down, K, kp);
-    else if (up == 3)
-      rs_tile_chains<3>(x0, table, ys, r0, nt, up, down, K, kp);
-    else
-      rs_tile_chains<0>(x0, table, ys, r0, nt, up, down, K, kp);
+    rs_tile_chains_any(xs + (K - 1), table, ys, t.r0, nt, up, down, K, kp);   // xs[K - 1]: x[n_hi] of the first output
     __syncthreads();
-    float *__restrict__ dst = y + (int64_t)rec[6] * y_pitch + rec[10] + t0;
+    float *__restrict__ dst = y + (int64_t)rec[kSlYRow] * y_pitch + rec[kSlYCol] + t0;
     for (int o = threadIdx.x; o < nt; o += RS_THREADS) dst[o] = ys[o];
   }
   if (tile == last) {
@@ -282,13 +315,10 @@ __global__ __launch_bounds__(RS_THREADS) void resample_slots_kernel(const int32_
 // clip, row batch + b the noisy clip, `pitch` int16 apart -- but a row holds the window of its file, at the file's rate,
 // that the crop reads, and leaves as the model-rate crop in the step's input buffers.
 //
-// Record b = 16 int32 {plan, n_src, M, N, 0 x 8, in0 (int64 in ints 12-13), out0 (int64 in ints 14-15)}, one per PAIR:
-//   plan: index into `plans` (the cum_resample_slots layout), -1 = the pair is at the model rate (up = down = K = 1,
-//   H = 0, the tap 1: y[m] = x[m]);  n_src: samples staged in both rows, absolute positions [in0, in0 + n_src) of a
-//   file of N samples with M = ceil(N up / down) outputs;  out[t] = y[(out0 + t) mod M], t < len.
+// One record per PAIR (RsFeedField; include/cleanumamba_hip.h, cum_pcm_batch_resample_f32): plan -1 = the pair is at the
+// model rate (up = down = K = 1, H = 0, the tap 1: y[m] = x[m]);  out[t] = y[(out0 + t) mod M], t < len.
 // A workgroup owns RS_TILE outputs m = out0 + t0 + o of one row, computes each ONCE and stores it to every t = t0 + o + k M
 // below len, so a tiled clip repeats bit for bit.
-constexpr int kRsFeedRecInts = 16;
 constexpr int RS_COPY_SPAN = RS_TILE + 8;    // LDS floats a tile of a model-rate row stages (its outputs + chunk slack)
 
 // ys[0, n) -> dst[0, n) by the whole workgroup: 16-byte stores from dst's first 16-byte boundary on, elements around them
@@ -311,19 +341,17 @@ __global__ __launch_bounds__(RS_THREADS) void pcm_batch_resample_kernel(
     const int64_t len, float *__restrict__ clean, const int64_t clean_sb, float *__restrict__ noisy,
     const int64_t noisy_sb, const int span_cap) {
   extern __shared__ __attribute__((aligned(16))) float rs_lds[];
-  constexpr int E = 8;                                       // samples of one 16-byte chunk
   const int r = blockIdx.y;
   const int b = r < batch ? r : r - batch;
-  const int32_t *__restrict__ rec = recs + (int64_t)b * kRsFeedRecInts;          // workgroup-uniform, as all below
-  const int plan = rec[0];
+  const int32_t *__restrict__ rec = recs + (int64_t)b * kRsRecInts;              // workgroup-uniform, as all below
+  const int plan = rec[kFdPlan];
   if (plan < -1 || plan >= n_plans) return;
   // a bad table can never index outside a row: n in [0, pitch], M >= 1, positions in [0, 2^51], out0 < M
-  constexpr int64_t kPosMax = INT64_MAX >> 12;
-  int64_t n = rec[1], M = rec[2];
+  int64_t n = rec[kFdNSrc], M = rec[kFdM];
   n = n < 0 ? 0 : (n > pitch ? pitch : n);
   M = M < 1 ? 1 : M;
-  int64_t in0 = *reinterpret_cast<const int64_t *>(rec + 12), out0 = *reinterpret_cast<const int64_t *>(rec + 14);
-  in0 = in0 < 0 ? 0 : (in0 > kPosMax ? kPosMax : in0);
+  int64_t in0 = rs_pos(rec, kRsRecIn0), out0 = rs_pos(rec, kRsRecOut0);
+  in0 = in0 < 0 ? 0 : (in0 > kRsPosMax ? kRsPosMax : in0);
   out0 = out0 < 0 ? 0 : (out0 > M - 1 ? M - 1 : out0);
   const int64_t cnt = M - out0 < len ? M - out0 : len;       // distinct outputs the row needs: y[out0, out0 + cnt)
   const int64_t t0 = (int64_t)blockIdx.x * RS_TILE;
@@ -334,53 +362,19 @@ __global__ __launch_bounds__(RS_THREADS) void pcm_batch_resample_kernel(
   const float *__restrict__ table = tables;
   if (plan >= 0) {
     const int32_t *__restrict__ pl = plans + (int64_t)plan * kRsPlanInts;
-    up = pl[0], down = pl[1], H = (pl[2] - 1) / 2, K = pl[3], kp = pl[4];
-    table = tables + pl[5];
+    up = pl[kPlUp], down = pl[kPlDown], H = (pl[kPlTaps] - 1) / 2, K = pl[kPlK], kp = pl[kPlPitch];
+    table = tables + pl[kPlOffset];
   }
-  const int64_t c0 = (out0 + t0) * down + H;                 // >= 0
-  const int64_t q0 = c0 / up;
-  const int r0 = (int)(c0 - q0 * up);
-  const int64_t rel_first = q0 - (K - 1) - in0;              // row index of the oldest sample the first output reads
-  const int64_t rel_base = (rel_first >= 0 ? rel_first / E : -((-rel_first + E - 1) / E)) * E;   // floor to a chunk
-  const int off = (int)(rel_first - rel_base);               // in [0, E)
-  const int dq_last = (r0 + (nt - 1) * down) / up;
-  int need = K + dq_last + off;                              // LDS floats the tile reads: [0, need)
-  need = need > span_cap ? span_cap : need;                  // (never: span_cap is sized for it)
+  const RsTile t = rs_tile_geometry<8>(out0 + t0, nt, in0, up, down, H, K, span_cap);
 
   float *__restrict__ xs = rs_lds;
   float *ys = rs_lds + span_cap;                             // the tile's RS_TILE results
-  const int16_t *__restrict__ row = pcm + (int64_t)r * pitch;                    // 16-byte aligned: pitch % 8 == 0
-  for (int c = threadIdx.x; c * E < need; c += RS_THREADS) {
-    const int64_t s0 = rel_base + (int64_t)c * E;            // a multiple of E: the chunk is 16-byte aligned
-    float v[E];
-    if (s0 >= 0 && s0 + E <= n) {
-      const rs_short8 s = *reinterpret_cast<const rs_short8 *>(row + s0);
-#pragma unroll
-      for (int j = 0; j < E; ++j) v[j] = (float)s[j] * kRsPcm;
-    } else {
-#pragma unroll
-      for (int j = 0; j < E; ++j) {
-        float s = 0.f;                                       // before the window, behind its n_src samples: zero
-        if (s0 + j >= 0 && s0 + j < n) s = (float)row[s0 + j] * kRsPcm;
-        v[j] = s;
-      }
-    }
-    *reinterpret_cast<rs_float4 *>(xs + c * E) = rs_float4{v[0], v[1], v[2], v[3]};
-    *reinterpret_cast<rs_float4 *>(xs + c * E + 4) = rs_float4{v[4], v[5], v[6], v[7]};
-  }
+  rs_stage_span(xs, pcm + (int64_t)r * pitch, n, t.rel_base, t.need, true);      // 16-byte aligned: pitch % 8 == 0
   __syncthreads();
-  const float *__restrict__ x0 = xs + (K - 1) + off;         // x[n_hi] of the tile's first output; output o: x0[dq(o)]
   if (plan < 0) {
-    ys = xs + off;                                           // the model rate: output o IS staged sample o (exact)
+    ys = xs + t.off;                                         // the model rate: output o IS staged sample o (exact)
   } else {
-    if (up == 1)
-      rs_tile_chains<1>(x0, table, ys, r0, nt, up, down, K, kp);
-    else if (up == 2)
-      rs_tile_chains<2>(x0, table, ys, r0, nt, up, down, K, kp);
-    else if (up == 3)
-      rs_tile_chains<3>(x0, table, ys, r0, nt, up, down, K, kp);
-    else
-      rs_tile_chains<0>(x0, table, ys, r0, nt, up, down, K, kp);
+    rs_tile_chains_any(xs + (K - 1) + t.off, table, ys, t.r0, nt, up, down, K, kp);
     __syncthreads();
   }
   // a file that fits the tile and is repeated: lay whole periods side by side first, so the replicas leave in runs of
@@ -397,6 +391,50 @@ __global__ __launch_bounds__(RS_THREADS) void pcm_batch_resample_kernel(
     rs_store_run(dst + tb, ys, len - tb < nt ? (int)(len - tb) : nt);
 }
 
+// ---- host checks shared by the three entries: CUM_EINVAL with "<who>: <what>" as the error ----------------------------
+static int rs_fail(const char *who, const char *what) {
+  char msg[256];
+  snprintf(msg, sizeof msg, "%s: %s", who, what);
+  cum_set_error(msg);
+  return CUM_EINVAL;
+}
+#define RS_REQUIRE(cond, what)              /* in a function with a `who` */ \
+  do {                                      \
+    if (!(cond)) return rs_fail(who, what); \
+  } while (0)
+
+// the factors, tap count, K and table pitch of one pair; *span: the LDS floats its tile span needs, which must fit
+static int rs_check_plan(const char *who, int64_t up, int64_t down, int64_t taps, int64_t K, int64_t kp, int64_t *span) {
+  RS_REQUIRE(up >= 1 && down >= 1, "up and down must be at least 1");
+  RS_REQUIRE(up <= 1024 && down <= 1024, "up and down must be at most 1024 (reduce the ratio)");
+  RS_REQUIRE(taps >= 1 && (taps & 1) == 1, "the tap count must be odd (taps h[0 .. 2H])");
+  RS_REQUIRE(K >= 1 && K * up >= taps, "K * up is smaller than the tap count");
+  RS_REQUIRE(kp >= K && kp % 4 == 0, "table_pitch must be a multiple of 4 floats and at least K");
+  *span = rs_span_cap(up, down, K);
+  RS_REQUIRE(*span <= RS_LDS_SPAN_FLOATS, "the input span of one tile (tile * down / up + K samples) does not fit in LDS");
+  return CUM_OK;
+}
+
+// every row of a plan table, and its table inside the blob; *span grows to the largest tile span of the plans
+static int rs_check_plan_table(const char *who, const int32_t *plans_host, int32_t n_plans, int64_t table_floats,
+                               int64_t *span) {
+  for (int32_t i = 0; i < n_plans; ++i) {
+    const int32_t *p = plans_host + (int64_t)i * kRsPlanInts;
+    int64_t s;
+    if (rs_check_plan(who, p[kPlUp], p[kPlDown], p[kPlTaps], p[kPlK], p[kPlPitch], &s)) return CUM_EINVAL;
+    RS_REQUIRE(p[kPlOffset] >= 0 && p[kPlOffset] % 4 == 0 &&
+                   p[kPlOffset] + (int64_t)p[kPlUp] * p[kPlPitch] <= table_floats,
+               "a plan's table does not lie in the blob at a multiple of 4 floats");
+    *span = s > *span ? s : *span;
+  }
+  return CUM_OK;
+}
+
+static int rs_check_positions(const char *who, int64_t in0, int64_t out0) {
+  RS_REQUIRE(in0 >= 0 && out0 >= 0 && in0 <= kRsPosMax && out0 <= kRsPosMax, "a position is negative or beyond 2^51");
+  return CUM_OK;
+}
+
 }  // namespace cum
 
 using namespace cum;
@@ -409,12 +447,8 @@ extern "C" int cum_resample_ragged(int32_t src_i16, const void *x, int32_t batch
                                    int64_t out_pitch, int64_t max_out, void *stream) {
   CUM_REQUIRE(src_i16 == 0 || src_i16 == 1, "resample_ragged: src_i16 must be 0 (f32 rows) or 1 (int16 rows)");
   CUM_REQUIRE(batch >= 1 && batch <= 65534, "resample_ragged: batch must be in [1, 65534]");
-  CUM_REQUIRE(up >= 1 && down >= 1, "resample_ragged: up and down must be at least 1");
-  CUM_REQUIRE(up <= 1024 && down <= 1024, "resample_ragged: up and down must be at most 1024 (reduce the ratio)");
-  CUM_REQUIRE(n_taps >= 1 && (n_taps & 1) == 1, "resample_ragged: the tap count must be odd (taps h[0 .. 2H])");
-  CUM_REQUIRE(K >= 1 && (int64_t)K * up >= n_taps, "resample_ragged: K * up is smaller than the tap count");
-  CUM_REQUIRE(table_pitch >= K && table_pitch % 4 == 0,
-              "resample_ragged: table_pitch must be a multiple of 4 floats and at least K");
+  int64_t span;
+  if (rs_check_plan("resample_ragged", up, down, n_taps, K, table_pitch, &span)) return CUM_EINVAL;
   CUM_REQUIRE(table != nullptr, "resample_ragged: null table");
   CUM_REQUIRE(lmax >= 0 && in_pitch >= 0 && out_pitch >= 0 && max_out >= 0,
               "resample_ragged: negative pitch or length");
@@ -424,9 +458,6 @@ extern "C" int cum_resample_ragged(int32_t src_i16, const void *x, int32_t batch
   CUM_REQUIRE((reinterpret_cast<uintptr_t>(x) & (src_i16 ? 1 : 3)) == 0 && (reinterpret_cast<uintptr_t>(len) & 3) == 0 &&
                   (reinterpret_cast<uintptr_t>(y) & 3) == 0 && (reinterpret_cast<uintptr_t>(origin) & 7) == 0,
               "resample_ragged: x, len, origin or y is misaligned");
-  const int64_t span = rs_span_cap(up, down, K);
-  CUM_REQUIRE(span <= RS_LDS_SPAN_FLOATS,
-              "resample_ragged: the input span of one tile (tile * down / up + K samples) does not fit in LDS");
   if (max_out == 0) return CUM_OK;
   RsArgs a;
   a.lmax = lmax, a.in_pitch = in_pitch, a.out_pitch = out_pitch, a.max_out = max_out;
@@ -461,31 +492,16 @@ extern "C" int cum_resample_slots(float *hist, int64_t hist_pitch, int32_t capac
                   (reinterpret_cast<uintptr_t>(y) & 3) == 0,
               "resample_slots: hist, plans, recs, x or y is misaligned (records 8 bytes, the rest 4)");
   int64_t span = 0;
-  for (int32_t i = 0; i < n_plans; ++i) {
-    const int32_t *p = plans_host + (int64_t)i * kRsPlanInts;
-    const int32_t up = p[0], down = p[1], n_taps = p[2], K = p[3], kp = p[4], off = p[5];
-    CUM_REQUIRE(up >= 1 && down >= 1, "resample_slots: up and down must be at least 1");
-    CUM_REQUIRE(up <= 1024 && down <= 1024, "resample_slots: up and down must be at most 1024 (reduce the ratio)");
-    CUM_REQUIRE(n_taps >= 1 && (n_taps & 1) == 1, "resample_slots: the tap count must be odd (taps h[0 .. 2H])");
-    CUM_REQUIRE(K >= 1 && (int64_t)K * up >= n_taps, "resample_slots: K * up is smaller than the tap count");
-    CUM_REQUIRE(kp >= K && kp % 4 == 0, "resample_slots: table_pitch must be a multiple of 4 floats and at least K");
-    CUM_REQUIRE(off >= 0 && off % 4 == 0 && (int64_t)off + (int64_t)up * kp <= table_floats,
-                "resample_slots: a plan's table does not lie in the blob at a multiple of 4 floats");
-    const int64_t s = rs_span_cap(up, down, K);
-    CUM_REQUIRE(s <= RS_LDS_SPAN_FLOATS,
-                "resample_slots: the input span of one tile (tile * down / up + K samples) does not fit in LDS");
-    span = s > span ? s : span;
-  }
+  if (rs_check_plan_table("resample_slots", plans_host, n_plans, table_floats, &span)) return CUM_EINVAL;
   if (n_recs == 0) return CUM_OK;
   std::vector<uint8_t> named((size_t)capacity, 0);
   int32_t tiles = 1;
   for (int32_t i = 0; i < n_recs; ++i) {
     const int32_t *r = recs_host + (int64_t)i * kRsRecInts;
-    const int32_t slot = r[0], plan = r[1], n_hist = r[2], x_row = r[3], n_new = r[4], n_out = r[5], y_row = r[6];
-    const int32_t ends = r[7], keep = r[8], parity = r[9], y_col = r[10];
-    int64_t in0, out0;
-    memcpy(&in0, r + 12, sizeof in0);
-    memcpy(&out0, r + 14, sizeof out0);
+    const int32_t slot = r[kSlSlot], plan = r[kSlPlan], n_hist = r[kSlNHist], x_row = r[kSlXRow], n_new = r[kSlNNew];
+    const int32_t n_out = r[kSlNOut], y_row = r[kSlYRow], ends = r[kSlEnds], keep = r[kSlKeep], parity = r[kSlParity];
+    const int32_t y_col = r[kSlYCol];
+    const int64_t in0 = rs_pos(r, kRsRecIn0), out0 = rs_pos(r, kRsRecOut0);
     CUM_REQUIRE(slot >= 0 && slot < capacity, "resample_slots: a record names a slot outside the pool (slot < capacity)");
     CUM_REQUIRE(!named[slot], "resample_slots: a slot is named twice");
     named[slot] = 1;
@@ -499,19 +515,14 @@ extern "C" int cum_resample_slots(float *hist, int64_t hist_pitch, int32_t capac
     CUM_REQUIRE(n_out >= 0 && y_col >= 0 && (int64_t)y_col + n_out <= y_pitch &&
                     (n_out == 0 || (y_row >= 0 && y_row < y_rows)),
                 "resample_slots: the outputs do not fit the rows of y");
-    CUM_REQUIRE(in0 >= 0 && out0 >= 0 && in0 <= (INT64_MAX >> 12) && out0 <= (INT64_MAX >> 12),
-                "resample_slots: a position is negative or beyond 2^51");
+    if (rs_check_positions("resample_slots", in0, out0)) return CUM_EINVAL;
     // the outputs asked for must exist: all of the signal's when it ends here, else those no later sample can change
     const int32_t *p = plans_host + (int64_t)plan * kRsPlanInts;
-    const int64_t up = p[0], down = p[1], H = (p[2] - 1) / 2, K = p[3];
-    const int64_t total = in0 + n_hist + n_new;
-    const int64_t all = (total * up + down - 1) / down;
-    int64_t fin = total * up - H;
-    fin = fin <= 0 ? 0 : (fin + down - 1) / down;
-    CUM_REQUIRE(out0 + n_out <= (ends ? all : (fin < all ? fin : all)),
+    const int64_t up = p[kPlUp], down = p[kPlDown], H = (p[kPlTaps] - 1) / 2, K = p[kPlK];
+    CUM_REQUIRE(out0 + n_out <= rs_final_outputs(in0 + n_hist + n_new, up, down, H, ends != 0),
                 "resample_slots: more outputs than the samples received make final");
     // ... and the history must reach back to the oldest sample the first of them reads
-    CUM_REQUIRE(n_out == 0 || in0 == 0 || (out0 * down + H) / up - (K - 1) >= in0,
+    CUM_REQUIRE(n_out == 0 || in0 == 0 || rs_first_tap(out0, up, down, H, K) >= in0,
                 "resample_slots: the history starts behind the oldest sample the first output reads");
     const int32_t t = (n_out + RS_TILE - 1) / RS_TILE;
     tiles = t > tiles ? t : tiles;
@@ -543,36 +554,19 @@ extern "C" int cum_pcm_batch_resample_f32(const int16_t *pcm, int64_t pitch, con
                   (reinterpret_cast<uintptr_t>(plans) & 3) == 0 && (reinterpret_cast<uintptr_t>(plans_host) & 3) == 0,
               "pcm_batch_resample: recs or plans is misaligned (records 8 bytes, plans 4)");
   int64_t span = RS_COPY_SPAN;
-  for (int32_t i = 0; i < n_plans; ++i) {
-    const int32_t *p = plans_host + (int64_t)i * kRsPlanInts;
-    const int32_t up = p[0], down = p[1], n_taps = p[2], K = p[3], kp = p[4], off = p[5];
-    CUM_REQUIRE(up >= 1 && down >= 1, "pcm_batch_resample: up and down must be at least 1");
-    CUM_REQUIRE(up <= 1024 && down <= 1024, "pcm_batch_resample: up and down must be at most 1024 (reduce the ratio)");
-    CUM_REQUIRE(n_taps >= 1 && (n_taps & 1) == 1, "pcm_batch_resample: the tap count must be odd (taps h[0 .. 2H])");
-    CUM_REQUIRE(K >= 1 && (int64_t)K * up >= n_taps, "pcm_batch_resample: K * up is smaller than the tap count");
-    CUM_REQUIRE(kp >= K && kp % 4 == 0, "pcm_batch_resample: table_pitch must be a multiple of 4 floats and at least K");
-    CUM_REQUIRE(off >= 0 && off % 4 == 0 && (int64_t)off + (int64_t)up * kp <= table_floats,
-                "pcm_batch_resample: a plan's table does not lie in the blob at a multiple of 4 floats");
-    const int64_t s = rs_span_cap(up, down, K);
-    CUM_REQUIRE(s <= RS_LDS_SPAN_FLOATS,
-                "pcm_batch_resample: the input span of one tile (tile * down / up + K samples) does not fit in LDS");
-    span = s > span ? s : span;
-  }
+  if (rs_check_plan_table("pcm_batch_resample", plans_host, n_plans, table_floats, &span)) return CUM_EINVAL;
   for (int32_t i = 0; i < batch; ++i) {
-    const int32_t *r = recs_host + (int64_t)i * kRsFeedRecInts;
-    const int32_t plan = r[0];
-    const int64_t n_src = r[1], M = r[2], N = r[3];
-    int64_t in0, out0;
-    memcpy(&in0, r + 12, sizeof in0);
-    memcpy(&out0, r + 14, sizeof out0);
+    const int32_t *r = recs_host + (int64_t)i * kRsRecInts;
+    const int32_t plan = r[kFdPlan];
+    const int64_t n_src = r[kFdNSrc], M = r[kFdM], N = r[kFdN];
+    const int64_t in0 = rs_pos(r, kRsRecIn0), out0 = rs_pos(r, kRsRecOut0);
     CUM_REQUIRE(plan >= -1 && plan < n_plans, "pcm_batch_resample: a record names a plan outside the table");
     CUM_REQUIRE(n_src >= 0 && n_src <= pitch, "pcm_batch_resample: pitch is smaller than a record's n_src");
-    CUM_REQUIRE(in0 >= 0 && out0 >= 0 && in0 <= (INT64_MAX >> 12) && out0 <= (INT64_MAX >> 12),
-                "pcm_batch_resample: a position is negative or beyond 2^51");
+    if (rs_check_positions("pcm_batch_resample", in0, out0)) return CUM_EINVAL;
     int64_t up = 1, down = 1, H = 0, K = 1;
     if (plan >= 0) {
       const int32_t *p = plans_host + (int64_t)plan * kRsPlanInts;
-      up = p[0], down = p[1], H = (p[2] - 1) / 2, K = p[3];
+      up = p[kPlUp], down = p[kPlDown], H = (p[kPlTaps] - 1) / 2, K = p[kPlK];
     }
     CUM_REQUIRE(M >= 1 && N >= 1 && M == (N * up + down - 1) / down,
                 "pcm_batch_resample: M must be at least 1 and the output count of the file's N samples");
@@ -580,7 +574,7 @@ extern "C" int cum_pcm_batch_resample_f32(const int16_t *pcm, int64_t pitch, con
     CUM_REQUIRE(in0 + n_src <= N, "pcm_batch_resample: a window runs past the end of its file");
     // the window must hold every sample the distinct outputs y[out0, out0 + cnt) read (what lies outside the file is zero)
     const int64_t cnt = M - out0 < len ? M - out0 : len;
-    const int64_t first = (out0 * down + H) / up - (K - 1);
+    const int64_t first = rs_first_tap(out0, up, down, H, K);
     int64_t last = ((out0 + cnt - 1) * down + H) / up;
     last = last < N - 1 ? last : N - 1;
     CUM_REQUIRE(in0 == 0 || in0 <= first,

@@ -38,7 +38,6 @@ from . import hopplan
 from . import streaming
 
 _REC = 8        # int32 per record of both tables (csrc/hop.hip: kHopItemInts, kStageRecInts)
-_RS_REC, _RS_PLAN = 16, 8   # int32 per record / plan of the conversion (csrc/resample.hip: kRsRecInts, kRsPlanInts)
 
 Schedule = collections.namedtuple("Schedule", "first n_hops offset consumed remainder")
 
@@ -85,9 +84,7 @@ class StreamPool:
         if capacity < 1:
             raise ValueError("stream pool: capacity must be >= 1")
         self.model, self.capacity = model, capacity
-        # conversion of rated slots (one plan pair per rate the pool has seen)
-        self._rs_plans, self._rs_ids = [], {}                 # Plans: [2 k] rate -> model, [2 k + 1] model -> rate
-        self._rs_plan_host = self._rs_plan_dev = self._rs_tables = self.rs_hist = None
+        self._rs, self.rs_hist = rs.PlanTable("cpu"), None    # rated slots' plan pairs (_adopt moves them)
         self._adopt(hopplan.HopPlan(model))
         self._open = np.zeros(capacity, dtype=bool)
         self._pend = np.zeros(capacity, dtype=np.int64)       # samples in hist[slot]
@@ -126,10 +123,10 @@ class StreamPool:
             raise ValueError(f"stream pool: {n} slots asked for, {free.size} of {self.capacity} free")
         got = free[:n]
         if rate and n:
-            k = self._register(rate)
-            for d in (0, 1):
-                p = self._rs_plans[k + d]
-                self._rs_par[got, d] = (k + d, p.up, p.down, p.H, p.K)
+            for d, pair in enumerate(((rate, self.model_rate), (self.model_rate, rate))):
+                p = rs.plan(*pair)
+                self._rs_par[got, d] = (self._rs.add(p), p.up, p.down, p.H, p.K)
+            self._rs_size_hist()
         self._rate[got] = rate
         self._open[got] = True
         return [int(s) for s in got]
@@ -143,41 +140,16 @@ class StreamPool:
             return 0
         for pair in ((r, self.model_rate), (self.model_rate, r)):
             try:
-                p = rs.plan(*pair)
+                rs.check_fits(rs.plan(*pair))
             except ValueError as exc:
                 raise ValueError(f"stream pool: rate {r}: {exc}") from exc
-            if rs.tile_span(p.up, p.down, p.K) > rs.LDS_SPAN_FLOATS:
-                raise ValueError(f"stream pool: rate {r}: {pair[0]} -> {pair[1]} reduces to {p.up}/{p.down}, whose input "
-                                 f"span per tile ({rs.tile_span(p.up, p.down, p.K)} samples) does not fit the kernel's LDS")
         return r
 
-    def _register(self, rate):
-        """The id of ``rate``'s plan pair (in: id, out: id + 1); a rate the pool has not seen extends the plan table and
-        the table blob on the device, and the history rows if its filters are longer."""
-        if rate in self._rs_ids:
-            return self._rs_ids[rate]
-        k = len(self._rs_plans)
-        self._rs_plans += [rs.plan(rate, self.model_rate), rs.plan(self.model_rate, rate)]
-        self._rs_ids[rate] = k
-        self._rs_upload()
-        return k
-
-    def _rs_upload(self):
-        plans = self._rs_plans
-        if not plans:
-            return
-        ints = np.zeros((len(plans), _RS_PLAN), dtype=np.int32)
-        tabs, off = [], 0
-        for i, p in enumerate(plans):
-            ints[i, :6] = (p.up, p.down, len(p.taps), p.K, p.pitch, off)
-            tabs.append(p.host_table().reshape(-1))
-            off += p.up * p.pitch
-        self._rs_plan_host = torch.from_numpy(ints)
-        self._rs_plan_dev = self._rs_plan_host.to(self.device)
-        self._rs_tables = torch.cat(tabs).to(self.device)
-        pitch = hopplan._rup(max(max(rs.history_bound(p.K) for p in plans), 1), 4)
+    def _rs_size_hist(self):
+        """History rows on the pool's device that hold the longest filter of the plan table (none while it is empty)."""
+        pitch = hopplan._rup(max([rs.history_bound(p.K) for p in self._rs.plans] + [1]), 4)
         old = self.rs_hist
-        if old is None or old.shape[3] < pitch or old.device != self.device:
+        if self._rs.plans and (old is None or old.shape[3] < pitch or old.device != self.device):
             # [direction][slot][parity][pitch]: the inputs a slot's unfinished outputs may still read, two rows each
             self.rs_hist = torch.zeros(2, self.capacity, 2, pitch, dtype=torch.float32, device=self.device)
             if old is not None and old.device == self.device:
@@ -215,7 +187,8 @@ class StreamPool:
         self.hop, self.frame_len, self.device = plan.hop, plan.frame_len, plan.device
         self.state = torch.zeros(self.capacity, plan.state_stride, dtype=torch.float32, device=self.device)
         self.hist = torch.zeros(self.capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32, device=self.device)
-        self._rs_upload()                   # (the conversion tables follow the model's device)
+        self._rs.to(self.device)            # (the conversion tables follow the model's device)
+        self._rs_size_hist()
 
     def invalidate_packed_weights(self):
         """Re-pack the weight blob on the next call (``CleanUMamba.invalidate_packed_weights`` calls this)."""
@@ -362,12 +335,14 @@ class StreamPool:
         if act.size == 0:
             return
         sa = s[act]
-        rec = np.zeros((act.size, _RS_REC), dtype=np.int32)
-        rec[:, 0], rec[:, 1], rec[:, 2] = sa, self._rs_par[sa, d, 0], pos[act, 0] - pos[act, 2]
-        rec[:, 3], rec[:, 4], rec[:, 5], rec[:, 6] = src_rows[act], lens[act], count[act], dst_rows[act]
-        rec[:, 7], rec[:, 8], rec[:, 9] = int(bool(ends)), got[act] - base[act], self._rs_parity[sa, d]
-        wide = rec.view(np.int64)                        # ints 12-13: the history's position, 14-15: the first output's
-        wide[:, 6], wide[:, 7] = pos[act, 2], pos[act, 1]
+        rec = np.zeros((act.size, rs.REC_INTS), dtype=np.int32)
+        rec[:, rs.SLOT_SLOT], rec[:, rs.SLOT_PLAN] = sa, self._rs_par[sa, d, 0]
+        rec[:, rs.SLOT_N_HIST], rec[:, rs.SLOT_KEEP] = pos[act, 0] - pos[act, 2], got[act] - base[act]
+        rec[:, rs.SLOT_X_ROW], rec[:, rs.SLOT_N_NEW], rec[:, rs.SLOT_N_OUT] = src_rows[act], lens[act], count[act]
+        rec[:, rs.SLOT_Y_ROW], rec[:, rs.SLOT_ENDS] = dst_rows[act], int(bool(ends))
+        rec[:, rs.SLOT_PARITY] = self._rs_parity[sa, d]
+        wide = rec.view(np.int64)                        # the history's position, the first output's
+        wide[:, rs.REC_IN0 // 2], wide[:, rs.REC_OUT0 // 2] = pos[act, 2], pos[act, 1]
         self._rs_parity[sa, d] ^= 1
         host = torch.from_numpy(rec).pin_memory()
         drec = host.to(self.device, non_blocking=True)
@@ -375,9 +350,8 @@ class StreamPool:
         rows, pitch = (0, 0) if src is None else (src.shape[0], max(src.stride(0), src.shape[1]))
         with torch.cuda.device(self.device):
             hip.check(hip.lib().cum_resample_slots(
-                hip.ptr(hist), hist.stride(1), self.capacity, hip.ptr(self._rs_plan_host), hip.ptr(self._rs_plan_dev),
-                len(self._rs_plans), hip.ptr(self._rs_tables), self._rs_tables.numel(), hip.ptr(host), hip.ptr(drec),
-                act.size, None if rows == 0 else hip.ptr(src), rows, pitch, hip.ptr(dst), dst.shape[0],
+                hip.ptr(hist), hist.stride(1), self.capacity, *self._rs.args(), hip.ptr(host), hip.ptr(drec), act.size,
+                None if rows == 0 else hip.ptr(src), rows, pitch, hip.ptr(dst), dst.shape[0],
                 max(dst.stride(0), dst.shape[1]), hip.stream_ptr()))
 
     def _feed_rated(self, a, x, lengths, rated):

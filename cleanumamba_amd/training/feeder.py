@@ -49,7 +49,6 @@ from ..util import resample as rs
 
 SAMPLE_RATE = 16000
 PCM_SCALE = 1.0 / 32768.0
-_REC, _PLAN = 16, 8          # int32 per record / plan of a rated batch (csrc/resample.hip: kRsFeedRecInts, kRsPlanInts)
 
 
 def _round_up(n, m):
@@ -77,7 +76,7 @@ class _Slot:
 
     def records(self):
         """(batch, 16) int32 view of a rated slot's tail (8-byte aligned: a row is 16 bytes times a whole number)."""
-        return self.flat[2 * self.batch * self.pitch:].view(torch.int32).view(self.batch, _REC)
+        return self.flat[2 * self.batch * self.pitch:].view(torch.int32).view(self.batch, rs.REC_INTS)
 
 
 class _Pending:
@@ -129,7 +128,7 @@ class PcmBatch:
                 raise ValueError(f"PcmBatch.into: {name} must have unit stride along time")
             strides.append(t.stride(0) if nb > 1 else length)
         if self.device.type == "cpu":
-            n = slot.src_len()[:nb] if self._records is None else slot.records()[:nb, 1]     # (rated: all at the model rate)
+            n = slot.src_len()[:nb] if self._records is None else slot.records()[:nb, rs.FEED_N_SRC]     # (model rate)
             rows, n = slot.rows(nb), n.to(torch.int64).clamp(1, length)
             idx = torch.arange(length)[None, :] % n[:, None]
             for t, sb, src in ((clean, strides[0], rows[0]), (noisy, strides[1], rows[1])):
@@ -144,12 +143,10 @@ class PcmBatch:
                                                       hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
                                                       ctypes.c_void_p(stream.cuda_stream)))
             else:
-                f = self._feeder
                 hip.check(hip.lib().cum_pcm_batch_resample_f32(
                     hip.ptr(slot.flat), slot.pitch, hip.ptr(self._records), hip.ptr(slot.records()), nb,
-                    hip.ptr(f._rs_plan_host), hip.ptr(f._rs_plan_dev), len(f._rs_plans), hip.ptr(f._rs_tables),
-                    0 if f._rs_tables is None else f._rs_tables.numel(), length, hip.ptr(clean), strides[0],
-                    hip.ptr(noisy), strides[1], ctypes.c_void_p(stream.cuda_stream)))
+                    *self._feeder._rs.args(), length, hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
+                    ctypes.c_void_p(stream.cuda_stream)))
             done = torch.cuda.Event()
             done.record(stream)
             slot.released.append(done)       # the next upload into this block waits for it (on the device)
@@ -214,7 +211,7 @@ class BatchFeeder:
         if self.sample_rate is not None:
             need = self._read_rates(gpu)
         self.pitch = _round_up(need, 8)
-        tail = 1 if self.sample_rate is None else _REC
+        tail = 1 if self.sample_rate is None else rs.REC_INTS
         self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu, tail) for _ in range(self.depth)]
         self._stage_np = [s.flat.numpy() for s in self._stage]
         # one device block more than staging slots: batch k + 1 is uploaded while k and the depth - 1 before it are live
@@ -241,11 +238,11 @@ class BatchFeeder:
 
     # ------------------------------------------------------------------ rates
     def _read_rates(self, gpu):
-        """Every pair's rate, the plans of those that differ from the model's and their tables as one device blob.
-        Returns the longest source window a crop can read, in samples."""
+        """Every pair's rate and the plan table (``_rs``; ``_rs_ids``: rate -> plan id, -1 the model's) of those that
+        differ from the model's.  Returns the longest source window a crop can read, in samples."""
         files = getattr(self.dataset, "files", None)
         self._rates = [int(self.dataset.pair_rate(i)) for i in range(len(self.dataset))]
-        self._rs_plans, self._rs_ids = [], {self.sample_rate: -1}
+        self._rs, self._rs_ids = rs.PlanTable(self.device), {self.sample_rate: -1}
         need = self.crop_length                         # a pair at the model rate: the crop itself
         for i, rate in enumerate(self._rates):
             if rate in self._rs_ids:
@@ -256,44 +253,27 @@ class BatchFeeder:
                                  "needs the GPU (there is no CPU resampler)")
             try:
                 p = rs.plan(rate, self.sample_rate)
+                rs.check_fits(p)
             except ValueError as exc:
                 raise ValueError(f"BatchFeeder: {name} is at {rate} Hz: {exc}") from exc
-            if max(p.up, p.down) > rs.MAX_FACTOR or rs.tile_span(p.up, p.down, p.K) > rs.LDS_SPAN_FLOATS:
-                raise ValueError(f"BatchFeeder: {name} is at {rate} Hz: {rate} -> {self.sample_rate} reduces to "
-                                 f"{p.up}/{p.down}, whose input span per tile ({rs.tile_span(p.up, p.down, p.K)} samples) "
-                                 "does not fit the kernel's LDS")
-            self._rs_ids[rate] = len(self._rs_plans)
-            self._rs_plans.append(p)
+            self._rs_ids[rate] = self._rs.add(p)
             need = max(need, rs.window_bound(self.crop_length, p.up, p.down, p.K))
-        self._rs_plan_host = self._rs_plan_dev = self._rs_tables = None
-        if self._rs_plans:
-            ints = torch.zeros(len(self._rs_plans), _PLAN, dtype=torch.int32)
-            tabs, off = [], 0
-            for i, p in enumerate(self._rs_plans):
-                ints[i, :6] = torch.tensor([p.up, p.down, len(p.taps), p.K, p.pitch, off], dtype=torch.int32)
-                tabs.append(p.host_table().reshape(-1))
-                off += p.up * p.pitch
-            self._rs_plan_host = ints
-            self._rs_plan_dev = ints.to(self.device)
-            self._rs_tables = torch.cat(tabs).to(self.device)
         return need
 
     def _factors(self, rate):
         """up, down, H, K of ``rate`` -> the model's rate (1, 1, 0, 1 for the model's rate itself: y[m] = x[m])."""
         k = self._rs_ids[rate]
-        if k < 0:
-            return 1, 1, 0, 1
-        p = self._rs_plans[k]
-        return p.up, p.down, p.H, p.K
+        up, down, H, K, _ = self._rs.plans[k] if k >= 0 else (1, 1, 0, 1, None)
+        return up, down, H, K
 
     def _records(self, entries, windows):
         """The (nb, 16) int32 record table of one batch (include/cleanumamba_hip.h: cum_pcm_batch_resample_f32)."""
-        recs = torch.zeros(len(entries), _REC, dtype=torch.int32)
-        pos = recs.view(torch.int64)                    # in0: ints 12-13, out0: ints 14-15
+        recs = torch.zeros(len(entries), rs.REC_INTS, dtype=torch.int32)
+        pos = recs.view(torch.int64)
         for r, ((index, start, count), (m0, M, rate)) in enumerate(zip(entries, windows)):
-            recs[r, :4] = torch.tensor([self._rs_ids[rate], count, M, int(self.dataset.pair_length(index))],
-                                       dtype=torch.int32)
-            pos[r, 6], pos[r, 7] = start, m0
+            recs[r, rs.FEED_PLAN], recs[r, rs.FEED_N_SRC], recs[r, rs.FEED_M] = self._rs_ids[rate], count, M
+            recs[r, rs.FEED_N] = int(self.dataset.pair_length(index))
+            pos[r, rs.REC_IN0 // 2], pos[r, rs.REC_OUT0 // 2] = start, m0
         return recs
 
     # ------------------------------------------------------------------ plan

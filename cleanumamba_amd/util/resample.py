@@ -15,10 +15,12 @@ samples only, which is what makes a clip's result independent of its batch and a
   out_length       ceil(L up / down) (pure)
   final_outputs    outputs that no later input can change (pure)
   stream_step      one push of a stream: outputs now final, history to keep (pure; StreamResampler and the stream pool's
-                   rated slots, network/streampool.py); history_bound, tile_span: what sizes the pool's rows, what the
-                   kernels' LDS admits
+                   rated slots, network/streampool.py); history_bound: what sizes the pool's rows
+  tile_span        what the kernels' LDS admits; check_fits(plan): ValueError for a pair beyond it
   crop_window      the source samples that outputs [m0, m0 + count) of a file read; window_bound: the longest such range
                    (pure; what a rated training/feeder.py stages for cum_pcm_batch_resample_f32)
+  PlanTable        the pairs of one user (the stream pool, the feeder) as the plan table and tap blob of the slots and
+                   feeder entries; PLAN_INTS, REC_INTS, SLOT_*, FEED_*, REC_IN0 / REC_OUT0: their rows' sizes and fields
   resample_ragged  a ragged batch in one launch
   StreamResampler  push / finish over signals of any length, bit-identical to ``resample_ragged`` on the whole signal
 
@@ -37,6 +39,12 @@ MAX_FACTOR = 1024
 RS_TILE = 768                # outputs of one workgroup (csrc/resample.hip: RS_TILE = cum_resample_tile())
 LDS_SPAN_FLOATS = 12288      # ... and the longest input span it stages (RS_LDS_SPAN_FLOATS)
 PCM_SCALE = 1.0 / 32768.0
+# int32 per plan row / record of the slots and feeder entries and their fields (layouts: include/cleanumamba_hip.h)
+PLAN_INTS, REC_INTS = 8, 16
+(SLOT_SLOT, SLOT_PLAN, SLOT_N_HIST, SLOT_X_ROW, SLOT_N_NEW, SLOT_N_OUT, SLOT_Y_ROW, SLOT_ENDS, SLOT_KEEP, SLOT_PARITY,
+ SLOT_Y_COL) = range(11)                                 # a slot record's ints
+FEED_PLAN, FEED_N_SRC, FEED_M, FEED_N = range(4)         # a feeder record's ints
+REC_IN0, REC_OUT0 = 12, 14                               # both records' int64 positions: ints 12-13 and 14-15
 _PLANS = {}
 
 
@@ -81,6 +89,14 @@ def tile_span(up, down, K):
     """Floats of LDS one workgroup's input span needs (csrc/resample.hip: rs_span_cap); the kernels take a pair only if
     this is at most ``LDS_SPAN_FLOATS``."""
     return (int(K) + ((int(up) - 1) + (RS_TILE - 1) * int(down)) // int(up) + 16 + 7) // 8 * 8
+
+
+def check_fits(p):
+    """ValueError for a Plan whose ``tile_span`` the kernels' LDS does not hold (every C entry refuses it as well)."""
+    span = tile_span(p.up, p.down, p.K)
+    if span > LDS_SPAN_FLOATS:
+        raise ValueError(f"{p.rate_in} -> {p.rate_out} reduces to {p.up}/{p.down}, whose input span per tile ({span} "
+                         "samples) does not fit the kernel's LDS")
 
 
 def crop_window(N, up, down, H, K, m0, count):
@@ -150,6 +166,42 @@ def plan(rate_in, rate_out):
     if key not in _PLANS:
         _PLANS[key] = Plan(*key)
     return _PLANS[key]
+
+
+class PlanTable:
+    """The rate pairs of one user as the slots and feeder entries take them (include/cleanumamba_hip.h): ``plans`` in the
+    order they were added, a plan's place its id;  ``host`` (n, PLAN_INTS) int32, row i = (up, down, taps, K, pitch,
+    offset, 0, 0) of plans[i];  on ``device``: ``dev``, its copy, and ``blob``, the plans' polyphase tables end to end."""
+
+    def __init__(self, device):
+        self.device, self.plans, self._ids = torch.device(device), [], {}
+        self.host = self.dev = self.blob = None
+
+    def add(self, p):
+        """The id of Plan ``p``; a pair the table does not hold yet extends it, and the device gets the longer table."""
+        key = (p.rate_in, p.rate_out)
+        if key not in self._ids:
+            self._ids[key] = len(self.plans)
+            self.plans.append(p)
+            self.to(self.device)
+        return self._ids[key]
+
+    def to(self, device):
+        """Build the table and the blob on ``device`` (nothing while the table is empty)."""
+        self.device = torch.device(device)
+        if not self.plans:
+            return
+        offsets = np.cumsum([0] + [p.up * p.pitch for p in self.plans])
+        self.host = torch.tensor([(p.up, p.down, len(p.taps), p.K, p.pitch, off) + (0,) * (PLAN_INTS - 6)
+                                  for p, off in zip(self.plans, offsets.tolist())], dtype=torch.int32)
+        self.dev = self.host.to(self.device)
+        self.blob = torch.cat([p.host_table().reshape(-1) for p in self.plans]).to(self.device)
+
+    def args(self):
+        """plans_host, plans, n_plans, tables, table_floats of the two entries (nulls and zeros for an empty table)."""
+        if not self.plans:
+            return None, None, 0, None, 0
+        return hip.ptr(self.host), hip.ptr(self.dev), len(self.plans), hip.ptr(self.blob), self.blob.numel()
 
 
 def _rows(x, what):

@@ -896,6 +896,9 @@ int cum_resample_ragged(int32_t src_i16, const void *x, int32_t batch, int64_t l
  *   record reads row `parity` and writes the next history to row 1 - parity, so the workgroups of a record (one per
  *   cum_resample_tile outputs) never read what one of them writes.  The signal a record sees is
  *   hist[slot][parity][0, n_hist) ++ x[x_row][0, n_new), its first sample at absolute position in0.
+ *   The two layouts below and the record of cum_pcm_batch_resample_f32 are described here alone; their fields are named
+ *   in csrc/resample.hip (RsPlanField, RsSlotField, RsFeedField) and in util/resample.py (PLAN_INTS, REC_INTS, SLOT_*,
+ *   FEED_*, REC_IN0 / REC_OUT0), whose PlanTable builds `plans_host`, `plans` and `tables`.
  *   Plan p = 8 int32 {up, down, n_taps, K, table_pitch, table_offset, 0, 0}: the pair's polyphase table (as for
  *     cum_resample_ragged) starts table_offset floats (a multiple of 4) into `tables` (table_floats long, 16-byte
  *     aligned).  up <= 3 takes the scalar-tap route, any other the per-lane row route, per record.

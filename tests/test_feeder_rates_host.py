@@ -117,8 +117,7 @@ def _plan_only_feeder(ds, rates, **kw):
     f.close()                        # the readers would stage model-rate windows: only plan() is used
     f._rates = list(rates)
     for r in sorted(set(rates) - {MODEL}):
-        f._rs_ids[r] = len(f._rs_plans)
-        f._rs_plans.append(rs.plan(r, MODEL))
+        f._rs_ids[r] = f._rs.add(rs.plan(r, MODEL))
     return f
 
 

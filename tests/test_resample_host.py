@@ -129,6 +129,86 @@ def test_new_symbols_and_their_argument_errors_need_no_gpu():
     assert lib.cum_resample_ragged(*[none[k] for k in order], None) == 0
 
 
+def test_tile_span_is_the_c_sides_span_limit():
+    """``tile_span`` / ``LDS_SPAN_FLOATS`` / ``RS_TILE`` mirror rs_span_cap / RS_LDS_SPAN_FLOATS / RS_TILE of
+    csrc/resample.hip: a launch of nothing (max_out = 0 returns after every check) is accepted exactly when Python says
+    the pair fits, so ``check_fits`` never passes a pair the entries then refuse."""
+    from cleanumamba_amd import hip
+    from cleanumamba_amd.util import resample as rs
+    lib = hip.lib()
+    assert rs.RS_TILE == lib.cum_resample_tile()
+    P = ctypes.c_void_p
+
+    def accepted(up, down, K):
+        rc = lib.cum_resample_ragged(1, P(0x1000), 1, 8, 8, P(0x2000), None, 1, up, down, 1, K, P(0x3000), -(-K // 4) * 4,
+                                     P(0x4000), 0, 0, None)
+        assert rc == 0 or (rc == -1 and b"LDS" in lib.cum_last_error()), (up, down, K, lib.cum_last_error())
+        return rc == 0
+
+    # just inside and just outside the limit of 12288 floats
+    for triple, span in (((1, 14, 1500), 12256), ((1, 16, 1), 12296), ((3, 48, 1), 12296), ((1, 16, 219), 12512)):
+        assert rs.tile_span(*triple) == span and accepted(*triple) == (span <= rs.LDS_SPAN_FLOATS), triple
+    fits = 0
+    for up in (1, 2, 3, 4, 80, 147, 160, 441, 1024):
+        for down in (1, 2, 3, 6, 12, 14, 15, 16, 17, 48, 147, 160, 441, 1024):
+            for K in (1, 7, 73, 219, 640, 1500, 3477):
+                want = rs.tile_span(up, down, K) <= rs.LDS_SPAN_FLOATS
+                assert accepted(up, down, K) == want, (up, down, K)
+                fits += want
+    assert 0 < fits < 882                                # the sweep has pairs on both sides
+
+
+def test_plan_table_layout_and_the_c_checker_accepts_it():
+    from cleanumamba_amd import hip
+    from cleanumamba_amd.util import resample as rs
+    lib = hip.lib()
+    t = rs.PlanTable("cpu")
+    assert t.args() == (None, None, 0, None, 0) and t.host is None and t.plans == []
+    plans = [rs.plan(48000, 16000), rs.plan(16000, 44100), rs.plan(44100, 16000)]
+    assert [t.add(p) for p in plans] == [0, 1, 2]
+    assert t.plans == plans and t.host.dtype == torch.int32 and tuple(t.host.shape) == (3, rs.PLAN_INTS)
+    off = 0
+    for row, p in zip(t.host.tolist(), plans):
+        assert row == [p.up, p.down, len(p.taps), p.K, p.pitch, off, 0, 0] and off % 4 == 0
+        off += p.up * p.pitch
+    assert torch.equal(t.dev, t.host) and t.blob.dtype == torch.float32
+    assert torch.equal(t.blob, torch.cat([p.host_table().reshape(-1) for p in plans])) and t.blob.numel() == off
+    before = t.host
+    assert t.add(rs.plan(16000, 44100)) == 1 and len(t.plans) == 3 and t.host is before     # known: nothing is rebuilt
+    host, dev, n, blob, floats = t.args()
+    assert (host.value, dev.value, n, blob.value, floats) == (t.host.data_ptr(), t.dev.data_ptr(), 3, t.blob.data_ptr(), off)
+    P = ctypes.c_void_p
+    # no record: cum_resample_slots checks every plan row and the blob, and launches nothing
+    rc = lib.cum_resample_slots(P(0x10000), 220, 4, host, dev, n, blob, floats, P(0x40000), P(0x50000), 0, None, 0, 0,
+                                P(0x60000), 1, 8, None)
+    assert rc == 0, lib.cum_last_error()
+    rc = lib.cum_resample_slots(P(0x10000), 220, 4, host, dev, n, blob, floats - 1, P(0x40000), P(0x50000), 0, None, 0, 0,
+                                P(0x60000), 1, 8, None)
+    assert rc == -1 and b"blob" in lib.cum_last_error()
+
+
+def test_the_pool_and_the_feeder_each_hold_one_plan_table(tmp_path):
+    from cleanumamba_amd.util import resample as rs
+    from cleanumamba_amd.training.feeder import BatchFeeder
+    from test_feeder_rates_host import MIXED, MODEL, _dataset, _plan_only_feeder, mixed_tree
+    from test_pool_rates_host import _net
+    pool = _net("pruned500k").stream_pool(2)
+    pool.open(1, rate=48000)
+    assert isinstance(pool._rs, rs.PlanTable) and pool._rs.plans == [rs.plan(48000, 16000), rs.plan(16000, 48000)]
+    mixed_tree(str(tmp_path), MIXED)
+    rates = [r for r, _ in MIXED]
+    assert isinstance(_plan_only_feeder(_dataset(str(tmp_path)), rates)._rs, rs.PlanTable)
+    # the feeder's own registration, from the files' headers (its table on the host: nothing here touches a GPU)
+    f = BatchFeeder.__new__(BatchFeeder)
+    f.dataset, f.sample_rate, f.crop_length, f.device = _dataset(str(tmp_path)), MODEL, 4000, torch.device("cpu")
+    f._read_rates(True)
+    seen = list(dict.fromkeys(r for r in rates if r != MODEL))              # in the order the pairs bring them
+    assert f._rs.plans == [rs.plan(r, MODEL) for r in seen] and tuple(f._rs.host.shape) == (len(seen), rs.PLAN_INTS)
+    assert f._rs_ids == {MODEL: -1, **{r: i for i, r in enumerate(seen)}}
+    # the records' 64-bit positions stand where both packers and the C side read them: ints 12-13 and 14-15
+    assert (rs.REC_IN0, rs.REC_OUT0, rs.REC_INTS) == (12, 14, 16) and rs.REC_IN0 % 2 == rs.REC_OUT0 % 2 == 0
+
+
 def test_host_tensors_are_refused():
     from cleanumamba_amd.util.resample import StreamResampler, resample_ragged
     with pytest.raises(RuntimeError, match="GPU"):
