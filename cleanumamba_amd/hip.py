@@ -212,6 +212,9 @@ SIGNATURES = {
                                    c_i64, _P]),
     "cum_pcm_batch_resample_f32": (c_i32, [_P, c_i64, _P, _P, c_i32, _P, _P, c_i32, _P, c_i64, c_i64, _P, c_i64, _P, c_i64,
                                            _P]),
+    "cum_augment_workspace_elems": (c_i64, [c_i32, c_i64]),
+    "cum_augment_pairs": (c_i32, [_P, c_i64, _P, c_i64, c_i32, c_i64, c_i64, _P, _P, _P, c_i32, _P, _P, c_i64, _P, c_i64,
+                                  _P]),
 }
 
 _lib = None

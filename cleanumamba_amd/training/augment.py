@@ -1,0 +1,314 @@
+"""Training augmentation on the (noise, clean) pair: the hook of the reference's train loop (src/training/train.py:262-265)
+
+    # noise = noisy_audio - clean_audio
+    # noise, clean_audio = augment((noise, clean_audio))
+    # noisy_audio = noise + clean_audio
+
+with the augmentation family of the denoiser lineage CleanUNet comes from: exchange the noises within the batch (remix),
+shift noise against speech, re-draw the SNR and the level, add a synthetic room (echo).  DESIGN.md 7h.
+
+Two halves, kept apart:
+
+  Augment.draw(rng, nb, length)   pure host code: everything random about one batch, as an ``AugmentDraws`` of int32 /
+                                  float32 numpy arrays -- the values the kernel reads, already rounded;
+  apply(clean_src, noisy_src, draws)
+                                  the arithmetic, with nothing random in it: csrc/augment.hip (cum_augment_pairs) on
+                                  device tensors, a torch restatement on CPU tensors.
+
+The sources are the clean and noisy crops ``shift`` samples LONGER than the batch, (B, L + S); row b of the result is
+
+    c0[t] = C[b, t + off_clean[b]]                       n0[t] = Y[p, t + off_noise[b]] - C[p, t + off_noise[b]],  p = perm[b]
+    rc[t] = sum_k tap_gain[b, k] c0[t - delay[b, k]]     rn[t] = sum_k tap_gain[b, k] n0[t - delay[b, k]]
+    c1 = c0 + kappa rc                                   n1 = n0 + rn + (1 - kappa) rc
+    a  = sqrt(Ec / (En 10^(snr_db / 10))),  Ec = sum c1^2, En = sum n1^2 in f64  (1 if snr_db is NaN or a sum is 0)
+    clean' = gain c1                                     noisy' = gain (c1 + a n1)
+
+(k ascending, terms with t < delay dropped).  ``BatchFeeder(..., augment=Augment(...))`` (training/feeder.py) draws per
+batch from its own generator and runs this between the assembling kernel and the train step's inputs.
+
+Left out on purpose: BandMask, whose mel-edge low-pass filters are some 3 200 taps long and want an FFT convolution.
+"""
+import ctypes
+import math
+
+import numpy as np
+import torch
+
+from .. import hip
+
+K_MAX = 512                      # taps per row the kernel takes (csrc/augment.hip)
+REC_INTS = 8                     # one record per row: the fields below, then zeros
+REC_PERM, REC_OFF_CLEAN, REC_OFF_NOISE, REC_N_TAPS, REC_SNR_DB, REC_GAIN, REC_KAPPA = range(7)
+
+
+def _range(value, name):
+    if value is None:
+        return None
+    lo, hi = (float(v) for v in value)
+    if not (math.isfinite(lo) and math.isfinite(hi) and lo <= hi):
+        raise ValueError(f"{name} must be None or a finite (lo, hi) with lo <= hi; got {value!r}")
+    return lo, hi
+
+
+class Echo:
+    """A synthetic room: ``repeat`` trains of decaying reflections of the clip added to itself.  With probability
+    ``proba`` per row:  init = U(0, 1) initial, fd = U(first_delay) s, rt = U(rt60) s;  then ``repeat`` times, from
+    frac = 1, g = init, d = 0, while frac > 1e-3:
+
+        d += 1 + int((1 + jitter U(-1, 1)) fd sample_rate);  tap (d, g) if d < length;
+        a = 10^(-3 (1 + jitter U(-1, 1)) fd / rt);  g *= a;  frac *= a
+
+    ``keep_clean`` (kappa) is the share of the speech's reverberation that stays in the target; the rest goes to the
+    noise.  The constructor counts the taps of the worst case -- the smallest first delay, the largest rt60, the jitter
+    at its most negative -- and raises ValueError when they exceed K_MAX."""
+
+    def __init__(self, proba=1.0, initial=0.3, first_delay=(0.01, 0.03), rt60=(0.3, 1.3), repeat=3, jitter=0.1,
+                 keep_clean=0.1, sample_rate=16000):
+        self.proba, self.initial, self.jitter = float(proba), float(initial), float(jitter)
+        self.first_delay, self.rt60 = _range(first_delay, "first_delay"), _range(rt60, "rt60")
+        self.repeat, self.keep_clean, self.sample_rate = int(repeat), float(keep_clean), int(sample_rate)
+        if self.first_delay is None or self.rt60 is None or self.first_delay[0] <= 0 or self.rt60[0] <= 0:
+            raise ValueError("Echo: first_delay and rt60 must be positive (lo, hi) ranges in seconds")
+        if not (0 <= self.proba <= 1 and 0 <= self.jitter < 1 and self.repeat >= 1 and self.sample_rate >= 1):
+            raise ValueError("Echo: proba in [0, 1], jitter in [0, 1), repeat >= 1 and sample_rate >= 1 are required")
+        a = 10.0 ** (-3.0 * (1.0 - self.jitter) * self.first_delay[0] / self.rt60[1])
+        frac, per_repeat = 1.0, 0
+        while frac > 1e-3 and per_repeat <= K_MAX:
+            per_repeat, frac = per_repeat + 1, frac * a
+        self.max_taps = self.repeat * per_repeat
+        if self.max_taps > K_MAX:
+            raise ValueError(f"Echo: the worst case (first_delay {self.first_delay[0]:g} s, rt60 {self.rt60[1]:g} s, "
+                             f"jitter -{self.jitter:g}) gives {self.repeat} x {per_repeat}{'+' if per_repeat > K_MAX else ''}"
+                             f" taps, more than the kernel's {K_MAX}")
+
+    def draw(self, rng, length):
+        """[(delay, gain)] of one row (empty with probability 1 - proba)."""
+        taps = []
+        if not rng.random() < self.proba:
+            return taps
+        init = rng.random() * self.initial
+        fd = rng.uniform(*self.first_delay)
+        rt = rng.uniform(*self.rt60)
+        for _ in range(self.repeat):
+            frac, g, d = 1.0, init, 0
+            while frac > 1e-3:
+                d += 1 + int((1 + self.jitter * rng.uniform(-1, 1)) * fd * self.sample_rate)
+                if d < length:
+                    taps.append((d, g))
+                a = 10.0 ** (-3 * (1 + self.jitter * rng.uniform(-1, 1)) * fd / rt)
+                g *= a
+                frac *= a
+        return taps
+
+
+class AugmentDraws:
+    """Everything random about one batch of ``nb`` rows of ``length`` samples, as the kernel reads it: int32 ``perm``,
+    ``off_clean``, ``off_noise``, ``n_taps`` (nb,) and ``delay`` (nb, K_MAX); float32 ``snr_db`` (NaN: keep), ``gain``,
+    ``kappa`` (nb,) and ``tap_gain`` (nb, K_MAX).  ``shift``: the sources are ``length + shift`` long."""
+
+    def __init__(self, length, shift, perm, off_clean, off_noise, snr_db, gain, kappa, n_taps, delay, tap_gain):
+        self.length, self.shift = int(length), int(shift)
+        self.perm, self.off_clean, self.off_noise, self.n_taps = (np.ascontiguousarray(v, dtype=np.int32)
+                                                                  for v in (perm, off_clean, off_noise, n_taps))
+        self.snr_db, self.gain, self.kappa = (np.ascontiguousarray(v, dtype=np.float32) for v in (snr_db, gain, kappa))
+        self.delay = np.ascontiguousarray(delay, dtype=np.int32)
+        self.tap_gain = np.ascontiguousarray(tap_gain, dtype=np.float32)
+        nb = self.perm.shape[0]
+        if self.length < 1 or self.shift < 0 or nb < 1:
+            raise ValueError("AugmentDraws: length >= 1, shift >= 0 and at least one row are required")
+        for name in ("off_clean", "off_noise", "n_taps", "snr_db", "gain", "kappa"):
+            if getattr(self, name).shape != (nb,):
+                raise ValueError(f"AugmentDraws: {name} must have shape ({nb},)")
+        if self.delay.shape != self.tap_gain.shape or self.delay.ndim != 2 or self.delay.shape[0] != nb \
+                or self.delay.shape[1] > K_MAX:
+            raise ValueError(f"AugmentDraws: delay and tap_gain must both be ({nb}, K <= {K_MAX})")
+        if sorted(self.perm.tolist()) != list(range(nb)):
+            raise ValueError("AugmentDraws: perm must be a permutation of the rows")
+        if min(self.off_clean.min(), self.off_noise.min()) < 0 or max(self.off_clean.max(), self.off_noise.max()) > shift:
+            raise ValueError("AugmentDraws: offsets must lie in [0, shift]")
+        if self.n_taps.min() < 0 or self.n_taps.max() > self.delay.shape[1]:
+            raise ValueError("AugmentDraws: n_taps must lie in [0, K]")
+
+    @property
+    def batch(self):
+        return self.perm.shape[0]
+
+    @property
+    def rescales(self):
+        """Whether any row re-draws its SNR (the kernel then needs its second launch and a workspace)."""
+        return bool(np.isfinite(self.snr_db).any())
+
+    def columns(self):
+        """Tap columns a packed table of these draws needs: the longest list, rounded up to 4."""
+        return (int(self.n_taps.max()) + 3) // 4 * 4
+
+    def pack(self, k=None):
+        """The draws as one int32 array: nb records of 8, then delay[:, :k], then tap_gain[:, :k] (its bits)."""
+        k = self.columns() if k is None else int(k)
+        nb = self.batch
+        if not self.n_taps.max() <= k <= K_MAX:
+            raise ValueError(f"AugmentDraws.pack: k = {k} does not hold {int(self.n_taps.max())} taps (or exceeds {K_MAX})")
+        out = np.zeros(table_ints(nb, k), dtype=np.int32)
+        recs = out[:nb * REC_INTS].reshape(nb, REC_INTS)
+        recs[:, REC_PERM], recs[:, REC_OFF_CLEAN], recs[:, REC_OFF_NOISE] = self.perm, self.off_clean, self.off_noise
+        recs[:, REC_N_TAPS] = self.n_taps
+        recs[:, REC_SNR_DB], recs[:, REC_GAIN] = self.snr_db.view(np.int32), self.gain.view(np.int32)
+        recs[:, REC_KAPPA] = self.kappa.view(np.int32)
+        have = min(k, self.delay.shape[1])
+        taps = out[nb * REC_INTS:].reshape(2, nb, k)
+        taps[0, :, :have], taps[1, :, :have] = self.delay[:, :have], self.tap_gain[:, :have].view(np.int32)
+        return out
+
+
+def table_ints(nb, k):
+    """int32 entries of a packed table of nb rows with k tap columns."""
+    return nb * (REC_INTS + 2 * k)
+
+
+class Augment:
+    """``Augment(remix=False, shift=0, snr_db=None, gain_db=None, echo=None)``
+
+    remix: every row gets the noise of a row drawn by one uniform permutation of the batch.
+    shift: speech and noise each start at their own uniform offset in [0, shift] of crops ``shift`` samples longer.
+    snr_db: (lo, hi) -- the noise is rescaled so that the row's SNR is uniform in the range -- or None (keep).
+    gain_db: (lo, hi) -- both signals are scaled by 10^(g / 20), g uniform in the range -- or None.
+    echo: ``Echo(...)`` or None.
+    A config with every transform off is ``inactive`` and is treated by its users exactly as no augmentation."""
+
+    def __init__(self, remix=False, shift=0, snr_db=None, gain_db=None, echo=None):
+        self.remix, self.shift = bool(remix), int(shift)
+        self.snr_db, self.gain_db = _range(snr_db, "snr_db"), _range(gain_db, "gain_db")
+        if self.shift < 0:
+            raise ValueError("Augment: shift must be at least 0")
+        if echo is not None and not isinstance(echo, Echo):
+            raise ValueError("Augment: echo must be an Echo or None")
+        self.echo = echo
+
+    @property
+    def active(self):
+        return self.remix or self.shift > 0 or self.snr_db is not None or self.gain_db is not None \
+            or self.echo is not None
+
+    @property
+    def max_taps(self):
+        """Tap columns a batch of this config can need, rounded up to 4 (0 without echo)."""
+        return 0 if self.echo is None else min(K_MAX, (self.echo.max_taps + 3) // 4 * 4)
+
+    def draw(self, rng, nb, length):
+        """The draws of one batch from ``rng`` (a numpy Generator), in this order: the permutation; nb clean offsets;
+        nb noise offsets; nb SNRs; nb gains; then row by row the echo (Echo.draw).  A transform that is off draws
+        nothing."""
+        nb, length = int(nb), int(length)
+        perm = rng.permutation(nb) if self.remix else np.arange(nb)
+        if self.shift > 0:
+            off_clean = rng.integers(0, self.shift + 1, nb)
+            off_noise = rng.integers(0, self.shift + 1, nb)
+        else:
+            off_clean = off_noise = np.zeros(nb, np.int64)
+        snr = rng.uniform(*self.snr_db, nb) if self.snr_db is not None else np.full(nb, np.nan)
+        gain = 10.0 ** (rng.uniform(*self.gain_db, nb) / 20.0) if self.gain_db is not None else np.ones(nb)
+        n_taps = np.zeros(nb, np.int32)
+        delay, tap_gain = np.zeros((nb, K_MAX), np.int32), np.zeros((nb, K_MAX), np.float32)
+        kappa = np.full(nb, self.echo.keep_clean if self.echo is not None else 0.0)
+        if self.echo is not None:
+            for b in range(nb):
+                taps = self.echo.draw(rng, length)
+                n_taps[b] = len(taps)          # (at most echo.max_taps <= K_MAX: the constructor's worst case)
+                if taps:
+                    delay[b, :len(taps)], tap_gain[b, :len(taps)] = zip(*taps)
+        return AugmentDraws(length, self.shift, perm, off_clean, off_noise, snr, gain, kappa, n_taps, delay, tap_gain)
+
+
+# ---------------------------------------------------------------------------------------------------------------- apply
+def _rows(t, name, nb, n):
+    """(row stride in elements, whether t is (B, 1, n)) of a float32 (B, n) or (B, 1, n) tensor with unit time stride."""
+    if t.dtype != torch.float32 or tuple(t.shape) not in ((nb, n), (nb, 1, n)):
+        raise ValueError(f"augment.apply: {name} must be a float32 ({nb}, {n}) or ({nb}, 1, {n}) tensor; got {t.dtype} "
+                         f"{tuple(t.shape)}")
+    if n > 1 and t.stride(-1) != 1:
+        raise ValueError(f"augment.apply: {name} must have unit stride along time")
+    return (t.stride(0) if nb > 1 else n), t.dim() == 3
+
+
+def _span(t, sb, nb, n):
+    lo = t.data_ptr()
+    return lo, lo + 4 * ((nb - 1) * sb + n)
+
+
+def _host(clean_src, cs, noisy_src, ys, draws, clean_out, co, noisy_out, no):
+    """The arithmetic of the module's docstring with torch on the host, row by row, tap by tap in ascending k."""
+    nb, L, n = draws.batch, draws.length, draws.length + draws.shift
+    C = torch.as_strided(clean_src, (nb, n), (cs, 1))
+    Y = torch.as_strided(noisy_src, (nb, n), (ys, 1))
+    out_c = torch.as_strided(clean_out, (nb, L), (co, 1))
+    out_n = torch.as_strided(noisy_out, (nb, L), (no, 1))
+    for b in range(nb):
+        p, oc, on = int(draws.perm[b]), int(draws.off_clean[b]), int(draws.off_noise[b])
+        c0 = C[b, oc:oc + L].clone()
+        n0 = Y[p, on:on + L] - C[p, on:on + L]
+        rc, rn = torch.zeros(L), torch.zeros(L)
+        for k in range(int(draws.n_taps[b])):
+            d, g = int(draws.delay[b, k]), float(draws.tap_gain[b, k])
+            if 1 <= d < L:
+                rc[d:].add_(c0[:L - d], alpha=g)
+                rn[d:].add_(n0[:L - d], alpha=g)
+        kappa = torch.tensor(draws.kappa[b])
+        c1 = c0 + kappa * rc
+        n1 = (n0 + rn) + (1 - kappa) * rc
+        a = 1.0
+        ec, en = float(c1.double().square().sum()), float(n1.double().square().sum())
+        snr = float(draws.snr_db[b])
+        if math.isfinite(snr) and ec > 0 and en > 0:
+            a = math.sqrt(ec / (en * 10.0 ** (snr / 10.0)))
+        gain = torch.tensor(draws.gain[b])
+        out_c[b] = gain * c1
+        out_n[b] = gain * (c1 + torch.tensor(a, dtype=torch.float32) * n1)
+
+
+def launch(clean_src, cs, noisy_src, ys, nb, length, src_len, table, k, workspace, clean, co, noisy, no):
+    """cum_augment_pairs on the current stream.  table: the device int32 tensor of ``AugmentDraws.pack(k)``; workspace:
+    a device tensor of cum_augment_workspace_elems floats, or None when no row re-draws its SNR."""
+    recs = table.data_ptr()
+    delay = recs + 4 * nb * REC_INTS
+    hip.check(hip.lib().cum_augment_pairs(
+        hip.ptr(clean_src), cs, hip.ptr(noisy_src), ys, nb, length, src_len, ctypes.c_void_p(recs),
+        ctypes.c_void_p(delay if k else None), ctypes.c_void_p(delay + 4 * nb * k if k else None), k, hip.ptr(workspace),
+        hip.ptr(clean), co, hip.ptr(noisy), no, hip.stream_ptr()))
+
+
+def workspace_for(nb, length, device):
+    """The f64 tile sums' room for a batch of nb rows of length samples (8-byte aligned: a float64 tensor)."""
+    return torch.empty(max(1, hip.lib().cum_augment_workspace_elems(nb, length) // 2), dtype=torch.float64, device=device)
+
+
+def apply(clean_src, noisy_src, draws, clean_out=None, noisy_out=None):
+    """(clean', noisy') of the module's docstring.  clean_src, noisy_src: float32 (B, L + S) or (B, 1, L + S) tensors on
+    one device, unit stride along time, L = draws.length, S = draws.shift; clean_out, noisy_out: (B, L) or (B, 1, L), made
+    here (in the sources' form) if not given; on a GPU they start on a 16-byte boundary and must not overlap the sources.
+    Device tensors go through cum_augment_pairs on the current stream, CPU tensors through torch on the host."""
+    nb, L, n = draws.batch, draws.length, draws.length + draws.shift
+    dev = clean_src.device
+    cs, three = _rows(clean_src, "clean_src", nb, n)
+    ys, _ = _rows(noisy_src, "noisy_src", nb, n)
+    if clean_out is None:
+        clean_out = torch.empty((nb, 1, L) if three else (nb, L), dtype=torch.float32, device=dev)
+    if noisy_out is None:
+        noisy_out = torch.empty((nb, 1, L) if three else (nb, L), dtype=torch.float32, device=dev)
+    co, _ = _rows(clean_out, "clean_out", nb, L)
+    no, _ = _rows(noisy_out, "noisy_out", nb, L)
+    if not (noisy_src.device == clean_out.device == noisy_out.device == dev):
+        raise ValueError("augment.apply: all tensors must be on one device")
+    spans = [_span(clean_src, cs, nb, n), _span(noisy_src, ys, nb, n)]
+    outs = [_span(clean_out, co, nb, L), _span(noisy_out, no, nb, L)]
+    if any(o[0] < s[1] and s[0] < o[1] for o in outs for s in spans) or (outs[0][0] < outs[1][1] and outs[1][0] < outs[0][1]):
+        raise ValueError("augment.apply: the outputs must not overlap the sources or each other")
+    if dev.type == "cpu":
+        _host(clean_src, cs, noisy_src, ys, draws, clean_out, co, noisy_out, no)
+        return clean_out, noisy_out
+    hip.require_gpu(clean_src, noisy_src, clean_out, noisy_out)
+    k = draws.columns()
+    with torch.cuda.device(dev):
+        table = torch.from_numpy(draws.pack(k)).to(dev)
+        workspace = workspace_for(nb, L, dev) if draws.rescales else None
+        launch(clean_src, cs, noisy_src, ys, nb, L, n, table, k, workspace, clean_out, co, noisy_out, no)
+    return clean_out, noisy_out

@@ -32,6 +32,12 @@ buffers, bit-identical to ``resample_ragged`` on the whole file, sliced.  Pairs 
 cum_pcm_batch_f32's arithmetic, so an all-16 kHz dataset gives the unrated feeder's plan and batches.  Without
 ``sample_rate`` no header rate is read and nothing here changes.
 
+``BatchFeeder(..., augment=Augment(...))`` (training/augment.py) augments every batch on that last step:
+the plan crops ``shift`` samples more, the batch's draws -- from a generator of their own per (seed, epoch, rank, batch)
+-- ride in the slot's tail in the same upload, the assembling kernel writes the longer crops into float scratch the
+feeder owns, and cum_augment_pairs (csrc/augment.hip) writes the batch into the step's inputs.  Without ``augment``
+nothing here changes.
+
 ``device="cpu"`` keeps the same pipeline without pinning or streams and does the kernel's arithmetic with torch on the
 host, so the loop runs anywhere -- a rated feeder too, as long as every pair is at the model rate: there is no CPU
 resampler (util/resample.py), so any other rate is a ValueError at construction.
@@ -46,6 +52,7 @@ import torch
 
 from .. import hip
 from ..util import resample as rs
+from . import augment as aug
 
 SAMPLE_RATE = 16000
 PCM_SCALE = 1.0 / 32768.0
@@ -57,12 +64,14 @@ def _round_up(n, m):
 
 class _Slot:
     """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths -- in a rated feeder by
-    ``batch`` records of 16 int32 -- as one int16 tensor so that it moves in one copy."""
+    ``batch`` records of 16 int32 -- and, in an augmenting feeder, by ``aug_ints`` int32 of draw table, as one int16 tensor
+    so that it moves in one copy."""
 
-    def __init__(self, batch, pitch, device, pin, tail_ints=1):
+    def __init__(self, batch, pitch, device, pin, tail_ints=1, aug_ints=0):
         self.batch, self.pitch = batch, pitch
-        self.flat = torch.zeros(2 * batch * pitch + 2 * tail_ints * batch, dtype=torch.int16, device=device,
-                                pin_memory=pin)
+        self._aug = 2 * batch * pitch + 2 * tail_ints * batch       # an augmenting feeder's draw table starts here
+        self.flat = torch.zeros(self._aug + 2 * aug_ints, dtype=torch.int16, device=device, pin_memory=pin)
+        self.scratch = self.workspace = None     # device blocks of an augmenting feeder: the L + S float crops, tile sums
         self.seq = -1                # the batch this block holds
         self.uploaded = None         # event after the upload (device blocks on a GPU)
         self.released = []           # events after the assembling kernels that read this block
@@ -72,19 +81,24 @@ class _Slot:
         return self.flat[:2 * nb * self.pitch].view(2, nb, self.pitch)
 
     def src_len(self):
-        return self.flat[2 * self.batch * self.pitch:].view(torch.int32)
+        return self.flat[2 * self.batch * self.pitch:self._aug].view(torch.int32)
+
+    def aug_table(self, ints):
+        """The first ``ints`` int32 of the draw table (training/augment.py: AugmentDraws.pack)."""
+        return self.flat[self._aug:self._aug + 2 * ints].view(torch.int32)
 
     def records(self):
         """(batch, 16) int32 view of a rated slot's tail (8-byte aligned: a row is 16 bytes times a whole number)."""
-        return self.flat[2 * self.batch * self.pitch:].view(torch.int32).view(self.batch, rs.REC_INTS)
+        return self.flat[2 * self.batch * self.pitch:self._aug].view(torch.int32).view(self.batch, rs.REC_INTS)
 
 
 class _Pending:
     """A batch on its way through the staging slots."""
 
-    def __init__(self, seq, epoch, entries, windows=None, records=None):
+    def __init__(self, seq, epoch, entries, windows=None, records=None, draws=None, table=None):
         self.seq, self.epoch, self.entries = seq, epoch, entries
         self.windows, self.records = windows, records        # a rated feeder's: [(m0, M, rate)], (nb, 16) int32 on the host
+        self.draws, self.table = draws, table                # an augmenting feeder's: AugmentDraws, its packed int32 table
         self.todo = len(entries)     # rows not read yet
         self.error = None
 
@@ -95,12 +109,13 @@ class PcmBatch:
     fileids: [(clean path, noisy path)] per clip;  entries: the plan's (index, start, count) per clip -- the samples read
     from the files;  epoch;  shape: the (B, 1, L) of the float tensors it assembles;  windows (a rated feeder's, else
     None): [(m0, M, rate)] per clip -- the clip is outputs [m0, m0 + L) of its file's M model-rate samples, or, with
-    M <= L, all of them repeated."""
+    M <= L, all of them repeated;  draws (an augmenting feeder's, else None): the batch's ``AugmentDraws`` -- the plan's
+    crops are then ``draws.shift`` samples longer than L, and ``into`` applies the draws to them."""
 
-    def __init__(self, feeder, seq, epoch, entries, slot, windows=None, records=None):
+    def __init__(self, feeder, seq, epoch, entries, slot, windows=None, records=None, draws=None):
         self._feeder, self._seq, self._slot = feeder, seq, slot
         self.epoch, self.entries = epoch, entries
-        self.windows, self._records = windows, records
+        self.windows, self._records, self.draws = windows, records, draws
         files = getattr(feeder.dataset, "files", None)
         self.fileids = [tuple(files[i]) if files is not None else i for i, _, _ in entries]
         self.device = feeder.device
@@ -127,17 +142,28 @@ class PcmBatch:
             if t.stride(-1) != 1 and length > 1:
                 raise ValueError(f"PcmBatch.into: {name} must have unit stride along time")
             strides.append(t.stride(0) if nb > 1 else length)
+        out_clean, out_noisy, out_strides = clean, noisy, strides
+        if self.draws is not None:           # assemble the crops of length + shift samples, then augment into the outputs
+            length += self.draws.shift
         if self.device.type == "cpu":
+            if self.draws is not None:
+                clean, noisy = torch.empty(nb, length), torch.empty(nb, length)
+                strides = [length, length]
             n = slot.src_len()[:nb] if self._records is None else slot.records()[:nb, rs.FEED_N_SRC]     # (model rate)
             rows, n = slot.rows(nb), n.to(torch.int64).clamp(1, length)
             idx = torch.arange(length)[None, :] % n[:, None]
             for t, sb, src in ((clean, strides[0], rows[0]), (noisy, strides[1], rows[1])):
                 out = torch.as_strided(t, (nb, length), (sb, 1))
                 out.copy_(torch.gather(src, 1, idx).to(torch.float32) * PCM_SCALE)
-            return clean, noisy
+            if self.draws is not None:
+                aug.apply(clean, noisy, self.draws, out_clean, out_noisy)
+            return out_clean, out_noisy
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream()
             stream.wait_event(slot.uploaded)
+            if self.draws is not None:       # the block's own float scratch: the release events below cover it too
+                clean, noisy = slot.scratch
+                strides = [clean.stride(0), noisy.stride(0)]
             if self._records is None:
                 hip.check(hip.lib().cum_pcm_batch_f32(hip.ptr(slot.flat), slot.pitch, hip.ptr(slot.src_len()), nb, length,
                                                       hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
@@ -147,10 +173,15 @@ class PcmBatch:
                     hip.ptr(slot.flat), slot.pitch, hip.ptr(self._records), hip.ptr(slot.records()), nb,
                     *self._feeder._rs.args(), length, hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
                     ctypes.c_void_p(stream.cuda_stream)))
+            if self.draws is not None:
+                k = self._feeder._aug_k
+                aug.launch(clean, strides[0], noisy, strides[1], nb, self.shape[2], length,
+                           slot.aug_table(aug.table_ints(nb, k)), k, slot.workspace, out_clean, out_strides[0], out_noisy,
+                           out_strides[1])
             done = torch.cuda.Event()
             done.record(stream)
             slot.released.append(done)       # the next upload into this block waits for it (on the device)
-        return clean, noisy
+        return out_clean, out_noisy
 
     def tensors(self):
         """(clean, noisy): two fresh (B, 1, L) float32 tensors, assembled by ``into``."""
@@ -177,10 +208,16 @@ class BatchFeeder:
       interpreter lock; a handful saturates the page cache, and the count is deliberately not taken from the machine's
       CPU count.
     rank / world: this process takes ``perm[rank::world]`` of every epoch's permutation, truncated to the common count.
-    timeout_s: the longest ``next()`` waits for the readers or an upload before it raises TimeoutError."""
+    timeout_s: the longest ``next()`` waits for the readers or an upload before it raises TimeoutError.
+    augment: None, or a ``training.augment.Augment``: every batch is augmented on its way into the step's inputs
+      (csrc/augment.hip).  The draws of batch k of epoch e come from
+      ``numpy.random.Generator(PCG64([seed, e, rank, k, 0x417567]))`` -- never from the plan's generator -- and are the
+      batch's ``draws``; they travel in the slot's tail, in the same one upload.  With ``shift = S > 0`` the plan draws
+      crops of ``crop_length + S`` (model-rate) samples; otherwise the plan is the one without augmentation.  A config
+      with every transform off is taken as None."""
 
     def __init__(self, dataset, batch_size, device, crop_length=None, shuffle=True, seed=0, drop_last=True, depth=2,
-                 workers=4, rank=0, world=1, timeout_s=60, sample_rate=None):
+                 workers=4, rank=0, world=1, timeout_s=60, sample_rate=None, augment=None):
         self.dataset = dataset
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
@@ -189,6 +226,9 @@ class BatchFeeder:
         if crop_length is None:
             crop_length = int(getattr(dataset, "crop_length_sec", 0) * SAMPLE_RATE)
         self.crop_length = int(crop_length)
+        if augment is not None and not isinstance(augment, aug.Augment):
+            raise ValueError("BatchFeeder: augment must be a training.augment.Augment or None")
+        self.augment = augment if augment is not None and augment.active else None
         self.shuffle, self.seed, self.drop_last = bool(shuffle), int(seed), bool(drop_last)
         self.depth, self.workers = int(depth), int(workers)
         self.rank, self.world = int(rank), int(world)
@@ -207,15 +247,23 @@ class BatchFeeder:
         if gpu:
             hip.lib()                                   # a missing library is an error now, not at the first batch
         self.sample_rate = None if sample_rate is None else rs._rate(sample_rate, "sample_rate")
-        need = self.crop_length
+        need = self._plan_length
         if self.sample_rate is not None:
             need = self._read_rates(gpu)
         self.pitch = _round_up(need, 8)
         tail = 1 if self.sample_rate is None else rs.REC_INTS
-        self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu, tail) for _ in range(self.depth)]
+        self._aug_k = self.augment.max_taps if self.augment is not None else 0       # tap columns of the draw table
+        table = aug.table_ints(self.batch_size, self._aug_k) if self.augment is not None else 0
+        self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu, tail, table) for _ in range(self.depth)]
         self._stage_np = [s.flat.numpy() for s in self._stage]
         # one device block more than staging slots: batch k + 1 is uploaded while k and the depth - 1 before it are live
-        self._dev = [_Slot(self.batch_size, self.pitch, self.device, False, tail) for _ in range(self.depth + 1)]
+        self._dev = [_Slot(self.batch_size, self.pitch, self.device, False, tail, table) for _ in range(self.depth + 1)]
+        if gpu and self.augment is not None:
+            for block in self._dev:        # rows on the 16-byte grid, as the assembling kernels' wide stores want them
+                block.scratch = tuple(torch.empty(self.batch_size, _round_up(self._plan_length, 4), dtype=torch.float32,
+                                                  device=self.device)[:, :self._plan_length] for _ in range(2))
+                if self.augment.snr_db is not None:
+                    block.workspace = aug.workspace_for(self.batch_size, self.crop_length, self.device)
         self._stream = torch.cuda.Stream(self.device) if gpu else None
 
         self._cv = threading.Condition()
@@ -236,6 +284,12 @@ class BatchFeeder:
         for t in self._threads:
             t.start()
 
+    @property
+    def _plan_length(self):
+        """What the plan crops and the assembling kernel writes: the batch's length plus the room the shift moves in."""
+        augment = getattr(self, "augment", None)
+        return self.crop_length + (augment.shift if augment is not None else 0)
+
     # ------------------------------------------------------------------ rates
     def _read_rates(self, gpu):
         """Every pair's rate and the plan table (``_rs``; ``_rs_ids``: rate -> plan id, -1 the model's) of those that
@@ -243,7 +297,7 @@ class BatchFeeder:
         files = getattr(self.dataset, "files", None)
         self._rates = [int(self.dataset.pair_rate(i)) for i in range(len(self.dataset))]
         self._rs, self._rs_ids = rs.PlanTable(self.device), {self.sample_rate: -1}
-        need = self.crop_length                         # a pair at the model rate: the crop itself
+        need = self._plan_length                        # a pair at the model rate: the crop itself
         for i, rate in enumerate(self._rates):
             if rate in self._rs_ids:
                 continue
@@ -257,7 +311,7 @@ class BatchFeeder:
             except ValueError as exc:
                 raise ValueError(f"BatchFeeder: {name} is at {rate} Hz: {exc}") from exc
             self._rs_ids[rate] = self._rs.add(p)
-            need = max(need, rs.window_bound(self.crop_length, p.up, p.down, p.K))
+            need = max(need, rs.window_bound(self._plan_length, p.up, p.down, p.K))
         return need
 
     def _factors(self, rate):
@@ -294,7 +348,7 @@ class BatchFeeder:
 
     def _plan_full(self, epoch):
         """(the plan, [[(m0, M, rate)] per batch] or None)."""
-        n = len(self.dataset)
+        n, crop = len(self.dataset), self._plan_length
         rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch)]))
         perm = rng.permutation(n) if self.shuffle else np.arange(n)
         u = rng.random(n)
@@ -309,19 +363,27 @@ class BatchFeeder:
                 up, down, H, K = self._factors(rate)
                 M = rs.out_length(length, up, down)
                 m0, count = 0, M
-                if M > self.crop_length:
-                    room = M - self.crop_length
-                    m0, count = min(int(u[pos] * (room + 1)), room), self.crop_length
+                if M > crop:
+                    room = M - crop
+                    m0, count = min(int(u[pos] * (room + 1)), room), crop
                 entries.append((index,) + rs.crop_window(length, up, down, H, K, m0, count))
                 windows.append((m0, M, rate))
-            elif length <= self.crop_length:
+            elif length <= crop:
                 entries.append((index, 0, length))
             else:
-                room = length - self.crop_length
-                entries.append((index, min(int(u[pos] * (room + 1)), room), self.crop_length))
+                room = length - crop
+                entries.append((index, min(int(u[pos] * (room + 1)), room), crop))
         cuts = range(0, len(self) * self.batch_size, self.batch_size)
         return ([entries[i:i + self.batch_size] for i in cuts],
                 [windows[i:i + self.batch_size] for i in cuts] if self.sample_rate is not None else None)
+
+    def draws(self, epoch, k, nb=None):
+        """The ``AugmentDraws`` of batch ``k`` of ``epoch`` on this rank (None without augmentation): a function of
+        (seed, epoch, rank, k) and the config alone, whatever the workers do and wherever a run is resumed."""
+        if self.augment is None:
+            return None
+        rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch), self.rank, int(k), 0x417567]))
+        return self.augment.draw(rng, self.batch_size if nb is None else nb, self.crop_length)
 
     # ------------------------------------------------------------------ workers
     def _take_row(self):
@@ -343,15 +405,17 @@ class BatchFeeder:
         plan, windows = plan
         pend = self._pending.get(self._next_seq)
         if pend is None:
-            if windows is None:
+            try:
                 pend = _Pending(self._next_seq, epoch, plan[b])
-            else:
-                try:
-                    pend = _Pending(self._next_seq, epoch, plan[b], windows[b], self._records(plan[b], windows[b]))
-                except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
-                    self._failure = exc
-                    self._cv.notify_all()
-                    return None
+                if windows is not None:
+                    pend.windows, pend.records = windows[b], self._records(plan[b], windows[b])
+                if self.augment is not None:
+                    pend.draws = self.draws(epoch, b, len(plan[b]))
+                    pend.table = torch.from_numpy(pend.draws.pack(self._aug_k))
+            except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
+                self._failure = exc
+                self._cv.notify_all()
+                return None
             self._pending[self._next_seq] = pend
         taken, row = row, row + 1
         if row == len(plan[b]):
@@ -408,6 +472,8 @@ class BatchFeeder:
         stage, dev = self._stage[pend.seq % self.depth], self._dev[pend.seq % (self.depth + 1)]
         if pend.records is not None:
             stage.records()[:len(pend.entries)] = pend.records
+        if pend.table is not None:
+            stage.aug_table(pend.table.numel()).copy_(pend.table)
         if self._stream is None:
             dev.flat.copy_(stage.flat)
         else:
@@ -475,7 +541,7 @@ class BatchFeeder:
                                        f"{self.timeout_s:g} s")
                 time.sleep(1e-3)
         self.wait_upload_s += time.monotonic() - t1
-        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev, pend.windows, pend.records)
+        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev, pend.windows, pend.records, pend.draws)
         with self._cv:
             del self._pending[seq]
             self._returned = seq + 1                    # frees staging slot seq % depth; batch seq - depth goes stale

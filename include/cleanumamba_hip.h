@@ -950,6 +950,37 @@ int cum_pcm_batch_resample_f32(const int16_t *pcm, int64_t pitch, const int32_t 
                                const float *tables, int64_t table_floats, int64_t len, float *clean, int64_t clean_sb,
                                float *noisy, int64_t noisy_sb, void *stream);
 
+/* ---- training augmentation (csrc/augment.hip; training/augment.py) -----------------------------------
+ * cum_augment_pairs <- the hook of the train loop, src/training/train.py:262-265
+ *   (`noise = noisy_audio - clean_audio; noise, clean_audio = augment((noise, clean_audio)); noisy_audio = noise +
+ *   clean_audio`): exchange the noises within the batch, shift noise against speech, add a synthetic room, re-draw the
+ *   SNR and the level, from the assembled crops straight into the step's inputs.
+ *   clean_src / noisy_src: f32 rows of src_len samples, clean_src_sb / noisy_src_sb apart (C and Y below).
+ *   recs: device table, 8 int32 per row {perm, off_clean, off_noise, n_taps, snr_db (f32), gain (f32), kappa (f32), 0}.
+ *   tap_delay (i32) / tap_gain (f32): device tables of k_max entries per row, the first n_taps of them used.
+ *   For row b, p = perm[b], t < len, the sums over k < n_taps in ascending k as one fma chain, terms with
+ *   t < delay[b][k] dropped:
+ *     c0[t] = C[b][t + off_clean],  n0[t] = Y[p][t + off_noise] - C[p][t + off_noise]
+ *     rc[t] = sum_k tap_gain[b][k] c0[t - delay[b][k]],  rn[t] = sum_k tap_gain[b][k] n0[t - delay[b][k]]
+ *     c1 = c0 + kappa rc,  n1 = n0 + rn + (1 - kappa) rc
+ *     Ec = sum_t c1[t]^2, En = sum_t n1[t]^2 in f64, one fixed order
+ *     a = sqrt(Ec / (En 10^(snr_db / 10))) if snr_db is finite and Ec > 0 and En > 0, else 1
+ *     clean[b clean_sb + t] = gain c1[t],  noisy[b noisy_sb + t] = gain (c1[t] + a n1[t])
+ *   workspace: cum_augment_workspace_elems(batch, len) floats, 8-byte aligned; or NULL: no row has a finite snr_db (a
+ *   = 1 everywhere, snr_db is not read) and one launch does it all.  With a workspace there are two launches.  No
+ *   atomics: two runs give the same bits.  The kernel clamps perm into [0, batch), the offsets into [0, src_len - len]
+ *   and n_taps into [0, k_max], and drops a tap whose delay is below 1, so a bad table never indexes outside its rows.
+ *   The outputs must not overlap the sources (the caller's check).  Nothing is allocated, read on the host or waited for.
+ *   CUM_EINVAL before any launch: batch outside [1, 32767], len < 1, src_len < len (src_len is len plus the largest
+ *   offset), k_max outside [0, 512], a source stride below src_len, clean_sb or noisy_sb below len, a null pointer
+ *   (tap_delay / tap_gain may be NULL with k_max = 0), clean or noisy off a 16-byte boundary, workspace off an 8-byte
+ *   one, any other pointer off a 4-byte one. */
+int64_t cum_augment_workspace_elems(int32_t batch, int64_t len);
+int cum_augment_pairs(const float *clean_src, int64_t clean_src_sb, const float *noisy_src, int64_t noisy_src_sb,
+                      int32_t batch, int64_t len, int64_t src_len, const int32_t *recs, const int32_t *tap_delay,
+                      const float *tap_gain, int32_t k_max, float *workspace, float *clean, int64_t clean_sb,
+                      float *noisy, int64_t noisy_sb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
