@@ -1,5 +1,5 @@
 // In-LDS complex FFT of one wave (FusedFft<H>) and the packed real-input spectrum (packed_bin), shared by the fused
-// STFT loss (stft_loss.hip) and the speech metrics (metrics.hip).
+// STFT loss (stft_loss.hip), the speech metrics (metrics.hip) and the band-mask FFT convolution (bandmask.hip).
 #pragma once
 #include "common.h"
 
@@ -55,7 +55,7 @@ struct FusedFft {
   typedef typename FftVec<T>::v2 V2;
   __device__ static __forceinline__ V4 mk4(T a, T b, T c, T d) { return FftVec<T>::mk4(a, b, c, d); }
   __device__ static __forceinline__ V2 mk2(T a, T b) { return FftVec<T>::mk2(a, b); }
-  static constexpr int LOGH = H == 256 ? 8 : H == 512 ? 9 : 10;
+  static constexpr int LOGH = H == 256 ? 8 : H == 512 ? 9 : H == 1024 ? 10 : H == 2048 ? 11 : H == 4096 ? 12 : 13;
   static constexpr bool LEAD2 = (LOGH & 1) != 0;
   static constexpr int PER = H / 64;                 // points per lane
   static constexpr int SLOTS = H + H / 16;
@@ -69,7 +69,7 @@ struct FusedFft {
   // instruction-level overlap of their own; the smaller sizes run four or five waves per SIMD on <= 106 registers.
   // (Keeping each lane's stage twiddles in registers across its frames instead of looking them up in LDS was measured
   //  slower at every size: the 18 ... 44 extra registers cost a wave per SIMD, 117 -> 130 us on the 1024-point backward.)
-  static constexpr int UNR = H == 1024 ? 2 : 1;
+  static constexpr int UNR = H == 1024 ? 2 : H > 1024 ? 4 : 1;   // (H > 1024: the V2 form below, one wave per SIMD at most)
 
   __device__ static __forceinline__ int pad(int e) { return e + (e >> 4); }
 
@@ -190,6 +190,87 @@ struct FusedFft {
         const float2 a = ld(j), b = cmulc(ld(j + H / 2), twiddle(tw, j, H));
         st2(j, make_float2(a.x + b.x, a.y + b.y));
         st2(j + H / 2, make_float2(a.x - b.x, a.y - b.y));
+      }
+      stage_fence();
+    }
+  }
+  // ---- one complex signal per buffer (V2 elements): the overlap-save blocks of bandmask.hip, H = 4096.  The same index
+  // maps, twiddles and slot padding as the V4 form above; forward_c leaves X[k] at pos(k), inverse_c takes that order back
+  // to natural order, unnormalised.
+  __device__ static __forceinline__ V2 cmul2(V2 v, V2 w) { return mk2(v.x * w.x - v.y * w.y, v.x * w.y + v.y * w.x); }
+  __device__ static __forceinline__ V2 cmul2c(V2 v, V2 w) { return mk2(v.x * w.x + v.y * w.y, v.y * w.x - v.x * w.y); }   // v conj(w)
+  __device__ static __forceinline__ V2 add2(V2 a, V2 b) { return mk2(a.x + b.x, a.y + b.y); }
+  __device__ static __forceinline__ V2 sub2(V2 a, V2 b) { return mk2(a.x - b.x, a.y - b.y); }
+
+  __device__ static __forceinline__ void forward_c(V2 *buf, const V2 *tw, int lane) {
+    int L = H;
+    if constexpr (LEAD2) {
+#pragma unroll UNR
+      for (int i = 0; i < H / 128; ++i) {
+        const int j = lane + 64 * i;
+        const V2 a = buf[pad(j)], b = buf[pad(j + H / 2)];
+        buf[pad(j)] = add2(a, b);
+        buf[pad(j + H / 2)] = cmul2(sub2(a, b), twiddle(tw, j, H));
+      }
+      L = H / 2;
+      stage_fence();
+    }
+#pragma unroll
+    for (int st = 0; st < LOGH / 2; ++st, L >>= 2) {
+      const int q4 = L >> 2;
+#pragma unroll UNR
+      for (int i = 0; i < H / 256; ++i) {
+        const int q = lane + 64 * i;
+        const int j = q & (q4 - 1), p = ((q - j) << 2) + j;
+        const V2 a = buf[pad(p)], b = buf[pad(p + q4)], c = buf[pad(p + 2 * q4)], d = buf[pad(p + 3 * q4)];
+        const V2 t0 = add2(a, c), t1 = sub2(a, c), t2 = add2(b, d), u = sub2(b, d);
+        const V2 t3 = mk2(u.y, -u.x);                                          // (b - d) * (-i)
+        buf[pad(p)] = add2(t0, t2);
+        if (L > 4) {
+          buf[pad(p + q4)] = cmul2(add2(t1, t3), twiddle(tw, j, L));
+          buf[pad(p + 2 * q4)] = cmul2(sub2(t0, t2), twiddle(tw, 2 * j, L));
+          buf[pad(p + 3 * q4)] = cmul2(sub2(t1, t3), twiddle(tw, 3 * j, L));
+        } else {
+          buf[pad(p + q4)] = add2(t1, t3);
+          buf[pad(p + 2 * q4)] = sub2(t0, t2);
+          buf[pad(p + 3 * q4)] = sub2(t1, t3);
+        }
+      }
+      stage_fence();
+    }
+  }
+
+  __device__ static __forceinline__ void inverse_c(V2 *buf, const V2 *tw, int lane) {
+    int L = 4;
+#pragma unroll
+    for (int stg = 0; stg < LOGH / 2; ++stg, L <<= 2) {
+      const int q4 = L >> 2;
+#pragma unroll UNR
+      for (int i = 0; i < H / 256; ++i) {
+        const int q = lane + 64 * i;
+        const int j = q & (q4 - 1), p = ((q - j) << 2) + j;
+        V2 a = buf[pad(p)], b = buf[pad(p + q4)], c = buf[pad(p + 2 * q4)], d = buf[pad(p + 3 * q4)];
+        if (L > 4) {
+          b = cmul2c(b, twiddle(tw, j, L));
+          c = cmul2c(c, twiddle(tw, 2 * j, L));
+          d = cmul2c(d, twiddle(tw, 3 * j, L));
+        }
+        const V2 s0 = add2(a, c), s1 = sub2(a, c), s2 = add2(b, d), u = sub2(b, d);
+        const V2 s3 = mk2(-u.y, u.x);                                          // i (b - d)
+        buf[pad(p)] = add2(s0, s2);
+        buf[pad(p + q4)] = add2(s1, s3);
+        buf[pad(p + 2 * q4)] = sub2(s0, s2);
+        buf[pad(p + 3 * q4)] = sub2(s1, s3);
+      }
+      stage_fence();
+    }
+    if constexpr (LEAD2) {
+#pragma unroll UNR
+      for (int i = 0; i < H / 128; ++i) {
+        const int j = lane + 64 * i;
+        const V2 a = buf[pad(j)], b = cmul2c(buf[pad(j + H / 2)], twiddle(tw, j, H));
+        buf[pad(j)] = add2(a, b);
+        buf[pad(j + H / 2)] = sub2(a, b);
       }
       stage_fence();
     }

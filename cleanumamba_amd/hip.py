@@ -215,6 +215,9 @@ SIGNATURES = {
     "cum_augment_workspace_elems": (c_i64, [c_i32, c_i64]),
     "cum_augment_pairs": (c_i32, [_P, c_i64, _P, c_i64, c_i32, c_i64, c_i64, _P, _P, _P, c_i32, _P, _P, c_i64, _P, c_i64,
                                   _P]),
+    "cum_band_mask_block": (c_i32, []),
+    "cum_band_mask_workspace_elems": (c_i64, [c_i32]),
+    "cum_band_mask_pairs": (c_i32, [_P, c_i64, _P, c_i64, c_i32, c_i64, _P, _P, _P, c_i64, _P, c_i64, _P]),
 }
 
 _lib = None

@@ -5,7 +5,8 @@
     # noisy_audio = noise + clean_audio
 
 with the augmentation family of the denoiser lineage CleanUNet comes from: exchange the noises within the batch (remix),
-shift noise against speech, re-draw the SNR and the level, add a synthetic room (echo).  DESIGN.md 7h.
+shift noise against speech, re-draw the SNR and the level, add a synthetic room (echo), remove a mel band from speech and
+noise alike (BandMask).  DESIGN.md 7h.
 
 Two halves, kept apart:
 
@@ -26,7 +27,14 @@ The sources are the clean and noisy crops ``shift`` samples LONGER than the batc
 (k ascending, terms with t < delay dropped).  ``BatchFeeder(..., augment=Augment(...))`` (training/feeder.py) draws per
 batch from its own generator and runs this between the assembling kernel and the train step's inputs.
 
-Left out on purpose: BandMask, whose mel-edge low-pass filters are some 3 200 taps long and want an FFT convolution.
+BandMask is a stage of its own in front of that arithmetic: with a band drawn (``band_half`` W > 0, cutoffs ``band_lo``
+<= ``band_hi`` in cycles per sample), both source rows, zero outside their L + S samples, are filtered by
+
+    w[k] = 0.54 - 0.46 cos(pi (k + W) / W),  lp_c[k] = 2 c sinc(2 c k) w[k],  h[k] = [k == 0] + lp_lo[k] - lp_hi[k]
+
+(k = -W..W, in f64, h rounded to f32) and everything above reads the filtered rows in place of C and Y.  The filters are
+up to 3 201 taps long: csrc/bandmask.hip (cum_band_mask_pairs) applies them by overlap-save on an in-LDS FFT;
+``band_mask`` is that stage alone, ``apply`` runs it first when any row has a band.
 """
 import ctypes
 import math
@@ -39,6 +47,8 @@ from .. import hip
 K_MAX = 512                      # taps per row the kernel takes (csrc/augment.hip)
 REC_INTS = 8                     # one record per row: the fields below, then zeros
 REC_PERM, REC_OFF_CLEAN, REC_OFF_NOISE, REC_N_TAPS, REC_SNR_DB, REC_GAIN, REC_KAPPA = range(7)
+W_MAX = 1600                     # the longest half-width the band-mask kernel takes (csrc/bandmask.hip)
+BAND_INTS = 4                    # one band record per row: W, c_lo (f32 bits), c_hi (f32 bits), 0
 
 
 def _range(value, name):
@@ -101,12 +111,62 @@ class Echo:
         return taps
 
 
+def mel_edges(bands=120, min_freq=40.0, sample_rate=16000):
+    """The ``bands`` band edges in cycles per sample, float32: evenly spaced on the mel scale mel(f) = 2595 log10(1 +
+    f / 700) from ``min_freq`` to ``sample_rate / 2``, computed in f64 and rounded once."""
+    lo, hi = (2595.0 * np.log10(1.0 + f / 700.0) for f in (float(min_freq), sample_rate / 2.0))
+    hz = 700.0 * (10.0 ** (np.linspace(lo, hi, int(bands)) / 2595.0) - 1.0)
+    return (hz / sample_rate).astype(np.float32)
+
+
+def band_taps(W, c_lo, c_hi):
+    """h[-W..W] of the module's docstring for float32 cutoffs: evaluated in f64, returned as float32."""
+    W, lo, hi = int(W), float(np.float32(c_lo)), float(np.float32(c_hi))
+    k = np.arange(-W, W + 1, dtype=np.float64)
+    w = 0.54 - 0.46 * np.cos(np.pi * (k + W) / W)
+    h = 2 * lo * np.sinc(2 * lo * k) * w - 2 * hi * np.sinc(2 * hi * k) * w
+    h[W] += 1.0
+    return h.astype(np.float32)
+
+
+class BandMask:
+    """Remove one band between two of ``bands`` mel edges from speech and noise alike.  With probability ``proba`` per
+    batch: lo uniform over the edges, hi uniform in [lo, min(bands, lo + bandwidth)), bandwidth = int(maxwidth bands);
+    the filter's half-width is W = int(2 / c_lo), c_lo the lower edge in cycles per sample (float32).  The constructor
+    refuses a config whose lowest edge needs more than W_MAX."""
+
+    def __init__(self, maxwidth=0.2, bands=120, min_freq=40.0, proba=1.0, sample_rate=16000):
+        self.maxwidth, self.bands, self.min_freq = float(maxwidth), int(bands), float(min_freq)
+        self.proba, self.sample_rate = float(proba), int(sample_rate)
+        if not (self.bands >= 2 and self.sample_rate >= 1 and 0 < self.min_freq < self.sample_rate / 2
+                and 0 <= self.proba <= 1):
+            raise ValueError("BandMask: bands >= 2, 0 < min_freq < sample_rate / 2 and proba in [0, 1] are required")
+        self.bandwidth = int(self.maxwidth * self.bands)
+        if self.bandwidth < 1:
+            raise ValueError(f"BandMask: maxwidth {self.maxwidth:g} of {self.bands} bands is no band at all")
+        self.edges = mel_edges(self.bands, self.min_freq, self.sample_rate)
+        self.max_half = int(2.0 / float(self.edges[0]))
+        if self.max_half > W_MAX:
+            raise ValueError(f"BandMask: the edge at {self.min_freq:g} Hz needs a filter of half-width {self.max_half}, "
+                             f"more than the kernel's {W_MAX}")
+
+    def draw(self, rng):
+        """(W, c_lo, c_hi) of one batch; (0, 0, 0) with probability 1 - proba."""
+        if not rng.random() < self.proba:
+            return 0, np.float32(0), np.float32(0)
+        lo = int(rng.integers(0, self.bands))
+        hi = int(rng.integers(lo, min(self.bands, lo + self.bandwidth)))
+        return int(2.0 / float(self.edges[lo])), self.edges[lo], self.edges[hi]
+
+
 class AugmentDraws:
     """Everything random about one batch of ``nb`` rows of ``length`` samples, as the kernel reads it: int32 ``perm``,
     ``off_clean``, ``off_noise``, ``n_taps`` (nb,) and ``delay`` (nb, K_MAX); float32 ``snr_db`` (NaN: keep), ``gain``,
-    ``kappa`` (nb,) and ``tap_gain`` (nb, K_MAX).  ``shift``: the sources are ``length + shift`` long."""
+    ``kappa`` (nb,) and ``tap_gain`` (nb, K_MAX).  ``shift``: the sources are ``length + shift`` long.  The band of every
+    row (default: none): int32 ``band_half`` W (0: no band), float32 ``band_lo`` <= ``band_hi`` in cycles per sample."""
 
-    def __init__(self, length, shift, perm, off_clean, off_noise, snr_db, gain, kappa, n_taps, delay, tap_gain):
+    def __init__(self, length, shift, perm, off_clean, off_noise, snr_db, gain, kappa, n_taps, delay, tap_gain,
+                 band_half=None, band_lo=None, band_hi=None):
         self.length, self.shift = int(length), int(shift)
         self.perm, self.off_clean, self.off_noise, self.n_taps = (np.ascontiguousarray(v, dtype=np.int32)
                                                                   for v in (perm, off_clean, off_noise, n_taps))
@@ -114,9 +174,13 @@ class AugmentDraws:
         self.delay = np.ascontiguousarray(delay, dtype=np.int32)
         self.tap_gain = np.ascontiguousarray(tap_gain, dtype=np.float32)
         nb = self.perm.shape[0]
+        zeros = np.zeros(nb)
+        self.band_half = np.ascontiguousarray(zeros if band_half is None else band_half, dtype=np.int32)
+        self.band_lo, self.band_hi = (np.ascontiguousarray(zeros if v is None else v, dtype=np.float32)
+                                      for v in (band_lo, band_hi))
         if self.length < 1 or self.shift < 0 or nb < 1:
             raise ValueError("AugmentDraws: length >= 1, shift >= 0 and at least one row are required")
-        for name in ("off_clean", "off_noise", "n_taps", "snr_db", "gain", "kappa"):
+        for name in ("off_clean", "off_noise", "n_taps", "snr_db", "gain", "kappa", "band_half", "band_lo", "band_hi"):
             if getattr(self, name).shape != (nb,):
                 raise ValueError(f"AugmentDraws: {name} must have shape ({nb},)")
         if self.delay.shape != self.tap_gain.shape or self.delay.ndim != 2 or self.delay.shape[0] != nb \
@@ -128,6 +192,11 @@ class AugmentDraws:
             raise ValueError("AugmentDraws: offsets must lie in [0, shift]")
         if self.n_taps.min() < 0 or self.n_taps.max() > self.delay.shape[1]:
             raise ValueError("AugmentDraws: n_taps must lie in [0, K]")
+        if self.band_half.min() < 0 or self.band_half.max() > W_MAX:
+            raise ValueError(f"AugmentDraws: band_half must lie in [0, {W_MAX}]")
+        if not (np.isfinite(self.band_lo).all() and np.isfinite(self.band_hi).all() and self.band_lo.min() >= 0
+                and (self.band_lo <= self.band_hi).all() and self.band_hi.max() <= 0.5):
+            raise ValueError("AugmentDraws: 0 <= band_lo <= band_hi <= 0.5 (cycles per sample) is required")
 
     @property
     def batch(self):
@@ -137,6 +206,22 @@ class AugmentDraws:
     def rescales(self):
         """Whether any row re-draws its SNR (the kernel then needs its second launch and a workspace)."""
         return bool(np.isfinite(self.snr_db).any())
+
+    @property
+    def banded(self):
+        """Whether any row has a band to remove (the band-mask stage then runs in front of the rest)."""
+        return bool(self.band_half.any())
+
+    def without_band(self):
+        """The same draws with no band on any row."""
+        return AugmentDraws(self.length, self.shift, self.perm, self.off_clean, self.off_noise, self.snr_db, self.gain,
+                            self.kappa, self.n_taps, self.delay, self.tap_gain)
+
+    def pack_band(self):
+        """The bands as one int32 array: nb records {W, c_lo (its bits), c_hi (its bits), 0}."""
+        out = np.zeros((self.batch, BAND_INTS), dtype=np.int32)
+        out[:, 0], out[:, 1], out[:, 2] = self.band_half, self.band_lo.view(np.int32), self.band_hi.view(np.int32)
+        return out.reshape(-1)
 
     def columns(self):
         """Tap columns a packed table of these draws needs: the longest list, rounded up to 4."""
@@ -165,29 +250,37 @@ def table_ints(nb, k):
     return nb * (REC_INTS + 2 * k)
 
 
+def band_ints(nb):
+    """int32 entries of the packed bands of nb rows."""
+    return BAND_INTS * nb
+
+
 class Augment:
-    """``Augment(remix=False, shift=0, snr_db=None, gain_db=None, echo=None)``
+    """``Augment(remix=False, shift=0, snr_db=None, gain_db=None, echo=None, band_mask=None)``
 
     remix: every row gets the noise of a row drawn by one uniform permutation of the batch.
     shift: speech and noise each start at their own uniform offset in [0, shift] of crops ``shift`` samples longer.
     snr_db: (lo, hi) -- the noise is rescaled so that the row's SNR is uniform in the range -- or None (keep).
     gain_db: (lo, hi) -- both signals are scaled by 10^(g / 20), g uniform in the range -- or None.
     echo: ``Echo(...)`` or None.
+    band_mask: ``BandMask(...)`` or None: one band per batch is removed from speech and noise before everything else.
     A config with every transform off is ``inactive`` and is treated by its users exactly as no augmentation."""
 
-    def __init__(self, remix=False, shift=0, snr_db=None, gain_db=None, echo=None):
+    def __init__(self, remix=False, shift=0, snr_db=None, gain_db=None, echo=None, band_mask=None):
         self.remix, self.shift = bool(remix), int(shift)
         self.snr_db, self.gain_db = _range(snr_db, "snr_db"), _range(gain_db, "gain_db")
         if self.shift < 0:
             raise ValueError("Augment: shift must be at least 0")
         if echo is not None and not isinstance(echo, Echo):
             raise ValueError("Augment: echo must be an Echo or None")
-        self.echo = echo
+        if band_mask is not None and not isinstance(band_mask, BandMask):
+            raise ValueError("Augment: band_mask must be a BandMask or None")
+        self.echo, self.band_mask = echo, band_mask
 
     @property
     def active(self):
         return self.remix or self.shift > 0 or self.snr_db is not None or self.gain_db is not None \
-            or self.echo is not None
+            or self.echo is not None or self.band_mask is not None
 
     @property
     def max_taps(self):
@@ -196,8 +289,8 @@ class Augment:
 
     def draw(self, rng, nb, length):
         """The draws of one batch from ``rng`` (a numpy Generator), in this order: the permutation; nb clean offsets;
-        nb noise offsets; nb SNRs; nb gains; then row by row the echo (Echo.draw).  A transform that is off draws
-        nothing."""
+        nb noise offsets; nb SNRs; nb gains; then row by row the echo (Echo.draw); last the
+        batch's one band (BandMask.draw), copied into every row.  A transform that is off draws nothing."""
         nb, length = int(nb), int(length)
         perm = rng.permutation(nb) if self.remix else np.arange(nb)
         if self.shift > 0:
@@ -216,7 +309,11 @@ class Augment:
                 n_taps[b] = len(taps)          # (at most echo.max_taps <= K_MAX: the constructor's worst case)
                 if taps:
                     delay[b, :len(taps)], tap_gain[b, :len(taps)] = zip(*taps)
-        return AugmentDraws(length, self.shift, perm, off_clean, off_noise, snr, gain, kappa, n_taps, delay, tap_gain)
+        band = ()
+        if self.band_mask is not None:
+            band = [np.full(nb, v) for v in self.band_mask.draw(rng)]
+        return AugmentDraws(length, self.shift, perm, off_clean, off_noise, snr, gain, kappa, n_taps, delay, tap_gain,
+                            *band)
 
 
 # ---------------------------------------------------------------------------------------------------------------- apply
@@ -281,15 +378,71 @@ def workspace_for(nb, length, device):
     return torch.empty(max(1, hip.lib().cum_augment_workspace_elems(nb, length) // 2), dtype=torch.float64, device=device)
 
 
+def band_workspace_for(nb, device):
+    """The twiddle table's and the spectra's room for a batch of nb rows (8-byte aligned: a fresh tensor)."""
+    return torch.empty(hip.lib().cum_band_mask_workspace_elems(nb), dtype=torch.float32, device=device)
+
+
+def launch_band(clean_src, cs, noisy_src, ys, nb, n, recs, workspace, clean, co, noisy, no):
+    """cum_band_mask_pairs on the current stream.  recs: the device int32 tensor of ``AugmentDraws.pack_band()``;
+    workspace: a device tensor of cum_band_mask_workspace_elems floats."""
+    hip.check(hip.lib().cum_band_mask_pairs(hip.ptr(clean_src), cs, hip.ptr(noisy_src), ys, nb, n, hip.ptr(recs),
+                                            hip.ptr(workspace), hip.ptr(clean), co, hip.ptr(noisy), no, hip.stream_ptr()))
+
+
+def band_mask(clean_src, noisy_src, draws, clean_out=None, noisy_out=None):
+    """The band-mask stage alone: both sources, float32 (B, n) or (B, 1, n) with n = draws.length + draws.shift, filtered
+    row by row with the taps of (draws.band_half, band_lo, band_hi) into clean_out, noisy_out of the same shape (made
+    here if not given; on a GPU they start on a 16-byte boundary and must not overlap the sources).  Device tensors go
+    through cum_band_mask_pairs on the current stream; CPU tensors through a float32 direct convolution with the same
+    float32 taps.  A row with band_half = 0 is copied."""
+    nb, n = draws.batch, draws.length + draws.shift
+    dev = clean_src.device
+    cs, three = _rows(clean_src, "clean_src", nb, n)
+    ys, _ = _rows(noisy_src, "noisy_src", nb, n)
+    if clean_out is None:
+        clean_out = torch.empty((nb, 1, n) if three else (nb, n), dtype=torch.float32, device=dev)
+    if noisy_out is None:
+        noisy_out = torch.empty((nb, 1, n) if three else (nb, n), dtype=torch.float32, device=dev)
+    co, _ = _rows(clean_out, "clean_out", nb, n)
+    no, _ = _rows(noisy_out, "noisy_out", nb, n)
+    if not (noisy_src.device == clean_out.device == noisy_out.device == dev):
+        raise ValueError("augment.band_mask: all tensors must be on one device")
+    spans = [_span(clean_src, cs, nb, n), _span(noisy_src, ys, nb, n)]
+    outs = [_span(clean_out, co, nb, n), _span(noisy_out, no, nb, n)]
+    if any(o[0] < s[1] and s[0] < o[1] for o in outs for s in spans) or (outs[0][0] < outs[1][1] and outs[1][0] < outs[0][1]):
+        raise ValueError("augment.band_mask: the outputs must not overlap the sources or each other")
+    if dev.type == "cpu":
+        for src, sb, out, ob in ((clean_src, cs, clean_out, co), (noisy_src, ys, noisy_out, no)):
+            x, y = torch.as_strided(src, (nb, n), (sb, 1)), torch.as_strided(out, (nb, n), (ob, 1))
+            for b in range(nb):
+                W = int(draws.band_half[b])
+                if W == 0:
+                    y[b] = x[b]
+                    continue
+                h = torch.from_numpy(band_taps(W, draws.band_lo[b], draws.band_hi[b]))     # (symmetric: no flip)
+                y[b] = torch.nn.functional.conv1d(x[b].reshape(1, 1, n), h.reshape(1, 1, -1), padding=W).reshape(n)
+        return clean_out, noisy_out
+    hip.require_gpu(clean_src, noisy_src, clean_out, noisy_out)
+    with torch.cuda.device(dev):
+        recs = torch.from_numpy(draws.pack_band()).to(dev)
+        launch_band(clean_src, cs, noisy_src, ys, nb, n, recs, band_workspace_for(nb, dev), clean_out, co, noisy_out, no)
+    return clean_out, noisy_out
+
+
 def apply(clean_src, noisy_src, draws, clean_out=None, noisy_out=None):
     """(clean', noisy') of the module's docstring.  clean_src, noisy_src: float32 (B, L + S) or (B, 1, L + S) tensors on
     one device, unit stride along time, L = draws.length, S = draws.shift; clean_out, noisy_out: (B, L) or (B, 1, L), made
     here (in the sources' form) if not given; on a GPU they start on a 16-byte boundary and must not overlap the sources.
-    Device tensors go through cum_augment_pairs on the current stream, CPU tensors through torch on the host."""
+    Device tensors go through cum_augment_pairs on the current stream, CPU tensors through torch on the host.  When any
+    row has a band, the sources first pass through ``band_mask`` into scratch allocated here."""
     nb, L, n = draws.batch, draws.length, draws.length + draws.shift
     dev = clean_src.device
     cs, three = _rows(clean_src, "clean_src", nb, n)
     ys, _ = _rows(noisy_src, "noisy_src", nb, n)
+    if draws.banded:
+        clean_src, noisy_src = band_mask(clean_src, noisy_src, draws)
+        cs, ys = (t.stride(0) if nb > 1 else n for t in (clean_src, noisy_src))
     if clean_out is None:
         clean_out = torch.empty((nb, 1, L) if three else (nb, L), dtype=torch.float32, device=dev)
     if noisy_out is None:

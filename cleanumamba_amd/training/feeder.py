@@ -35,8 +35,9 @@ cum_pcm_batch_f32's arithmetic, so an all-16 kHz dataset gives the unrated feede
 ``BatchFeeder(..., augment=Augment(...))`` (training/augment.py) augments every batch on that last step:
 the plan crops ``shift`` samples more, the batch's draws -- from a generator of their own per (seed, epoch, rank, batch)
 -- ride in the slot's tail in the same upload, the assembling kernel writes the longer crops into float scratch the
-feeder owns, and cum_augment_pairs (csrc/augment.hip) writes the batch into the step's inputs.  Without ``augment``
-nothing here changes.
+feeder owns, and cum_augment_pairs (csrc/augment.hip) writes the batch into the step's inputs.  With a ``band_mask`` in
+the config the band records follow the draw table in the same upload, and cum_band_mask_pairs (csrc/bandmask.hip) runs
+between the two, from that scratch into a second pair the block owns.  Without ``augment`` nothing here changes.
 
 ``device="cpu"`` keeps the same pipeline without pinning or streams and does the kernel's arithmetic with torch on the
 host, so the loop runs anywhere -- a rated feeder too, as long as every pair is at the model rate: there is no CPU
@@ -64,14 +65,15 @@ def _round_up(n, m):
 
 class _Slot:
     """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths -- in a rated feeder by
-    ``batch`` records of 16 int32 -- and, in an augmenting feeder, by ``aug_ints`` int32 of draw table, as one int16 tensor
-    so that it moves in one copy."""
+    ``batch`` records of 16 int32 -- and, in an augmenting feeder, by ``aug_ints`` int32 of draw table (with a band mask:
+    the band records behind it), as one int16 tensor so that it moves in one copy."""
 
     def __init__(self, batch, pitch, device, pin, tail_ints=1, aug_ints=0):
         self.batch, self.pitch = batch, pitch
         self._aug = 2 * batch * pitch + 2 * tail_ints * batch       # an augmenting feeder's draw table starts here
         self.flat = torch.zeros(self._aug + 2 * aug_ints, dtype=torch.int16, device=device, pin_memory=pin)
         self.scratch = self.workspace = None     # device blocks of an augmenting feeder: the L + S float crops, tile sums
+        self.band_scratch = self.band_workspace = None       # ... with a band mask: the filtered crops, the spectra
         self.seq = -1                # the batch this block holds
         self.uploaded = None         # event after the upload (device blocks on a GPU)
         self.released = []           # events after the assembling kernels that read this block
@@ -87,6 +89,10 @@ class _Slot:
         """The first ``ints`` int32 of the draw table (training/augment.py: AugmentDraws.pack)."""
         return self.flat[self._aug:self._aug + 2 * ints].view(torch.int32)
 
+    def band_table(self, at, ints):
+        """``ints`` int32 of band records (AugmentDraws.pack_band) behind a draw table of ``at`` int32."""
+        return self.flat[self._aug + 2 * at:self._aug + 2 * (at + ints)].view(torch.int32)
+
     def records(self):
         """(batch, 16) int32 view of a rated slot's tail (8-byte aligned: a row is 16 bytes times a whole number)."""
         return self.flat[2 * self.batch * self.pitch:self._aug].view(torch.int32).view(self.batch, rs.REC_INTS)
@@ -95,10 +101,11 @@ class _Slot:
 class _Pending:
     """A batch on its way through the staging slots."""
 
-    def __init__(self, seq, epoch, entries, windows=None, records=None, draws=None, table=None):
+    def __init__(self, seq, epoch, entries, windows=None, records=None, draws=None, table=None, band=None):
         self.seq, self.epoch, self.entries = seq, epoch, entries
         self.windows, self.records = windows, records        # a rated feeder's: [(m0, M, rate)], (nb, 16) int32 on the host
         self.draws, self.table = draws, table                # an augmenting feeder's: AugmentDraws, its packed int32 table
+        self.band = band                                     # ... with a band mask: its packed band records
         self.todo = len(entries)     # rows not read yet
         self.error = None
 
@@ -173,6 +180,12 @@ class PcmBatch:
                     hip.ptr(slot.flat), slot.pitch, hip.ptr(self._records), hip.ptr(slot.records()), nb,
                     *self._feeder._rs.args(), length, hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
                     ctypes.c_void_p(stream.cuda_stream)))
+            if self.draws is not None and self._feeder._band_at is not None:     # scratch -> the block's second pair
+                src = (clean, strides[0], noisy, strides[1])
+                clean, noisy = slot.band_scratch
+                strides = [clean.stride(0), noisy.stride(0)]
+                aug.launch_band(*src, nb, length, slot.band_table(self._feeder._band_at, aug.band_ints(nb)),
+                                slot.band_workspace, clean, strides[0], noisy, strides[1])
             if self.draws is not None:
                 k = self._feeder._aug_k
                 aug.launch(clean, strides[0], noisy, strides[1], nb, self.shape[2], length,
@@ -214,7 +227,8 @@ class BatchFeeder:
       ``numpy.random.Generator(PCG64([seed, e, rank, k, 0x417567]))`` -- never from the plan's generator -- and are the
       batch's ``draws``; they travel in the slot's tail, in the same one upload.  With ``shift = S > 0`` the plan draws
       crops of ``crop_length + S`` (model-rate) samples; otherwise the plan is the one without augmentation.  A config
-      with every transform off is taken as None."""
+      with every transform off is taken as None.  With ``band_mask`` the band records ride behind the draw table and
+      every batch takes one more launch pair (csrc/bandmask.hip) between the assembling kernel and the augmenting one."""
 
     def __init__(self, dataset, batch_size, device, crop_length=None, shuffle=True, seed=0, drop_last=True, depth=2,
                  workers=4, rank=0, world=1, timeout_s=60, sample_rate=None, augment=None):
@@ -254,6 +268,9 @@ class BatchFeeder:
         tail = 1 if self.sample_rate is None else rs.REC_INTS
         self._aug_k = self.augment.max_taps if self.augment is not None else 0       # tap columns of the draw table
         table = aug.table_ints(self.batch_size, self._aug_k) if self.augment is not None else 0
+        self._band_at = None                    # with a band mask: where its records start, in int32 behind the draw table
+        if self.augment is not None and self.augment.band_mask is not None:
+            self._band_at, table = table, table + aug.band_ints(self.batch_size)
         self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu, tail, table) for _ in range(self.depth)]
         self._stage_np = [s.flat.numpy() for s in self._stage]
         # one device block more than staging slots: batch k + 1 is uploaded while k and the depth - 1 before it are live
@@ -264,6 +281,10 @@ class BatchFeeder:
                                                   device=self.device)[:, :self._plan_length] for _ in range(2))
                 if self.augment.snr_db is not None:
                     block.workspace = aug.workspace_for(self.batch_size, self.crop_length, self.device)
+                if self._band_at is not None:
+                    block.band_scratch = tuple(torch.empty(self.batch_size, t.stride(0), dtype=torch.float32,
+                                                           device=self.device)[:, :self._plan_length] for t in block.scratch)
+                    block.band_workspace = aug.band_workspace_for(self.batch_size, self.device)
         self._stream = torch.cuda.Stream(self.device) if gpu else None
 
         self._cv = threading.Condition()
@@ -412,6 +433,8 @@ class BatchFeeder:
                 if self.augment is not None:
                     pend.draws = self.draws(epoch, b, len(plan[b]))
                     pend.table = torch.from_numpy(pend.draws.pack(self._aug_k))
+                    if self._band_at is not None:
+                        pend.band = torch.from_numpy(pend.draws.pack_band())
             except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
                 self._failure = exc
                 self._cv.notify_all()
@@ -474,6 +497,8 @@ class BatchFeeder:
             stage.records()[:len(pend.entries)] = pend.records
         if pend.table is not None:
             stage.aug_table(pend.table.numel()).copy_(pend.table)
+        if pend.band is not None:
+            stage.band_table(self._band_at, pend.band.numel()).copy_(pend.band)
         if self._stream is None:
             dev.flat.copy_(stage.flat)
         else:

@@ -981,6 +981,33 @@ int cum_augment_pairs(const float *clean_src, int64_t clean_src_sb, const float 
                       const float *tap_gain, int32_t k_max, float *workspace, float *clean, int64_t clean_sb,
                       float *noisy, int64_t noisy_sb, void *stream);
 
+/* ---- BandMask (csrc/bandmask.hip; training/augment.py) ----------------------------------------------
+ * cum_band_mask_pairs <- the same hook of the train loop, src/training/train.py:262-265 (`noise, clean_audio =
+ *   augment((noise, clean_audio))`): the BandMask of the denoiser lineage, a band-stop between two mel edges applied
+ *   to speech and noisy alike, as the stage in front of cum_augment_pairs.
+ *   clean_src / noisy_src: f32 rows of n samples, clean_src_sb / noisy_src_sb apart (C and Y below, zero outside [0, n)).
+ *   recs: device table, 4 int32 per row {W, c_lo (f32), c_hi (f32), 0}: the half-width and the two cutoffs in cycles
+ *   per sample.  For a row with W > 0, k = -W..W, everything in f64 and h then rounded to f32:
+ *     w[k]    = 0.54 - 0.46 cos(pi (k + W) / W)
+ *     lp_c[k] = 2 c sinc(2 c k) w[k],  sinc(x) = sin(pi x) / (pi x), sinc(0) = 1
+ *     h[k]    = [k == 0] + lp_lo[k] - lp_hi[k]
+ *     clean[b clean_sb + t] = sum_k h[k] C[b][t - k],  noisy[b noisy_sb + t] = sum_k h[k] Y[b][t - k],  t in [0, n)
+ *   by overlap-save on an in-LDS FFT of cum_band_mask_block() points (z = C + i Y: one transform pair filters both).
+ *   A row with W = 0 is copied bit for bit.  The kernel clamps W into [0, 1600] and takes a row whose cutoffs are not
+ *   finite or not 0 <= c_lo <= c_hi <= 0.5 as W = 0, so a bad table never indexes anywhere.
+ *   workspace: cum_band_mask_workspace_elems(batch) floats, 8-byte aligned (the twiddle table and one spectrum per
+ *   row; written by the first of the two launches, read by the second).  No atomics: two runs give the same bits, and a
+ *   row's result does not depend on the rest of the batch.  Nothing outside [row, row + n) is read or written.
+ *   The outputs must not overlap the sources (the caller's check).  Nothing is allocated, read on the host or waited for.
+ *   CUM_EINVAL before any launch: batch outside [1, 32767], n < 1, a stride below n, a null pointer, clean or noisy off
+ *   a 16-byte boundary, workspace off an 8-byte one, any other pointer off a 4-byte one.
+ * cum_band_mask_block: N, the FFT length; a row with half-width W is cut into blocks of V = N - 2 W outputs. */
+int32_t cum_band_mask_block(void);
+int64_t cum_band_mask_workspace_elems(int32_t batch);
+int cum_band_mask_pairs(const float *clean_src, int64_t clean_src_sb, const float *noisy_src, int64_t noisy_src_sb,
+                        int32_t batch, int64_t n, const int32_t *recs, float *workspace, float *clean, int64_t clean_sb,
+                        float *noisy, int64_t noisy_sb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

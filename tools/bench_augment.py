@@ -16,6 +16,13 @@ Two measurements, the E8 batch of bench.py throughout (B = 16, 10 s crops = 160 
             Q  the same with remix + shift + SNR + gain;
             R  the same plus the default echo.
 
+With ``--band`` the same two measurements for the band-mask stage (csrc/bandmask.hip) instead:
+
+  alone   cum_band_mask_pairs (two launches) on L + shift samples per row, every row at the lowest band (W = 800, the
+          longest default filter) and at a mid band (edges 60 and 80, W = 17).  Bytes: per signal n read, the halo
+          re-reads 2 W / V of n, n written; against the time, the fraction of the HBM rate.
+  fed     P and Q as above and M: Q plus the default ``BandMask``.
+
 The last line is the result as JSON.
 """
 import argparse
@@ -60,6 +67,7 @@ def main():
     ap.add_argument("--shift", type=int, default=8000)
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "f32"])
     ap.add_argument("--skip-fed", action="store_true", help="only the launches alone")
+    ap.add_argument("--band", action="store_true", help="measure the band-mask stage instead of the echo")
     ap.add_argument("--out", default=None, help="also write the JSON result here")
     args = ap.parse_args()
 
@@ -89,7 +97,25 @@ def main():
     clean, noisy = torch.empty(B, 1, L, device=dev), torch.empty(B, 1, L, device=dev)
     work = A.workspace_for(B, L, dev)
     alone = {}
-    for tag, taps, snr in (("echo_off_snr", 0, True), ("echo_off_keep", 0, False), ("echo_435_taps_snr", 435, True)):
+    if args.band:
+        n, N, edges = L + S, hip.lib().cum_band_mask_block(), A.mel_edges()
+        out_c, out_y = torch.empty(B, n, device=dev), torch.empty(B, n, device=dev)
+        band_work = A.band_workspace_for(B, dev)
+        for tag, lo, hi in (("band_0_23", 0, 23), ("band_60_80", 60, 80)):
+            W = int(2.0 / float(edges[lo]))
+            draws = full_draws(B, L, S, 0, False)
+            draws = A.AugmentDraws(L, S, draws.perm, draws.off_clean, draws.off_noise, draws.snr_db, draws.gain, draws.kappa,
+                                   draws.n_taps, draws.delay, draws.tap_gain, np.full(B, W), np.full(B, edges[lo]),
+                                   np.full(B, edges[hi]))
+            recs = torch.from_numpy(draws.pack_band()).to(dev)
+            ms = timed(lambda: A.launch_band(C, n, Y, n, B, n, recs, band_work, out_c, n, out_y, n))
+            moved = int(4 * B * n * 2 * (2 + 2 * W / (N - 2 * W)))
+            alone[tag] = {"ms": round(ms, 4), "launches": 2, "W": W, "block": N, "valid_per_block": N - 2 * W, "bytes": moved,
+                          "TB_per_s": round(moved / (ms * 1e-3) / 1e12, 3),
+                          "frac_of_hbm_peak": round(moved / (ms * 1e-3) / HBM_PEAK, 3)}
+            print(f"alone {tag}: {alone[tag]}", flush=True)
+    for tag, taps, snr in (() if args.band else
+                           (("echo_off_snr", 0, True), ("echo_off_keep", 0, False), ("echo_435_taps_snr", 435, True))):
         draws = full_draws(B, L, S, taps, snr)
         k = draws.columns()
         table = torch.from_numpy(draws.pack(k)).to(dev)
@@ -117,7 +143,9 @@ def main():
         step = TrainStep(Net("CleanUMamba", bf.E8).to(dev).train(), autocast_dtype=ac)
         dataset = CleanNoisyPairDataset(root=tmp.name, subset="training", crop_length_sec=args.crop_seconds)
         base = dict(remix=True, shift=S, snr_db=(-5.0, 15.0), gain_db=(-6.0, 3.0))
-        configs = {"P": None, "Q": A.Augment(**base), "R": A.Augment(echo=A.Echo(), **base)}
+        third = "M" if args.band else "R"
+        configs = {"P": None, "Q": A.Augment(**base),
+                   third: A.Augment(band_mask=A.BandMask(), **base) if args.band else A.Augment(echo=A.Echo(), **base)}
         feeders = {tag: BatchFeeder(dataset, B, dev, crop_length=L, seed=0, augment=cfg) for tag, cfg in configs.items()}
 
         def batches(feeder):
@@ -144,7 +172,7 @@ def main():
         assert step.graph_status == "captured", step.graph_status
         windows = []
         for _ in range(args.rounds):
-            for tag in ("P", "Q", "R"):
+            for tag in ("P", "Q", third):
                 torch.cuda.synchronize()
                 t = time.perf_counter()
                 run(tag, args.steps)
@@ -152,7 +180,7 @@ def main():
                 ms = 1e3 * (time.perf_counter() - t) / args.steps
                 windows.append({"mode": tag, "ms_per_step": round(ms, 4)})
                 print(f"{tag}: {ms:.3f} ms/step", flush=True)
-        taps = [int(next(streams["R"]).draws.n_taps.mean()) for _ in range(4)]
+        last = [next(streams[third]).draws for _ in range(4)]
         for f in feeders.values():
             f.close()
         tmp.cleanup()
@@ -161,9 +189,13 @@ def main():
         result.update(workload=f"CleanUMamba-E8 train step, B={B}, {args.crop_seconds:g} s crops, {args.dtype}, one hipGraph",
                       steps_per_window=args.steps, warmup=args.warmup, settle_steps=settle, windows=windows,
                       P_to_P_spread_ms=round(max(p) - min(p), 4), mean_ms={k: round(v, 4) for k, v in mean.items()},
-                      Q_minus_P_ms=round(mean["Q"] - mean["P"], 4), R_minus_P_ms=round(mean["R"] - mean["P"], 4),
-                      Q_minus_P_frac=round(mean["Q"] / mean["P"] - 1, 5), R_minus_P_frac=round(mean["R"] / mean["P"] - 1, 5),
-                      mean_taps_per_row_R=taps)
+                      Q_minus_P_ms=round(mean["Q"] - mean["P"], 4), Q_minus_P_frac=round(mean["Q"] / mean["P"] - 1, 5))
+        result.update({f"{third}_minus_P_ms": round(mean[third] - mean["P"], 4),
+                       f"{third}_minus_P_frac": round(mean[third] / mean["P"] - 1, 5)})
+        if args.band:
+            result.update(M_minus_Q_ms=round(mean["M"] - mean["Q"], 4), band_half_M=[int(d.band_half[0]) for d in last])
+        else:
+            result.update(mean_taps_per_row_R=[int(d.n_taps.mean()) for d in last])
     line = json.dumps(result)
     if args.out:
         os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
