@@ -218,6 +218,11 @@ SIGNATURES = {
     "cum_band_mask_block": (c_i32, []),
     "cum_band_mask_workspace_elems": (c_i64, [c_i32]),
     "cum_band_mask_pairs": (c_i32, [_P, c_i64, _P, c_i64, c_i32, c_i64, _P, _P, _P, c_i64, _P, c_i64, _P]),
+    "cum_reverb_block": (c_i32, []),
+    "cum_reverb_max_taps": (c_i32, []),
+    "cum_reverb_workspace_elems": (c_i64, [c_i32, c_i64]),
+    "cum_reverb_pairs": (c_i32, [_P, c_i64, _P, c_i64, c_i32, c_i64, _P, _P, c_i64, _P, _P, c_i32, _P, _P, c_i64, _P, c_i64,
+                                 _P]),
 }
 
 _lib = None

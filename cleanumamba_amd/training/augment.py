@@ -6,7 +6,7 @@
 
 with the augmentation family of the denoiser lineage CleanUNet comes from: exchange the noises within the batch (remix),
 shift noise against speech, re-draw the SNR and the level, add a synthetic room (echo), remove a mel band from speech and
-noise alike (BandMask).  DESIGN.md 7h.
+noise alike (BandMask), and put the speech into a measured room (Reverb).  DESIGN.md 7h.
 
 Two halves, kept apart:
 
@@ -35,9 +35,20 @@ BandMask is a stage of its own in front of that arithmetic: with a band drawn (`
 (k = -W..W, in f64, h rounded to f32) and everything above reads the filtered rows in place of C and Y.  The filters are
 up to 3 201 taps long: csrc/bandmask.hip (cum_band_mask_pairs) applies them by overlap-save on an in-LDS FFT;
 ``band_mask`` is that stage alone, ``apply`` runs it first when any row has a band.
+
+Reverb is the stage in front of both: row b carries an id ``rir[b]`` into a bank of room impulse responses (``Reverb``:
+measured or simulated, cut at the direct path and at -60 dB of the Schroeder integral, at most 16 384 dense taps, unit
+energy).  With h = taps[rir[b]] of T taps (an id outside the bank: the row is copied),
+
+    Cr[b, t] = sum_{k = 0 .. min(t, T - 1)} h[k] C[b, t - k]      clean = Cr      noisy = (Y - C) + Cr
+
+so the target is the reverberant speech and the noise Y - C stays free of speech.  csrc/reverb.hip (cum_reverb_pairs)
+does it by partitioned overlap-save on the same in-LDS FFT; ``reverb`` is that stage alone, ``apply(..., reverb=...)``
+runs it first when any row has a response.  The order is fixed: assemble -> reverb -> band mask -> the arithmetic above.
 """
 import ctypes
 import math
+import os
 
 import numpy as np
 import torch
@@ -49,6 +60,7 @@ REC_INTS = 8                     # one record per row: the fields below, then ze
 REC_PERM, REC_OFF_CLEAN, REC_OFF_NOISE, REC_N_TAPS, REC_SNR_DB, REC_GAIN, REC_KAPPA = range(7)
 W_MAX = 1600                     # the longest half-width the band-mask kernel takes (csrc/bandmask.hip)
 BAND_INTS = 4                    # one band record per row: W, c_lo (f32 bits), c_hi (f32 bits), 0
+REVERB_INTS = 4                  # one reverb record per row: rir, 0, 0, 0
 
 
 def _range(value, name):
@@ -159,14 +171,119 @@ class BandMask:
         return int(2.0 / float(self.edges[lo])), self.edges[lo], self.edges[hi]
 
 
+def prepare_rir(h, decay_db=60.0, max_taps=None):
+    """One raw response as the kernel gets it, deterministic, in f64: cut in front of the direct path (the first sample
+    of the largest magnitude), cut behind the last sample at which the backward-integrated energy (Schroeder) is still
+    above ``-decay_db`` of the total, capped at ``max_taps``, scaled to unit energy, rounded to float32."""
+    h = np.asarray(h)
+    if h.ndim == 2:
+        h = h[0]                                         # channels first: channel 0
+    if h.ndim != 1 or h.size == 0:
+        raise ValueError(f"Reverb: a response must be a non-empty 1-D (or channels-first 2-D) array; got shape {h.shape}")
+    h = h.astype(np.float64)
+    if not np.isfinite(h).all() or not np.abs(h).max() > 0:
+        raise ValueError("Reverb: a response must be finite and not all zero")
+    h = h[int(np.argmax(np.abs(h))):]
+    tail = np.cumsum((h * h)[::-1])[::-1]                # energy from t to the end
+    h = h[:max(1, int(np.count_nonzero(tail > tail[0] * 10.0 ** (-float(decay_db) / 10.0))))]
+    if max_taps is not None:
+        h = h[:int(max_taps)]
+    return (h / math.sqrt(float((h * h).sum()))).astype(np.float32)
+
+
+class ReverbBank:
+    """A ``Reverb``'s responses on one device as cum_reverb_pairs reads them: ``blob`` (float32, every response on a
+    16-byte boundary), ``table`` (int32 (R, 4): {offset in floats as int64 in ints 0-1, taps, 0}), ``table_host`` (the
+    same as a numpy array, for the library's check before the launch) and ``taps`` (the float32 numpy arrays)."""
+
+    def __init__(self, taps, device):
+        self.taps = taps
+        self.table_host = np.zeros((len(taps), 4), dtype=np.int32)
+        at = 0
+        for r, h in enumerate(taps):
+            self.table_host[r].view(np.int64)[0], self.table_host[r, 2] = at, h.shape[0]
+            at += (h.shape[0] + 3) // 4 * 4
+        blob = np.zeros(at, dtype=np.float32)
+        for r, h in enumerate(taps):
+            o = int(self.table_host[r].view(np.int64)[0])
+            blob[o:o + h.shape[0]] = h
+        self.blob, self.table = torch.from_numpy(blob).to(device), torch.from_numpy(self.table_host).to(device)
+        self.device = self.blob.device
+
+    def __len__(self):
+        return len(self.taps)
+
+
+class Reverb:
+    """A bank of room impulse responses.  ``rirs``: a sequence of 1-D (or channels-first 2-D: channel 0) float arrays, or
+    a directory: every ``*.wav`` below it, sorted by relative path, read whole (util/dataset.py); a file at another rate
+    than ``sample_rate`` or in an encoding the reader does not take is a ValueError naming the file (responses are not
+    resampled).  Every response is prepared once, here (``prepare_rir``: direct path first, cut at ``-decay_db`` of the
+    Schroeder integral, at most ``min(max_taps, T_MAX)`` taps, T_MAX = cum_reverb_max_taps() = 16 384, unit energy,
+    float32); ``taps[r]`` is what the kernel gets.  With probability ``proba`` per row a response is drawn uniformly."""
+
+    def __init__(self, rirs, proba=0.5, sample_rate=16000, decay_db=60.0, max_taps=None):
+        self.proba, self.sample_rate, self.decay_db = float(proba), int(sample_rate), float(decay_db)
+        if not 0 <= self.proba <= 1:
+            raise ValueError("Reverb: proba must lie in [0, 1]")
+        if not (math.isfinite(self.decay_db) and self.decay_db > 0):
+            raise ValueError("Reverb: decay_db must be positive")
+        if max_taps is not None and int(max_taps) < 1:
+            raise ValueError("Reverb: max_taps must be at least 1")
+        self.t_max = int(hip.lib().cum_reverb_max_taps())
+        self.max_taps = min(int(max_taps) if max_taps is not None else self.t_max, self.t_max)
+        if isinstance(rirs, (str, os.PathLike)):
+            rirs = self._read_tree(os.fspath(rirs))
+        rirs = list(rirs)
+        if not rirs:
+            raise ValueError("Reverb: no room impulse response given")
+        self.taps = [prepare_rir(h, self.decay_db, self.max_taps) for h in rirs]
+        self._banks = {}
+
+    def _read_tree(self, root):
+        from ..util.dataset import _read_whole_float
+        names = sorted(os.path.relpath(os.path.join(d, f), root) for d, _, files in os.walk(root) for f in files
+                       if f.lower().endswith(".wav"))
+        out = []
+        for name in names:
+            path = os.path.join(root, name)
+            try:
+                rate, x = _read_whole_float(path)
+            except Exception as exc:      # noqa: BLE001 - whatever the reader raises, with the file's name
+                raise ValueError(f"Reverb: {path} cannot be read: {exc}") from exc
+            if int(rate) != self.sample_rate:
+                raise ValueError(f"Reverb: {path} is at {rate} Hz, not {self.sample_rate} (responses are not resampled)")
+            out.append(x)
+        return out
+
+    def __len__(self):
+        return len(self.taps)
+
+    def bank(self, device):
+        """The ``ReverbBank`` on ``device``, uploaded once and kept."""
+        device = torch.device(device)
+        if device.type == "cuda" and device.index is None:
+            device = torch.device("cuda", torch.cuda.current_device())
+        if device not in self._banks:
+            self._banks[device] = ReverbBank(self.taps, device)
+        return self._banks[device]
+
+    def draw(self, rng):
+        """The response id of one row; -1 with probability 1 - proba."""
+        if not rng.random() < self.proba:
+            return -1
+        return int(rng.integers(0, len(self.taps)))
+
+
 class AugmentDraws:
     """Everything random about one batch of ``nb`` rows of ``length`` samples, as the kernel reads it: int32 ``perm``,
     ``off_clean``, ``off_noise``, ``n_taps`` (nb,) and ``delay`` (nb, K_MAX); float32 ``snr_db`` (NaN: keep), ``gain``,
     ``kappa`` (nb,) and ``tap_gain`` (nb, K_MAX).  ``shift``: the sources are ``length + shift`` long.  The band of every
-    row (default: none): int32 ``band_half`` W (0: no band), float32 ``band_lo`` <= ``band_hi`` in cycles per sample."""
+    row (default: none): int32 ``band_half`` W (0: no band), float32 ``band_lo`` <= ``band_hi`` in cycles per sample.  The
+    room of every row (default: none): int32 ``rir``, an id into a ``Reverb``'s bank; an id outside it (-1) is no room."""
 
     def __init__(self, length, shift, perm, off_clean, off_noise, snr_db, gain, kappa, n_taps, delay, tap_gain,
-                 band_half=None, band_lo=None, band_hi=None):
+                 band_half=None, band_lo=None, band_hi=None, rir=None):
         self.length, self.shift = int(length), int(shift)
         self.perm, self.off_clean, self.off_noise, self.n_taps = (np.ascontiguousarray(v, dtype=np.int32)
                                                                   for v in (perm, off_clean, off_noise, n_taps))
@@ -178,9 +295,11 @@ class AugmentDraws:
         self.band_half = np.ascontiguousarray(zeros if band_half is None else band_half, dtype=np.int32)
         self.band_lo, self.band_hi = (np.ascontiguousarray(zeros if v is None else v, dtype=np.float32)
                                       for v in (band_lo, band_hi))
+        self.rir = np.ascontiguousarray(np.full(nb, -1) if rir is None else rir, dtype=np.int32)
         if self.length < 1 or self.shift < 0 or nb < 1:
             raise ValueError("AugmentDraws: length >= 1, shift >= 0 and at least one row are required")
-        for name in ("off_clean", "off_noise", "n_taps", "snr_db", "gain", "kappa", "band_half", "band_lo", "band_hi"):
+        for name in ("off_clean", "off_noise", "n_taps", "snr_db", "gain", "kappa", "band_half", "band_lo", "band_hi",
+                     "rir"):
             if getattr(self, name).shape != (nb,):
                 raise ValueError(f"AugmentDraws: {name} must have shape ({nb},)")
         if self.delay.shape != self.tap_gain.shape or self.delay.ndim != 2 or self.delay.shape[0] != nb \
@@ -212,10 +331,26 @@ class AugmentDraws:
         """Whether any row has a band to remove (the band-mask stage then runs in front of the rest)."""
         return bool(self.band_half.any())
 
+    @property
+    def reverberant(self):
+        """Whether any row has a room (the reverb stage then runs in front of everything else)."""
+        return bool((self.rir >= 0).any())
+
     def without_band(self):
         """The same draws with no band on any row."""
         return AugmentDraws(self.length, self.shift, self.perm, self.off_clean, self.off_noise, self.snr_db, self.gain,
-                            self.kappa, self.n_taps, self.delay, self.tap_gain)
+                            self.kappa, self.n_taps, self.delay, self.tap_gain, rir=self.rir)
+
+    def without_reverb(self):
+        """The same draws with no room on any row."""
+        return AugmentDraws(self.length, self.shift, self.perm, self.off_clean, self.off_noise, self.snr_db, self.gain,
+                            self.kappa, self.n_taps, self.delay, self.tap_gain, self.band_half, self.band_lo, self.band_hi)
+
+    def pack_reverb(self):
+        """The rooms as one int32 array: nb records {rir, 0, 0, 0}."""
+        out = np.zeros((self.batch, REVERB_INTS), dtype=np.int32)
+        out[:, 0] = self.rir
+        return out.reshape(-1)
 
     def pack_band(self):
         """The bands as one int32 array: nb records {W, c_lo (its bits), c_hi (its bits), 0}."""
@@ -255,8 +390,13 @@ def band_ints(nb):
     return BAND_INTS * nb
 
 
+def reverb_ints(nb):
+    """int32 entries of the packed rooms of nb rows."""
+    return REVERB_INTS * nb
+
+
 class Augment:
-    """``Augment(remix=False, shift=0, snr_db=None, gain_db=None, echo=None, band_mask=None)``
+    """``Augment(remix=False, shift=0, snr_db=None, gain_db=None, echo=None, band_mask=None, reverb=None)``
 
     remix: every row gets the noise of a row drawn by one uniform permutation of the batch.
     shift: speech and noise each start at their own uniform offset in [0, shift] of crops ``shift`` samples longer.
@@ -264,9 +404,10 @@ class Augment:
     gain_db: (lo, hi) -- both signals are scaled by 10^(g / 20), g uniform in the range -- or None.
     echo: ``Echo(...)`` or None.
     band_mask: ``BandMask(...)`` or None: one band per batch is removed from speech and noise before everything else.
+    reverb: ``Reverb(...)`` or None: a row's speech is convolved with a room impulse response, before the band mask.
     A config with every transform off is ``inactive`` and is treated by its users exactly as no augmentation."""
 
-    def __init__(self, remix=False, shift=0, snr_db=None, gain_db=None, echo=None, band_mask=None):
+    def __init__(self, remix=False, shift=0, snr_db=None, gain_db=None, echo=None, band_mask=None, reverb=None):
         self.remix, self.shift = bool(remix), int(shift)
         self.snr_db, self.gain_db = _range(snr_db, "snr_db"), _range(gain_db, "gain_db")
         if self.shift < 0:
@@ -275,12 +416,14 @@ class Augment:
             raise ValueError("Augment: echo must be an Echo or None")
         if band_mask is not None and not isinstance(band_mask, BandMask):
             raise ValueError("Augment: band_mask must be a BandMask or None")
-        self.echo, self.band_mask = echo, band_mask
+        if reverb is not None and not isinstance(reverb, Reverb):
+            raise ValueError("Augment: reverb must be a Reverb or None")
+        self.echo, self.band_mask, self.reverb = echo, band_mask, reverb
 
     @property
     def active(self):
         return self.remix or self.shift > 0 or self.snr_db is not None or self.gain_db is not None \
-            or self.echo is not None or self.band_mask is not None
+            or self.echo is not None or self.band_mask is not None or self.reverb is not None
 
     @property
     def max_taps(self):
@@ -289,8 +432,9 @@ class Augment:
 
     def draw(self, rng, nb, length):
         """The draws of one batch from ``rng`` (a numpy Generator), in this order: the permutation; nb clean offsets;
-        nb noise offsets; nb SNRs; nb gains; then row by row the echo (Echo.draw); last the
-        batch's one band (BandMask.draw), copied into every row.  A transform that is off draws nothing."""
+        nb noise offsets; nb SNRs; nb gains; then row by row the echo (Echo.draw); then the
+        batch's one band (BandMask.draw), copied into every row; last, row by row, the room (Reverb.draw).  A transform
+        that is off draws nothing."""
         nb, length = int(nb), int(length)
         perm = rng.permutation(nb) if self.remix else np.arange(nb)
         if self.shift > 0:
@@ -312,8 +456,9 @@ class Augment:
         band = ()
         if self.band_mask is not None:
             band = [np.full(nb, v) for v in self.band_mask.draw(rng)]
+        rir = [self.reverb.draw(rng) for _ in range(nb)] if self.reverb is not None else None
         return AugmentDraws(length, self.shift, perm, off_clean, off_noise, snr, gain, kappa, n_taps, delay, tap_gain,
-                            *band)
+                            *band, rir=rir)
 
 
 # ---------------------------------------------------------------------------------------------------------------- apply
@@ -430,16 +575,90 @@ def band_mask(clean_src, noisy_src, draws, clean_out=None, noisy_out=None):
     return clean_out, noisy_out
 
 
-def apply(clean_src, noisy_src, draws, clean_out=None, noisy_out=None):
+def reverb_workspace_for(nb, n, device):
+    """The twiddle table's and the spectra's room for a batch of nb rows of n samples (8-byte aligned: a fresh tensor)."""
+    return torch.empty(hip.lib().cum_reverb_workspace_elems(nb, n), dtype=torch.float32, device=device)
+
+
+def launch_reverb(clean_src, cs, noisy_src, ys, nb, n, recs, bank, workspace, clean, co, noisy, no):
+    """cum_reverb_pairs on the current stream.  recs: the device int32 tensor of ``AugmentDraws.pack_reverb()``; bank: the
+    ``ReverbBank`` of the tensors' device; workspace: a device tensor of cum_reverb_workspace_elems floats."""
+    hip.check(hip.lib().cum_reverb_pairs(hip.ptr(clean_src), cs, hip.ptr(noisy_src), ys, nb, n, hip.ptr(recs),
+                                         hip.ptr(bank.blob), bank.blob.numel(),
+                                         ctypes.c_void_p(bank.table_host.ctypes.data), hip.ptr(bank.table), len(bank),
+                                         hip.ptr(workspace), hip.ptr(clean), co, hip.ptr(noisy), no, hip.stream_ptr()))
+
+
+def reverb(clean_src, noisy_src, draws, bank, clean_out=None, noisy_out=None):
+    """The reverb stage alone: the sources, float32 (B, n) or (B, 1, n) with n = draws.length + draws.shift; row b with
+    h = bank.taps[draws.rir[b]] gives clean = h * C (causal, n samples) and noisy = (Y - C) + clean into clean_out,
+    noisy_out of the same shape (made here if not given; on a GPU they start on a 16-byte boundary and must not overlap
+    the sources); a row whose id is outside the bank is copied.  ``bank``: ``Reverb.bank(device)``.  Device tensors go
+    through cum_reverb_pairs on the current stream; CPU tensors through a float32 direct convolution with the same
+    float32 taps."""
+    nb, n = draws.batch, draws.length + draws.shift
+    dev = clean_src.device
+    cs, three = _rows(clean_src, "clean_src", nb, n)
+    ys, _ = _rows(noisy_src, "noisy_src", nb, n)
+    if not isinstance(bank, ReverbBank):
+        raise ValueError("augment.reverb: bank must be a ReverbBank (Reverb.bank(device))")
+    if clean_out is None:
+        clean_out = torch.empty((nb, 1, n) if three else (nb, n), dtype=torch.float32, device=dev)
+    if noisy_out is None:
+        noisy_out = torch.empty((nb, 1, n) if three else (nb, n), dtype=torch.float32, device=dev)
+    co, _ = _rows(clean_out, "clean_out", nb, n)
+    no, _ = _rows(noisy_out, "noisy_out", nb, n)
+    if not (noisy_src.device == clean_out.device == noisy_out.device == dev):
+        raise ValueError("augment.reverb: all tensors must be on one device")
+    spans = [_span(clean_src, cs, nb, n), _span(noisy_src, ys, nb, n)]
+    outs = [_span(clean_out, co, nb, n), _span(noisy_out, no, nb, n)]
+    if any(o[0] < s[1] and s[0] < o[1] for o in outs for s in spans) or (outs[0][0] < outs[1][1] and outs[1][0] < outs[0][1]):
+        raise ValueError("augment.reverb: the outputs must not overlap the sources or each other")
+    if dev.type == "cpu":
+        C, Y = torch.as_strided(clean_src, (nb, n), (cs, 1)), torch.as_strided(noisy_src, (nb, n), (ys, 1))
+        out_c, out_y = torch.as_strided(clean_out, (nb, n), (co, 1)), torch.as_strided(noisy_out, (nb, n), (no, 1))
+        for b in range(nb):
+            r = int(draws.rir[b])
+            if not 0 <= r < len(bank):
+                out_c[b], out_y[b] = C[b], Y[b]
+                continue
+            h = torch.from_numpy(bank.taps[r][:n].copy())          # (taps past n never meet a sample)
+            T = h.shape[0]
+            x = torch.nn.functional.pad(C[b].reshape(1, 1, n), (T - 1, 0))
+            cr = torch.nn.functional.conv1d(x, h.flip(0).reshape(1, 1, T)).reshape(n)
+            out_y[b] = (Y[b] - C[b]) + cr
+            out_c[b] = cr
+        return clean_out, noisy_out
+    hip.require_gpu(clean_src, noisy_src, clean_out, noisy_out)
+    if bank.device != dev:
+        raise ValueError(f"augment.reverb: the bank is on {bank.device}, the tensors on {dev}")
+    with torch.cuda.device(dev):
+        recs = torch.from_numpy(draws.pack_reverb()).to(dev)
+        launch_reverb(clean_src, cs, noisy_src, ys, nb, n, recs, bank, reverb_workspace_for(nb, n, dev), clean_out, co,
+                      noisy_out, no)
+    return clean_out, noisy_out
+
+
+_reverb_stage = reverb           # (``apply`` has a parameter of the stage's name)
+
+
+def apply(clean_src, noisy_src, draws, clean_out=None, noisy_out=None, reverb=None):
     """(clean', noisy') of the module's docstring.  clean_src, noisy_src: float32 (B, L + S) or (B, 1, L + S) tensors on
     one device, unit stride along time, L = draws.length, S = draws.shift; clean_out, noisy_out: (B, L) or (B, 1, L), made
     here (in the sources' form) if not given; on a GPU they start on a 16-byte boundary and must not overlap the sources.
     Device tensors go through cum_augment_pairs on the current stream, CPU tensors through torch on the host.  When any
-    row has a band, the sources first pass through ``band_mask`` into scratch allocated here."""
+    row has a band, the sources first pass through ``band_mask`` into scratch allocated here; when any row has a room
+    (``draws.reverberant``), they pass through the ``reverb`` stage before that, with the bank of ``reverb`` (the
+    ``Reverb`` the ids were drawn from; without it such draws are a ValueError)."""
     nb, L, n = draws.batch, draws.length, draws.length + draws.shift
     dev = clean_src.device
     cs, three = _rows(clean_src, "clean_src", nb, n)
     ys, _ = _rows(noisy_src, "noisy_src", nb, n)
+    if draws.reverberant:
+        if not isinstance(reverb, Reverb):
+            raise ValueError("augment.apply: the draws have rooms (rir >= 0): pass reverb=, the Reverb they were drawn from")
+        clean_src, noisy_src = _reverb_stage(clean_src, noisy_src, draws, reverb.bank(dev))
+        cs, ys = (t.stride(0) if nb > 1 else n for t in (clean_src, noisy_src))
     if draws.banded:
         clean_src, noisy_src = band_mask(clean_src, noisy_src, draws)
         cs, ys = (t.stride(0) if nb > 1 else n for t in (clean_src, noisy_src))

@@ -37,7 +37,10 @@ the plan crops ``shift`` samples more, the batch's draws -- from a generator of 
 -- ride in the slot's tail in the same upload, the assembling kernel writes the longer crops into float scratch the
 feeder owns, and cum_augment_pairs (csrc/augment.hip) writes the batch into the step's inputs.  With a ``band_mask`` in
 the config the band records follow the draw table in the same upload, and cum_band_mask_pairs (csrc/bandmask.hip) runs
-between the two, from that scratch into a second pair the block owns.  Without ``augment`` nothing here changes.
+between the two, from that scratch into a second pair the block owns.  With a ``reverb`` in the config the room records
+follow the band records (or the draw table), still in the one upload; the bank of responses goes to the device once, at
+construction, in uploads of its own; and cum_reverb_pairs (csrc/reverb.hip) runs first: assemble -> A, reverb A -> B,
+band B -> A, augment A -> the step's inputs (two scratch pairs, never a third).  Without ``augment`` nothing here changes.
 
 ``device="cpu"`` keeps the same pipeline without pinning or streams and does the kernel's arithmetic with torch on the
 host, so the loop runs anywhere -- a rated feeder too, as long as every pair is at the model rate: there is no CPU
@@ -66,14 +69,16 @@ def _round_up(n, m):
 class _Slot:
     """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths -- in a rated feeder by
     ``batch`` records of 16 int32 -- and, in an augmenting feeder, by ``aug_ints`` int32 of draw table (with a band mask:
-    the band records behind it), as one int16 tensor so that it moves in one copy."""
+    the band records behind it, with a reverb: the room records behind those), as one int16 tensor so that it moves in one
+    copy."""
 
     def __init__(self, batch, pitch, device, pin, tail_ints=1, aug_ints=0):
         self.batch, self.pitch = batch, pitch
         self._aug = 2 * batch * pitch + 2 * tail_ints * batch       # an augmenting feeder's draw table starts here
         self.flat = torch.zeros(self._aug + 2 * aug_ints, dtype=torch.int16, device=device, pin_memory=pin)
         self.scratch = self.workspace = None     # device blocks of an augmenting feeder: the L + S float crops, tile sums
-        self.band_scratch = self.band_workspace = None       # ... with a band mask: the filtered crops, the spectra
+        self.band_scratch = self.band_workspace = None       # ... with a band mask or a reverb: the second pair; the spectra
+        self.reverb_workspace = None                         # ... with a reverb: its spectra
         self.seq = -1                # the batch this block holds
         self.uploaded = None         # event after the upload (device blocks on a GPU)
         self.released = []           # events after the assembling kernels that read this block
@@ -90,7 +95,8 @@ class _Slot:
         return self.flat[self._aug:self._aug + 2 * ints].view(torch.int32)
 
     def band_table(self, at, ints):
-        """``ints`` int32 of band records (AugmentDraws.pack_band) behind a draw table of ``at`` int32."""
+        """``ints`` int32 of band records (AugmentDraws.pack_band) or room records (pack_reverb) that start ``at`` int32
+        behind the start of the draw table."""
         return self.flat[self._aug + 2 * at:self._aug + 2 * (at + ints)].view(torch.int32)
 
     def records(self):
@@ -101,11 +107,13 @@ class _Slot:
 class _Pending:
     """A batch on its way through the staging slots."""
 
-    def __init__(self, seq, epoch, entries, windows=None, records=None, draws=None, table=None, band=None):
+    def __init__(self, seq, epoch, entries, windows=None, records=None, draws=None, table=None, band=None,
+                 rooms=None):
         self.seq, self.epoch, self.entries = seq, epoch, entries
         self.windows, self.records = windows, records        # a rated feeder's: [(m0, M, rate)], (nb, 16) int32 on the host
         self.draws, self.table = draws, table                # an augmenting feeder's: AugmentDraws, its packed int32 table
         self.band = band                                     # ... with a band mask: its packed band records
+        self.rooms = rooms                                   # ... with a reverb: its packed room records
         self.todo = len(entries)     # rows not read yet
         self.error = None
 
@@ -163,7 +171,7 @@ class PcmBatch:
                 out = torch.as_strided(t, (nb, length), (sb, 1))
                 out.copy_(torch.gather(src, 1, idx).to(torch.float32) * PCM_SCALE)
             if self.draws is not None:
-                aug.apply(clean, noisy, self.draws, out_clean, out_noisy)
+                aug.apply(clean, noisy, self.draws, out_clean, out_noisy, reverb=self._feeder.augment.reverb)
             return out_clean, out_noisy
         with torch.cuda.device(self.device):
             stream = torch.cuda.current_stream()
@@ -180,9 +188,16 @@ class PcmBatch:
                     hip.ptr(slot.flat), slot.pitch, hip.ptr(self._records), hip.ptr(slot.records()), nb,
                     *self._feeder._rs.args(), length, hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
                     ctypes.c_void_p(stream.cuda_stream)))
-            if self.draws is not None and self._feeder._band_at is not None:     # scratch -> the block's second pair
+            other = slot.band_scratch        # the stages ping-pong between the block's two pairs
+            if self.draws is not None and self._feeder._reverb_at is not None:
                 src = (clean, strides[0], noisy, strides[1])
-                clean, noisy = slot.band_scratch
+                (clean, noisy), other = other, (clean, noisy)
+                strides = [clean.stride(0), noisy.stride(0)]
+                aug.launch_reverb(*src, nb, length, slot.band_table(self._feeder._reverb_at, aug.reverb_ints(nb)),
+                                  self._feeder._bank, slot.reverb_workspace, clean, strides[0], noisy, strides[1])
+            if self.draws is not None and self._feeder._band_at is not None:
+                src = (clean, strides[0], noisy, strides[1])
+                (clean, noisy), other = other, (clean, noisy)
                 strides = [clean.stride(0), noisy.stride(0)]
                 aug.launch_band(*src, nb, length, slot.band_table(self._feeder._band_at, aug.band_ints(nb)),
                                 slot.band_workspace, clean, strides[0], noisy, strides[1])
@@ -228,7 +243,10 @@ class BatchFeeder:
       batch's ``draws``; they travel in the slot's tail, in the same one upload.  With ``shift = S > 0`` the plan draws
       crops of ``crop_length + S`` (model-rate) samples; otherwise the plan is the one without augmentation.  A config
       with every transform off is taken as None.  With ``band_mask`` the band records ride behind the draw table and
-      every batch takes one more launch pair (csrc/bandmask.hip) between the assembling kernel and the augmenting one."""
+      every batch takes one more launch pair (csrc/bandmask.hip) between the assembling kernel and the augmenting one.
+      With ``reverb`` the room records ride behind those, the bank of responses is uploaded here, once, and every batch
+      takes three more launches (csrc/reverb.hip) right behind the assembling kernel; every device block owns the
+      stage's workspace (48 MB at the E8 batch)."""
 
     def __init__(self, dataset, batch_size, device, crop_length=None, shuffle=True, seed=0, drop_last=True, depth=2,
                  workers=4, rank=0, world=1, timeout_s=60, sample_rate=None, augment=None):
@@ -271,6 +289,11 @@ class BatchFeeder:
         self._band_at = None                    # with a band mask: where its records start, in int32 behind the draw table
         if self.augment is not None and self.augment.band_mask is not None:
             self._band_at, table = table, table + aug.band_ints(self.batch_size)
+        self._reverb_at = self._bank = None     # with a reverb: where its records start, likewise; the bank on the device
+        if self.augment is not None and self.augment.reverb is not None:
+            self._reverb_at, table = table, table + aug.reverb_ints(self.batch_size)
+            if gpu:
+                self._bank = self.augment.reverb.bank(self.device)
         self._stage = [_Slot(self.batch_size, self.pitch, "cpu", gpu, tail, table) for _ in range(self.depth)]
         self._stage_np = [s.flat.numpy() for s in self._stage]
         # one device block more than staging slots: batch k + 1 is uploaded while k and the depth - 1 before it are live
@@ -281,10 +304,13 @@ class BatchFeeder:
                                                   device=self.device)[:, :self._plan_length] for _ in range(2))
                 if self.augment.snr_db is not None:
                     block.workspace = aug.workspace_for(self.batch_size, self.crop_length, self.device)
-                if self._band_at is not None:
+                if self._band_at is not None or self._reverb_at is not None:
                     block.band_scratch = tuple(torch.empty(self.batch_size, t.stride(0), dtype=torch.float32,
                                                            device=self.device)[:, :self._plan_length] for t in block.scratch)
+                if self._band_at is not None:
                     block.band_workspace = aug.band_workspace_for(self.batch_size, self.device)
+                if self._reverb_at is not None:
+                    block.reverb_workspace = aug.reverb_workspace_for(self.batch_size, self._plan_length, self.device)
         self._stream = torch.cuda.Stream(self.device) if gpu else None
 
         self._cv = threading.Condition()
@@ -435,6 +461,8 @@ class BatchFeeder:
                     pend.table = torch.from_numpy(pend.draws.pack(self._aug_k))
                     if self._band_at is not None:
                         pend.band = torch.from_numpy(pend.draws.pack_band())
+                    if self._reverb_at is not None:
+                        pend.rooms = torch.from_numpy(pend.draws.pack_reverb())
             except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next()
                 self._failure = exc
                 self._cv.notify_all()
@@ -499,6 +527,8 @@ class BatchFeeder:
             stage.aug_table(pend.table.numel()).copy_(pend.table)
         if pend.band is not None:
             stage.band_table(self._band_at, pend.band.numel()).copy_(pend.band)
+        if pend.rooms is not None:
+            stage.band_table(self._reverb_at, pend.rooms.numel()).copy_(pend.rooms)
         if self._stream is None:
             dev.flat.copy_(stage.flat)
         else:

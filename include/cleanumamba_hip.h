@@ -1008,6 +1008,44 @@ int cum_band_mask_pairs(const float *clean_src, int64_t clean_src_sb, const floa
                         int32_t batch, int64_t n, const int32_t *recs, float *workspace, float *clean, int64_t clean_sb,
                         float *noisy, int64_t noisy_sb, void *stream);
 
+/* ---- room impulse responses (csrc/reverb.hip; training/augment.py) -----------------------------------
+ * cum_reverb_pairs <- the same hook of the train loop, src/training/train.py:262-265 (`noise, clean_audio =
+ *   augment((noise, clean_audio))`): the speech of a row convolved with a measured or simulated room response, as the
+ *   DNS synthesiser does before it adds the noise; the stage in front of cum_band_mask_pairs and cum_augment_pairs.
+ *   clean_src / noisy_src: f32 rows of n samples, clean_src_sb / noisy_src_sb apart (C and Y below, zero outside [0, n)).
+ *   recs: device table, 4 int32 per row {rir, 0, 0, 0}: the id of the row's response.
+ *   bank: device blob of bank_floats f32, every response starting on a 16-byte boundary, h[0] the direct path.
+ *   rirs: device table of n_rirs records of 4 int32 {offset into the bank in floats (int64 in ints 0-1), taps, 0};
+ *   rirs_host: the same in host memory, checked before the launch.
+ *   A row with rir outside [0, n_rirs) is copied bit for bit.  Otherwise, h = bank[rir] of T taps, t in [0, n):
+ *     Cr[t] = sum_{k = 0 .. min(t, T - 1)} h[k] C[b][t - k]
+ *     clean[b clean_sb + t] = Cr[t]
+ *     noisy[b noisy_sb + t] = (Y[b][t] - C[b][t]) + Cr[t]          (f32: one subtraction, then one addition)
+ *   by uniformly partitioned overlap-save on an in-LDS FFT of N = cum_reverb_block() points: partitions of the response
+ *   and output blocks are N / 2 long, the spectra of block m - k and partition k are multiplied and added in ascending k
+ *   as one fma chain, one inverse transform per block.  The target is the reverberant speech and the noise Y - C stays
+ *   free of speech.  The kernel reads the device table again and does not trust it: an offset outside the bank makes
+ *   the row a copy, taps are clamped into [1, cum_reverb_max_taps()] and to what the bank holds behind the offset, so a
+ *   bad device table never indexes outside the bank.
+ *   workspace: cum_reverb_workspace_elems(batch, n) floats, 8-byte aligned (the twiddle table, the spectra of every
+ *   row's partitions and input blocks; written by the first two of the three launches, read by the last two).  No
+ *   atomics: two runs give the same bits, and a row's result depends on its own record and samples only.  Nothing
+ *   outside [row, row + n) is read or written.  The outputs must not overlap the sources (the caller's check).  Nothing
+ *   is allocated, read back or waited for.
+ *   CUM_EINVAL before any launch: batch outside [1, 32767], n < 1, a stride below n, a null pointer, clean or noisy off
+ *   a 16-byte boundary, workspace off an 8-byte one, any other pointer off a 4-byte one, n_rirs or bank_floats below 1,
+ *   a response in rirs_host with taps outside [1, cum_reverb_max_taps()], with an offset that is negative or not a
+ *   multiple of 4 floats, or whose span leaves the bank.
+ * cum_reverb_block: N, the FFT length; partitions and output blocks are N / 2 long.
+ * cum_reverb_max_taps: T_MAX = 16384: 1.02 s at 16 kHz, 8 partitions at N = 4096. */
+int32_t cum_reverb_block(void);
+int32_t cum_reverb_max_taps(void);
+int64_t cum_reverb_workspace_elems(int32_t batch, int64_t n);
+int cum_reverb_pairs(const float *clean_src, int64_t clean_src_sb, const float *noisy_src, int64_t noisy_src_sb,
+                     int32_t batch, int64_t n, const int32_t *recs, const float *bank, int64_t bank_floats,
+                     const int32_t *rirs_host, const int32_t *rirs, int32_t n_rirs, float *workspace, float *clean,
+                     int64_t clean_sb, float *noisy, int64_t noisy_sb, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

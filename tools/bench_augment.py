@@ -23,6 +23,16 @@ With ``--band`` the same two measurements for the band-mask stage (csrc/bandmask
           re-reads 2 W / V of n, n written; against the time, the fraction of the HBM rate.
   fed     P and Q as above and M: Q plus the default ``BandMask``.
 
+With ``--reverb`` the same two measurements for the reverb stage (csrc/reverb.hip) instead:
+
+  alone   cum_reverb_pairs (three launches, the best of three runs of 20) on L + shift samples per row, every row with
+          a response of T = 2048, 8192 and 16 384 taps (K = T / P partitions, P = N / 2), and with no row reverberant
+          (the copy path).  Bytes by the
+          design's own count, per row of n samples: the input blocks read C twice (8 n), their spectra are written (16 n),
+          every output block reads K block spectra and K partition spectra (32 K n; fewer in the row's first K blocks),
+          C and Y are read again and both outputs written (16 n); a copied row moves 16 n.
+  fed     P and Q as above, V: nothing but ``Reverb(proba=1)`` at T = 8192, and W: Q plus that reverb.
+
 The last line is the result as JSON.
 """
 import argparse
@@ -68,8 +78,10 @@ def main():
     ap.add_argument("--dtype", default="f16", choices=["f16", "bf16", "f32"])
     ap.add_argument("--skip-fed", action="store_true", help="only the launches alone")
     ap.add_argument("--band", action="store_true", help="measure the band-mask stage instead of the echo")
+    ap.add_argument("--reverb", action="store_true", help="measure the reverb stage instead of the echo")
     ap.add_argument("--out", default=None, help="also write the JSON result here")
     args = ap.parse_args()
+    assert not (args.band and args.reverb), "--band or --reverb, not both"
 
     assert torch.cuda.is_available(), "bench_augment.py needs a GPU"
     dev = torch.device("cuda", 0)
@@ -81,16 +93,19 @@ def main():
     B, L, S = args.batch, int(args.crop_seconds * bf.RATE), args.shift
 
     # ---- the launches alone
-    def timed(fn, n=20):
+    def timed(fn, n=20, runs=1):
         fn()
         torch.cuda.synchronize()
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(n):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        return a.elapsed_time(b) / n
+        best = float("inf")
+        for _ in range(runs):
+            a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            a.record()
+            for _ in range(n):
+                fn()
+            b.record()
+            torch.cuda.synchronize()
+            best = min(best, a.elapsed_time(b) / n)
+        return best
     g = torch.Generator(device=dev).manual_seed(0)
     C = 0.05 * torch.randn(B, L + S, device=dev, generator=g)
     Y = C + 0.05 * torch.randn(B, L + S, device=dev, generator=g)
@@ -114,7 +129,35 @@ def main():
                           "TB_per_s": round(moved / (ms * 1e-3) / 1e12, 3),
                           "frac_of_hbm_peak": round(moved / (ms * 1e-3) / HBM_PEAK, 3)}
             print(f"alone {tag}: {alone[tag]}", flush=True)
-    for tag, taps, snr in (() if args.band else
+    def rooms(T, proba=1.0):
+        """Four synthetic responses of exactly T taps: decaying Gaussian noise, the direct path first."""
+        raw = []
+        for i in range(4):
+            h = np.random.default_rng(900 + i).standard_normal(T) * 10.0 ** (-3.0 * np.arange(T) / T)
+            h[0] = 1.5 * max(1.0, np.abs(h).max())
+            raw.append(h)
+        rv = A.Reverb(raw, proba=proba, decay_db=400.0)          # (every tap stays)
+        assert all(h.shape[0] == T for h in rv.taps)
+        return rv
+    if args.reverb:
+        n, N = L + S, hip.lib().cum_reverb_block()
+        out_c, out_y = torch.empty(B, n, device=dev), torch.empty(B, n, device=dev)
+        rev_work = A.reverb_workspace_for(B, n, dev)
+        for tag, T in (("taps_2048", 2048), ("taps_8192", 8192), ("taps_16384", 16384), ("copy", 0)):
+            bank = rooms(T or 2048).bank(dev)
+            ids = np.arange(B) % len(bank) if T else np.full(B, -1)
+            recs = np.zeros((B, A.REVERB_INTS), dtype=np.int32)
+            recs[:, 0] = ids
+            recs = torch.from_numpy(recs.reshape(-1)).to(dev)
+            ms = timed(lambda: A.launch_reverb(C, n, Y, n, B, n, recs, bank, rev_work, out_c, n, out_y, n), runs=3)
+            K = -(-T // (N // 2))
+            moved = int(4 * B * n * (10 + 8 * K)) if T else 16 * B * n
+            alone[tag] = {"ms": round(ms, 4), "launches": 3, "taps": T, "block": N, "partitions": K, "bytes": moved,
+                          "TB_per_s": round(moved / (ms * 1e-3) / 1e12, 3),
+                          "frac_of_hbm_peak": round(moved / (ms * 1e-3) / HBM_PEAK, 3)}
+            print(f"alone {tag}: {alone[tag]}", flush=True)
+        alone["workspace_MB_per_block"] = round(4 * rev_work.numel() / 1e6, 1)
+    for tag, taps, snr in (() if args.band or args.reverb else
                            (("echo_off_snr", 0, True), ("echo_off_keep", 0, False), ("echo_435_taps_snr", 435, True))):
         draws = full_draws(B, L, S, taps, snr)
         k = draws.columns()
@@ -143,9 +186,14 @@ def main():
         step = TrainStep(Net("CleanUMamba", bf.E8).to(dev).train(), autocast_dtype=ac)
         dataset = CleanNoisyPairDataset(root=tmp.name, subset="training", crop_length_sec=args.crop_seconds)
         base = dict(remix=True, shift=S, snr_db=(-5.0, 15.0), gain_db=(-6.0, 3.0))
-        third = "M" if args.band else "R"
-        configs = {"P": None, "Q": A.Augment(**base),
-                   third: A.Augment(band_mask=A.BandMask(), **base) if args.band else A.Augment(echo=A.Echo(), **base)}
+        third = "M" if args.band else "W" if args.reverb else "R"
+        configs = {"P": None, "Q": A.Augment(**base)}
+        if args.reverb:
+            room = rooms(8192)
+            configs["V"] = A.Augment(reverb=room)
+            configs["W"] = A.Augment(reverb=room, **base)
+        else:
+            configs[third] = A.Augment(band_mask=A.BandMask(), **base) if args.band else A.Augment(echo=A.Echo(), **base)
         feeders = {tag: BatchFeeder(dataset, B, dev, crop_length=L, seed=0, augment=cfg) for tag, cfg in configs.items()}
 
         def batches(feeder):
@@ -172,7 +220,7 @@ def main():
         assert step.graph_status == "captured", step.graph_status
         windows = []
         for _ in range(args.rounds):
-            for tag in ("P", "Q", third):
+            for tag in configs:
                 torch.cuda.synchronize()
                 t = time.perf_counter()
                 run(tag, args.steps)
@@ -192,7 +240,10 @@ def main():
                       Q_minus_P_ms=round(mean["Q"] - mean["P"], 4), Q_minus_P_frac=round(mean["Q"] / mean["P"] - 1, 5))
         result.update({f"{third}_minus_P_ms": round(mean[third] - mean["P"], 4),
                        f"{third}_minus_P_frac": round(mean[third] / mean["P"] - 1, 5)})
-        if args.band:
+        if args.reverb:
+            result.update(W_minus_Q_ms=round(mean["W"] - mean["Q"], 4), V_minus_P_ms=round(mean["V"] - mean["P"], 4),
+                          reverberant_rows_W=[int((d.rir >= 0).sum()) for d in last])
+        elif args.band:
             result.update(M_minus_Q_ms=round(mean["M"] - mean["Q"], 4), band_half_M=[int(d.band_half[0]) for d in last])
         else:
             result.update(mean_taps_per_row_R=[int(d.n_taps.mean()) for d in last])
