@@ -135,6 +135,7 @@ SIGNATURES = {
     "cum_stream_hop": (c_i32, [_P, _P, _P, c_i64, c_i32, _P, c_i64, _P, c_i64, c_i32, c_i32, _P]),
     "cum_stream_hop_slots": (c_i32, [_P, _P, _P, c_i64, c_i32, _P, _P, c_i32, _P, c_i64, _P, c_i64, c_i32, _P]),
     "cum_stream_pool_stage": (c_i32, [_P, c_i64, c_i32, _P, _P, c_i32, _P, c_i64, _P, c_i64, _P]),
+    "cum_stream_slots_move": (c_i32, [c_i32, _P, c_i64, c_i32, _P, _P, c_i32, _P, _P, c_i32, _P, _P, c_i32, _P]),
     "cum_fft_plan_create": (c_i32, [c_i32, c_i32, c_i64, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_i64)]),
     "cum_fft_plan_destroy": (c_i32, [_P]),
     "cum_fft_exec": (c_i32, [_P, _P, _P, c_i32, _P, _P]),

@@ -498,14 +498,18 @@ class CleanUMamba(nn.Module):
             raise ValueError("input should be two dimensional: (streams, samples)")
         return streaming.feed_batch(self, noisy_input)
 
-    def stream_pool(self, capacity, model_rate=16000):
+    def stream_pool(self, capacity, model_rate=16000, backend=None):
         """A pool of ``capacity`` stream slots on this model (network/streampool.py): streams that join, feed any number of
-        samples and leave independently, every call's hops in one launch of the one-launch hop.  The pool keeps its own
-        state; ``feed`` / ``feed_batch`` / ``flush`` of the model are not affected.  Models the one-launch hop declines
-        (hopplan.unsupported_reason: Mamba2, above hopplan.MAX_PARAMS, non-f32) raise ValueError.  ``model_rate``: the
-        sample rate the model works at; ``pool.open(rate=...)`` gives a slot that is fed and answers at its own rate."""
+        samples and leave independently.  ``pool.backend`` says what runs the hops: "kernel", every call's hops in one
+        launch of the one-launch hop, wherever that hop runs the model; "layers", the per-layer fused hop on dense batches
+        of the slots that have a hop to run, for models that are only too LARGE for it (above hopplan.MAX_PARAMS, a layer
+        wider than 1 024 channels, a plan that overruns LDS: the E6 / E8 networks).  ``backend`` forces one of the two.
+        The pool keeps its own state; ``feed`` / ``feed_batch`` / ``flush`` of the model are not affected.  Models neither
+        runs (Mamba2, non-f32, other kernel / stride, ``stream_bf16`` on the per-layer backend) raise ValueError.
+        ``model_rate``: the sample rate the model works at; ``pool.open(rate=...)`` gives a slot that is fed and answers
+        at its own rate."""
         from .streampool import StreamPool
-        pool = StreamPool(self, capacity, model_rate)
+        pool = StreamPool(self, capacity, model_rate, backend)
         self.__dict__.setdefault("_stream_pools", weakref.WeakSet()).add(pool)
         return pool
 

@@ -139,34 +139,58 @@ def _stages(op):
     return waves
 
 
-def unsupported_reason(model):
-    """None if the one-launch hop can run this model, else why not."""
+def _obstacles(model):
+    """Every reason the one-launch hop declines ``model``, in the order ``unsupported_reason`` names them: (text, whether
+    it is one of SIZE only -- the model itself is one the per-layer path streams)."""
     E = model.encoder_n_layers
     if model.kernel_size != 4 or model.stride != 2:
-        return "kernel_size / stride other than 4 / 2"
+        yield "kernel_size / stride other than 4 / 2", False
     if E > _MAX_LAYERS or E < 1 or len(model.tsfm_Mamba_layers) > _MAX_BLOCKS:
-        return "too many layers"
+        yield "too many layers", E >= 1
+        if E < 1:
+            return
     if model.encoder[0][0].weight.shape[1] != 1 or model.decoder[E - 1][2].weight.shape[1] != 1:
-        return "more than one input / output channel"
+        yield "more than one input / output channel", False
     if sum(p.numel() for p in model.parameters()) > MAX_PARAMS:
-        return "weights too large to be re-read per stream"
+        yield "weights too large to be re-read per stream", True
     # csrc/hop.hip moves an encoder layer's two carry rows with ONE pass of the 512-thread workgroup, a float4 per thread
     # (`tid < 2 * lq`, lq = ld_out / 4): rows wider than 1 024 floats would be copied in part
     if any(_rup(model.encoder[i][2].weight.shape[0] // 2, 16) > _MAX_LD_OUT for i in range(E)):
-        return "an encoder layer wider than 1 024 channels"
+        yield "an encoder layer wider than 1 024 channels", True
     if any(p.dtype != torch.float32 for p in model.parameters()):
-        return "parameters are not f32"
+        yield "parameters are not f32", False
     for blk in model.tsfm_Mamba_layers:
         m = blk.mixer
         if type(m).__name__ == "Mamba2":
-            return "Mamba2 bottleneck (mamba_v2=True): the one-launch hop covers Mamba1 blocks only"
+            yield "Mamba2 bottleneck (mamba_v2=True): the one-launch hop covers Mamba1 blocks only", False
+            return
         if type(m).__name__ != "Mamba" or not isinstance(blk.norm, nn.LayerNorm) or not blk.norm.elementwise_affine:
-            return "bottleneck block is not LayerNorm + Mamba"
+            yield "bottleneck block is not LayerNorm + Mamba", False
+            return
         if m.activation not in ("silu", "swish") or m.conv1d.weight.shape[-1] > 8:
-            return "Mamba variant outside the kernel"
+            yield "Mamba variant outside the kernel", False
+            return
     if not isinstance(model.norm_f, nn.LayerNorm) or not model.norm_f.elementwise_affine:
-        return "norm_f is not an affine LayerNorm"
-    return None
+        yield "norm_f is not an affine LayerNorm", False
+
+
+def unsupported_reason(model):
+    """None if the one-launch hop can run this model, else why not."""
+    return next((why for why, _ in _obstacles(model)), None)
+
+
+def pool_backend(model):
+    """What a stream pool of ``model`` runs its hops on: "kernel" (the one-launch hop) where nothing stands against it,
+    "layers" (the per-layer hop, slots batched as GEMM rows) where every obstacle is one of size (parameter count, a
+    layer wider than the kernel's carry copy, more layers or blocks than its tables hold).  Any other obstacle raises
+    ValueError with ``unsupported_reason``'s text for it -- looked at on its own: size is checked first there, so a large
+    Mamba2 model answers "too large" to ``unsupported_reason``.  (A plan that overruns LDS shows only when the
+    ``HopPlan`` is built: the pool falls to "layers" on that ValueError.)"""
+    found = list(_obstacles(model))
+    other = [why for why, size_only in found if not size_only]
+    if other:
+        raise ValueError(other[0])
+    return "layers" if found else "kernel"
 
 
 class HopPlan:

@@ -1,4 +1,5 @@
-"""Stream pool: streams that join, feed and leave independently, on the one-launch hop (csrc/hop.hip).
+"""Stream pool: streams that join, feed and leave independently, on the one-launch hop (csrc/hop.hip) or, for models
+too large for it, on the per-layer fused hop (backend "layers", below).
 
 ``feed_batch`` runs S streams in lock-step: they start together, every call gives each the same number of samples, and
 they end together.  A pool has a fixed number of SLOTS that share one packed weight blob and one state block
@@ -19,6 +20,17 @@ number of samples each, and every slot opens and closes on its own.  Per call:
 hops, the decoder drain from its state rows (each at its own ring phase), then the rows are zeroed and the slot id can be
 reused.
 
+Backend "layers" (models ``hopplan.pool_backend`` finds only too large for the one-launch hop; network/layerpool.py): the
+state block is a slot store -- a slot's row holds what one stream of ``streaming._fused_hop`` carries between hops, laid
+out by ``layerpool.segment_table`` -- and step 4 runs in ROUNDS: the slots that have a hop to run, longest first, round r
+those with more than r hops, as one dense batch of the fused hop on scratch sized once for the capacity.  One launch of
+``cum_stream_slots_move`` gathers the call's running slots' rows into the scratch before round 0; where the cohort
+shrinks one launch scatters the rows of the slots that leave, and one behind the last round those of the rest (a
+lock-step call gathers once and scatters once).  The running std is kept per slot with the slot's own frame
+count: the host computes each round's pair (1 / f, 1 - 1 / f), it rides in the call's table, the device evaluates
+``(frame.std + 1e-3) * a + b * std``.  Steps 1 - 3, ``close``, the rated slots and all host bookkeeping are shared; the
+first-frame cohort's state is scattered as it is instead of converted.
+
 A slot can work at its own sample rate (``open(rate=...)``): the host keeps, per slot and direction, what a
 ``StreamResampler`` keeps (``resample.stream_step``), the device the inputs its unfinished outputs still read
 (``rs_hist``), and a call that names such a slot converts all of them in ONE launch in front of step 2 and ONE behind
@@ -35,6 +47,7 @@ from .. import hip
 from ..util import resample as rs
 from . import convstack as cs
 from . import hopplan
+from . import layerpool
 from . import streaming
 
 _REC = 8        # int32 per record of both tables (csrc/hop.hip: kHopItemInts, kStageRecInts)
@@ -68,24 +81,24 @@ def schedule(pending, started, lengths, frame_len, hop):
 class StreamPool:
     """``capacity`` stream slots of one model; see the module docstring.  Made by ``CleanUMamba.stream_pool``.
 
-    Only models the one-launch hop runs can be pooled (``hopplan.unsupported_reason``: Mamba1 bottleneck, at most
-    ``hopplan.MAX_PARAMS`` parameters, f32): every slot re-reads the weight blob per hop, and a slot's whole state lives in
-    one row of the kernel's state block.  Others raise ``ValueError``."""
+    ``backend`` ("kernel", "layers" or None: chosen) is what runs the slots' hops.  "kernel": the one-launch hop, for the
+    models it runs (``hopplan.unsupported_reason``: Mamba1 bottleneck, at most ``hopplan.MAX_PARAMS`` parameters, f32) --
+    every slot re-reads the weight blob per hop, and a slot's whole state lives in one row of the kernel's state block.
+    "layers": the per-layer fused hop on dense batches of slots, for models only too large for the kernel (and for any
+    model the kernel runs, when forced); f32 only.  Models neither runs raise ``ValueError``."""
 
-    def __init__(self, model, capacity, model_rate=16000):
+    def __init__(self, model, capacity, model_rate=16000, backend=None):
         self.model_rate = rs._rate(model_rate, "model_rate")
-        why = hopplan.unsupported_reason(model)
-        if why is not None:
-            raise ValueError(f"stream pool: {why}")
-        if not cs.supported(model):
-            raise ValueError("stream pool: the first frame of a slot runs on the fused per-layer hop, which does not "
-                             "cover this model")
+        if backend not in (None, "kernel", "layers"):
+            raise ValueError('stream pool: backend is None, "kernel" or "layers"')
+        self._forced = backend
         capacity = int(capacity)
+        self.model, self.capacity = model, capacity
+        backend, plan = self._choose()
         if capacity < 1:
             raise ValueError("stream pool: capacity must be >= 1")
-        self.model, self.capacity = model, capacity
         self._rs, self.rs_hist = rs.PlanTable("cpu"), None    # rated slots' plan pairs (DESIGN.md 7g; _adopt moves them)
-        self._adopt(hopplan.HopPlan(model))
+        self._adopt(backend, plan)
         self._open = np.zeros(capacity, dtype=bool)
         self._pend = np.zeros(capacity, dtype=np.int64)       # samples in hist[slot]
         self._frames = np.zeros(capacity, dtype=np.int64)     # frames run (the first one included)
@@ -95,6 +108,33 @@ class StreamPool:
         self._rs_parity = np.zeros((capacity, 2), dtype=np.int64)   # ... the row of rs_hist that holds the history
         self._fed = np.zeros(capacity, dtype=np.int64)        # samples a rated slot was fed / has returned, at its rate
         self._given = np.zeros(capacity, dtype=np.int64)
+
+    def _choose(self):
+        """(backend, plan) for the model as it is now: the forced backend, else "kernel" wherever a HopPlan can be built and
+        "layers" where only size stands against one (``hopplan.pool_backend``).  ValueError for every other model."""
+        model = self.model
+        if self._forced == "kernel":
+            why = hopplan.unsupported_reason(model)
+        else:
+            try:
+                backend, why = hopplan.pool_backend(model), None
+            except ValueError as exc:
+                why = str(exc)
+        if why is not None:
+            raise ValueError(f"stream pool: {why}")
+        if not cs.supported(model):
+            raise ValueError("stream pool: the first frame of a slot runs on the fused per-layer hop, which does not "
+                             "cover this model")
+        if self._forced == "kernel":
+            return "kernel", hopplan.HopPlan(model)
+        if self._forced is None and backend == "kernel":
+            try:
+                return "kernel", hopplan.HopPlan(model)
+            except ValueError:                      # e.g. the LDS budget: an obstacle of size
+                pass
+        if streaming.switch(model, "stream_bf16"):
+            raise ValueError("stream pool: the per-layer backend is f32 only (stream_bf16 is set on the model)")
+        return "layers", layerpool.LayerPlan(model)
 
     # ------------------------------------------------------------------ slots
     @property
@@ -169,24 +209,28 @@ class StreamPool:
         self._fed[:], self._given[:] = 0, 0
 
     def relayout(self):
-        """The model's widths changed (pruning) while no slot is open: take the new plan and size the state blocks to it.
-        A model the one-launch hop no longer runs leaves the pool stale (its next call raises)."""
+        """The model's widths changed (pruning) while no slot is open: take the new plan and size the state blocks to it;
+        the backend is chosen again unless it was forced.  A model no backend runs any more leaves the pool stale (its
+        next call raises)."""
         if self._open.any():
             raise RuntimeError("stream pool: close the slots before the model's widths change")
         try:
-            plan = hopplan.HopPlan(self.model)
+            backend, plan = self._choose()
         except ValueError:
             self._stale = True
             return
-        self._adopt(plan)
+        self._adopt(backend, plan)
         self.reset()
 
-    def _adopt(self, plan):
+    def _adopt(self, backend, plan):
         """Take ``plan`` (of the model's current weights) and size zeroed state blocks to it."""
-        self.plan, self._wv, self._stale = plan, streaming.weights_version(self.model), False
+        self.backend, self.plan, self._wv, self._stale = backend, plan, streaming.weights_version(self.model), False
         self.hop, self.frame_len, self.device = plan.hop, plan.frame_len, plan.device
         self.state = torch.zeros(self.capacity, plan.state_stride, dtype=torch.float32, device=self.device)
         self.hist = torch.zeros(self.capacity, hopplan._rup(self.frame_len - 1, 4), dtype=torch.float32, device=self.device)
+        # the "layers" backend's dense side: scratch in the fused hop's layout, sized once for the capacity
+        self.dense = layerpool.Dense(self.model, plan, self.capacity) if backend == "layers" else None
+        self._ar = torch.arange(self.frame_len, device=self.device) if backend == "layers" else None
         self._rs.to(self.device)            # (the conversion tables follow the model's device)
         self._rs_size_hist()
 
@@ -282,10 +326,16 @@ class StreamPool:
         outs = [torch.zeros(0, dtype=torch.float32, device=self.device) for _ in range(a.size)]
         live = np.flatnonzero(total > 0)
         if live.size:
-            idx = self._index(a[live])
-            st = self.state.index_select(0, idx)
-            std = st[:, 0:1] if self.plan.hdr["normalize"] else None
-            tail = streaming.drain(self.model, self.plan.export_rows(st), std)
+            if self.backend == "layers":
+                # a gather of exactly the closing slots: their per-layer buffers are the drain's input as they are
+                layers, _, std, clears = self.dense.cohort(live.size)
+                layerpool.move(0, self.state, a[live], self.dense.table, clears)
+                tail = streaming.drain(self.model, layers, std)
+            else:
+                idx = self._index(a[live])
+                st = self.state.index_select(0, idx)
+                std = st[:, 0:1] if self.plan.hdr["normalize"] else None
+                tail = streaming.drain(self.model, self.plan.export_rows(st), std)
             for j, i in enumerate(live):
                 outs[i] = torch.cat([heads[i], tail[j].to(heads[i].dtype)])[:int(pend[i])]
         if a.size:
@@ -306,6 +356,15 @@ class StreamPool:
     def _refresh_weights(self):
         wv = streaming.weights_version(self.model)
         if wv == self._wv and not self._stale:
+            return
+        if self.backend == "layers":
+            # no blob: the fused hop re-packs through the model's pack plan; only the shapes must still be the store's
+            plan = layerpool.LayerPlan(self.model)
+            if (plan.shapes, plan.normalize) != (self.plan.shapes, self.plan.normalize):
+                if (self._frames > 0).any() or self._pend.any():
+                    raise RuntimeError("stream pool: the model's shapes changed under live slots")
+                self._adopt("layers", plan)                 # (no slot holds a sample yet: nothing is lost)
+            self._wv, self._stale = wv, False
             return
         try:
             plan = hopplan.HopPlan(self.model)
@@ -426,7 +485,10 @@ class StreamPool:
         hops = np.flatnonzero(sch.n_hops > 0)
         hops = hops[np.argsort(-sch.n_hops[hops], kind="stable")]
         m = hops.size
-        tab = np.zeros((n + m) * _REC + k, dtype=np.int32)
+        rounds = self._rounds(a, sch, hops, row, stage.stride(0), out.stride(0)) if self.backend == "layers" else None
+        ids = (n + m) * _REC                            # the cohort's slot ids, padded to keep the rounds 8-byte aligned
+        rnd = ids + k + (k & 1)
+        tab = np.zeros(rnd + (0 if rounds is None else rounds[1].size), dtype=np.int32)
         srec = tab[:n * _REC].reshape(n, _REC)
         srec[:, 0], srec[:, 1], srec[:, 2], srec[:, 3] = a, pend, lengths, sch.consumed
         srec[:, 4], srec[:, 5] = np.arange(n), row
@@ -434,7 +496,9 @@ class StreamPool:
         hrec[:, 0], hrec[:, 1] = a[hops], sch.n_hops[hops]
         hrec[:, 2], hrec[:, 3] = row[hops], sch.offset[hops]
         hrec[:, 4], hrec[:, 5] = row[hops], sch.offset[hops]
-        tab[(n + m) * _REC:] = a[order[:k]]
+        tab[ids:ids + k] = a[order[:k]]
+        if rounds is not None:
+            tab[rnd:] = rounds[1]
         host = torch.from_numpy(tab).pin_memory()
         dtab = host.to(self.device, non_blocking=True)
         lib = hip.lib()
@@ -444,8 +508,10 @@ class StreamPool:
                                                 hip.ptr(dtab), n, hip.ptr(xs), xs.stride(0), hip.ptr(stage),
                                                 stage.stride(0), hip.stream_ptr()))
         if k:
-            self._first_frames(stage[:k, :F], out[:k, :hop], dtab[(n + m) * _REC:].long())
-        if m:
+            self._first_frames(stage[:k, :F], out[:k, :hop], dtab[ids:ids + k].long(), a[order[:k]])
+        if m and rounds is not None:
+            self._layer_rounds(a[hops], rounds[0], dtab[rnd:], stage, out)
+        elif m:
             p = self.plan
             with torch.cuda.device(self.device):
                 hip.check(lib.cum_stream_hop_slots(
@@ -456,11 +522,67 @@ class StreamPool:
         self._frames[a] += sch.first + sch.n_hops
         return out, row, sch.consumed
 
-    def _first_frames(self, frame, dst, slot_idx):
-        """The first frame of the slots in ``slot_idx`` (k, frame_len) on the per-layer fused path, in a private streaming
-        context, as ``feed_batch`` runs a stream's first frame; their state rows go into the pool's block."""
+    def _first_frames(self, frame, dst, slot_idx, slots):
+        """The first frame of the slots ``slots`` (``slot_idx``: the same on the device) (k, frame_len) on the per-layer
+        fused path, in a private streaming context, as ``feed_batch`` runs a stream's first frame; their state goes into
+        the pool's block: converted rows (the kernel's layout), or one scatter of the buffers as they are ("layers")."""
         state = streaming.StreamState()
         state.params = streaming.new_params(self.model, frame.shape[0])
         dst.copy_(streaming.first_frame(self.model, state, frame, streaming.fused_hop))
+        if self.backend == "layers":
+            std = state.input_std if self.plan.normalize else self.dense.std[:frame.shape[0]]
+            table = layerpool.MoveTable(self.plan, state.layers, state.params.key_value_memory_dict, std)
+            layerpool.move(1, self.state, slots, table)
+            return
         self.plan.import_state(state, into=self.state, at=slot_idx)
 
+    # ------------------------------------------------------------------ the hops of the "layers" backend
+    def _rounds(self, a, sch, hops, row, stage_pitch, out_pitch):
+        """The running slots' hops as rounds of dense batches: round r runs the slots with n_hops > r, the first ``counts[r]``
+        of ``hops`` (longest first).  -> (counts, the rounds' part of the call's table): per round the position of every
+        slot's frame in the staged rows and of its output (int64), and the pair (1 / f, 1 - 1 / f) of its running std,
+        f the frame's number in the slot's own stream (Python floats, as ``streaming.first_frame`` computes them)."""
+        nh = sch.n_hops[hops]
+        counts = [int((nh > r).sum()) for r in range(int(nh[0]) if hops.size else 0)]
+        frames = self._frames[a[hops]] + sch.first[hops]
+        start = sch.offset[hops]
+        parts = []
+        for r, c in enumerate(counts):
+            at = start[:c] + r * self.hop
+            f = (frames[:c] + r + 1).astype(np.float64)
+            coef = np.stack([1.0 / f, 1.0 - 1.0 / f], 1).astype(np.float32)
+            pos = np.concatenate([row[hops[:c]] * stage_pitch + at, row[hops[:c]] * out_pitch + at]).astype(np.int64)
+            parts += [pos.view(np.int32), coef.reshape(-1).view(np.int32)]       # (positions as int64: 2 ints each)
+        return counts, np.concatenate(parts) if parts else np.zeros(0, dtype=np.int32)
+
+    def _layer_rounds(self, slots, counts, dtab, stage, out):
+        """Run the rounds (``_rounds``) of the slots ``slots`` (longest first).  A round whose cohort equals the previous
+        round's runs on the dense state as it stands: rows move only where the cohort changes -- all of them in before
+        round 0, a slot's out behind its last round -- so every row is gathered once and scattered once per call."""
+        model, hop, norm = self.model, self.hop, self.plan.normalize
+        flat_in, flat_out, ar = stage.view(-1), out.view(-1), self._ar
+        cur, o = 0, 0
+        for c in counts:
+            if c != cur:
+                layers, params, std, clears = self.dense.cohort(c)
+                if cur:
+                    # the cohort shrinks to its first c slots, which stay where they are: the others' rows go back, then
+                    # the framing rows of a batch of c are cleared (they lie where stream c was)
+                    layerpool.move(1, self.state, slots[c:cur], self.dense.tail(c))
+                    layerpool.move(0, self.state, slots[:0], self.dense.table, clears)
+                else:
+                    layerpool.move(0, self.state, slots[:c], self.dense.table, clears)
+                cur = c
+            pos = dtab[o:o + 4 * c].view(torch.int64)
+            at_in, at_out = pos[:c], pos[c:]
+            coef = dtab[o + 4 * c:o + 6 * c].view(torch.float32).view(c, 2)
+            o += 6 * c
+            frame = flat_in[at_in[:, None] + ar[None, :]]
+            if norm:
+                std.copy_((frame.std(1, keepdim=True) + 1e-3) * coef[:, 0:1] + coef[:, 1:2] * std)
+                frame = frame / std
+            with cs.small_m_gemms():
+                y = streaming._fused_hop(model, layers, params, frame)[:, :hop]
+            flat_out[at_out[:, None] + ar[None, :hop]] = y * std if norm else y
+        if cur:
+            layerpool.move(1, self.state, slots[:cur], self.dense.table)

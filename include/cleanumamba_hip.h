@@ -496,6 +496,24 @@ int cum_stream_hop_slots(const void *plan, const float *weights, float *state, i
 int cum_stream_pool_stage(float *hist, int64_t hist_stride, int32_t capacity, const int32_t *recs_host,
                           const int32_t *recs, int32_t n_recs, const float *x, int64_t x_stride, float *stage,
                           int64_t stage_stride, void *stream);
+/* Slot-row mover of the per-layer pool (csrc/slotstate.hip; cleanumamba_amd/network/layerpool.py): the state that
+ * CleanUMamba.feed / _denoise_frame of src/network/CleanUMamba.py:358-490 keep for ONE stream in Python attributes lives
+ * per slot in one row of store [capacity][state_stride] f32; a dense batch of the per-layer hop holds stream j at
+ * `dense + j * pitch`.  direction 0 gathers (store -> dense), 1 scatters (dense -> store); ONE launch moves every segment
+ * of every named slot.  slots: n slot ids (stream j of the batch is slot slots[j]).  segs: n_segs records of 4 int64
+ * {dense base pointer (row 1 of a row buffer), dense per-stream pitch in bytes, offset in the store row in bytes, length
+ * in bytes}.  clears (gathers only): n_clears records of 4 int64 {base pointer of a dense row buffer, bytes to clear at
+ * its start, byte offset of the second range, its bytes}: the leading row and the slack rows behind stream n - 1.
+ * Every table is passed twice, as the device copy the kernel reads and as a host copy the entry point checks BEFORE the
+ * launch: a slot outside [0, capacity), a slot named twice, a segment that overruns the store row, segments that overlap
+ * in the store row, null pointers, and sizes that are not multiples of 4 bytes are refused (CUM_EINVAL).  Segments whose
+ * base, pitch and offset are multiples of 16 (and a 16-byte aligned store and row) move as 16-byte vectors, the rest as
+ * dwords; at most 256 segments.  Slots not named and store bytes outside every segment are not touched.  A gather with
+ * n = 0 only clears. */
+int cum_stream_slots_move(int32_t direction, float *store, int64_t state_stride, int32_t capacity,
+                          const int32_t *slots_host, const int32_t *slots, int32_t n, const int64_t *segs_host,
+                          const int64_t *segs, int32_t n_segs, const int64_t *clears_host, const int64_t *clears,
+                          int32_t n_clears, void *stream);
 
 /* ---- first encoder layer, fused (csrc/enc0.hip): Conv1d(1 -> 64, k 4, s 2) + ReLU + Conv1d(64 -> 128, 1x1) + GLU of
  * src/network/CleanUMamba.py:108-113 at channels_input = 1, channels_H = 64 (E6 / E8), 16-bit element types.  The ReLU
