@@ -2,10 +2,14 @@
 //
 //   metrics_frames_kernel   per 30 ms frame (480 samples, hop 120, 16 kHz): segmental SNR (:409 snr), LLR of order-16
 //                           LPC (:336 llr, :380 lpcoeff; f64 throughout), WSS (:139 wss; 1024-point FFT in LDS)
+//                           metrics_frames_kernel<true>: on the same frames, LPC, FFT and bands, the LPC cepstrum distance
+//                           and the frequency-weighted segmental SNR of Hu & Loizou 2008 (tests/metrics_ext_ref.py)
+//   metrics_sums_kernel / metrics_sums_reduce_kernel   per clip: exact int64 sum x^2, sum y^2, sum x y (overall SNR, SI-SDR)
 //   metrics_rank_kernel / metrics_clip_mean_kernel   per clip: mean of the lowest round(0.95 n) frame values (NaN sorts
 //                           last, as np.sort puts it), or the plain mean
 //   stoi_*_kernel           STOI (Taal et al. 2011): polyphase 16 k -> 10 k, silent-frame removal, 512-point STFT in LDS,
-//                           15 one-third-octave bands, 30-frame segments
+//                           15 one-third-octave bands, 30-frame segments; stoi_ecorr_kernel: eSTOI (Jensen & Taal 2016)
+//                           on the same band magnitudes
 // Every sum runs in a fixed order inside one clip's own workgroups: two runs give the same bits, and a clip's result does
 // not depend on the other clips of its batch.  No float atomics.
 #include <math.h>
@@ -73,9 +77,21 @@ struct FrameParams {
   const double *band_w;        // truncated Gaussian weights of every band's support
   const double *tw;            // e^{-2 pi i m / 1024}, m = 0..512
   double *seg_snr, *llr, *wss;
+  double *cep, *fwseg;         // the extended instantiation's outputs
 };
 
-// grid (ceil(max frames / kFpb), clips), 4 waves; each wave owns one frame at a time
+template <bool EXT>
+struct FramePw { typedef float2 T; };                    // bin powers of both signals, f32 (WSS)
+template <>
+struct FramePw<true> { typedef double2 T; };             // bin magnitudes, f64: fwseg subtracts two nearly equal band sums
+
+// limits that keep a NaN (fmin / fmax would drop it)
+__device__ __forceinline__ double limit_keep_nan(double v, double lo, double hi) { return v < lo ? lo : (v > hi ? hi : v); }
+
+// grid (ceil(max frames / kFpb), clips), 4 waves; each wave owns one frame at a time.  EXT = false: segSNR, LLR, WSS.
+// EXT = true: the same staging, autocorrelation, Levinson recursion, FFT and band table, then the LPC cepstrum distance
+// and the frequency-weighted segmental SNR (Hu & Loizou 2008) instead of the quadratic forms and the WSS peak search.
+template <bool EXT>
 __global__ __launch_bounds__(64 * kMetricWaves) void metrics_frames_kernel(const FrameParams p) {
   typedef FusedFft<512, double> F;
   __shared__ __attribute__((aligned(16))) float s_c[kSpanCap];
@@ -83,7 +99,7 @@ __global__ __launch_bounds__(64 * kMetricWaves) void metrics_frames_kernel(const
   __shared__ double s_win[kWin];
   __shared__ __attribute__((aligned(16))) double4 s_buf[kMetricWaves][F::SLOTS];
   __shared__ double2 s_tw[513];
-  __shared__ float2 s_pw[kMetricWaves][512];
+  __shared__ typename FramePw<EXT>::T s_pw[kMetricWaves][512];
   __shared__ double s_R[kMetricWaves][2][kLpc + 1];
   __shared__ double s_A[kMetricWaves][2][kLpc + 1];
   __shared__ double s_E[kMetricWaves][2][kBands];
@@ -151,7 +167,32 @@ __global__ __launch_bounds__(64 * kMetricWaves) void metrics_frames_kernel(const
       for (int j = 0; j < kLpc; ++j) s_A[wave][lane][j + 1] = -a[j];
     }
     F::stage_fence();
-    if (lane == 0) {                                     // A' T(R_clean) A for A = processed, clean
+    if constexpr (EXT) {
+      // cepstrum of 1 / A(z): c_1 = -a_1, c_k = -a_k - (1 / k) sum_{i < k} i c_i a_{k - i}; each lane overwrites its own R row
+      if (lane < 2) {
+        const double *A = s_A[wave][lane];
+        double c[kLpc + 1];
+#pragma unroll
+        for (int k = 1; k <= kLpc; ++k) {
+          double acc = 0.0;
+#pragma unroll
+          for (int i = 1; i < k; ++i) acc += (double)i * c[i] * A[k - i];
+          c[k] = -A[k] - acc / (double)k;
+        }
+#pragma unroll
+        for (int k = 1; k <= kLpc; ++k) s_R[wave][lane][k] = c[k];
+      }
+      F::stage_fence();
+      if (lane == 0) {
+        double d2 = 0.0;
+#pragma unroll
+        for (int k = 1; k <= kLpc; ++k) {
+          const double d = s_R[wave][0][k] - s_R[wave][1][k];
+          d2 += d * d;
+        }
+        p.cep[fo] = limit_keep_nan(4.342944819032518 * sqrt(2.0 * d2), 0.0, 10.0);   // 10 / ln 10
+      }
+    } else if (lane == 0) {                              // A' T(R_clean) A for A = processed, clean
       const double *R = s_R[wave][0];
       double qf[2];
 #pragma unroll
@@ -187,7 +228,18 @@ __global__ __launch_bounds__(64 * kMetricWaves) void metrics_frames_kernel(const
       const int m = j == 0 ? 0 : 512 - j;
       const double4 vj = buf[F::pad(F::pos(j))], vm = buf[F::pad(F::pos(m))];
       const double2 xj = make_double2(vj.x, vj.y), yj = make_double2(vj.z, vj.w), xm = make_double2(vm.x, vm.y), ym = make_double2(vm.z, vm.w);
-      if (j == 0) {
+      if constexpr (EXT) {
+        if (j == 0) {
+          s_pw[wave][0] = make_double2(fabs(xj.x + xj.y), fabs(yj.x + yj.y));
+        } else {
+          const double2 X = packed_bin(xj, xm, s_tw[j]), Y = packed_bin(yj, ym, s_tw[j]);
+          s_pw[wave][j] = make_double2(sqrt(X.x * X.x + X.y * X.y), sqrt(Y.x * Y.x + Y.y * Y.y));
+          if (m != j) {
+            const double2 X2 = packed_bin(xm, xj, s_tw[m]), Y2 = packed_bin(ym, yj, s_tw[m]);
+            s_pw[wave][m] = make_double2(sqrt(X2.x * X2.x + X2.y * X2.y), sqrt(Y2.x * Y2.x + Y2.y * Y2.y));
+          }
+        }
+      } else if (j == 0) {
         const double cx = xj.x + xj.y, cy = yj.x + yj.y;
         s_pw[wave][0] = make_float2((float)(cx * cx), (float)(cy * cy));
       } else {
@@ -200,13 +252,50 @@ __global__ __launch_bounds__(64 * kMetricWaves) void metrics_frames_kernel(const
       }
     }
     F::stage_fence();
+    if constexpr (EXT) {
+      // fwseg: magnitudes normalised to unit sum over bins 0..511, critical-band sums of them, then the band SNRs
+      // weighted by ce^0.2 (lane b: clean band b, lane 32 + b: processed)
+      double sx = 0.0, sy = 0.0;
+      for (int k = lane; k < 512; k += 64) {
+        sx += s_pw[wave][k].x;
+        sy += s_pw[wave][k].y;
+      }
+      sx = wave_sum_f64(sx) + kEpsF64;
+      sy = wave_sum_f64(sy) + kEpsF64;
+      const int b = lane & 31, s = lane >> 5;
+      if (b < kBands) {
+        const int lo = p.band_tab[3 * b], cnt = p.band_tab[3 * b + 1], wo = p.band_tab[3 * b + 2];
+        double e = 0.0;
+        for (int k = 0; k < cnt; ++k) {
+          const double2 mg = s_pw[wave][lo + k];
+          e = fma(p.band_w[wo + k], s ? mg.y / sy : mg.x / sx, e);
+        }
+        s_E[wave][s][b] = e;
+      }
+      F::stage_fence();
+      double num = 0.0, den = 0.0;
+      if (lane < kBands) {
+        const double ce = s_E[wave][0][lane], pe = s_E[wave][1][lane];
+        if (ce > 0.0) {
+          const double W = pow(ce, 0.2), d = ce - pe;
+          const double err = fmax(d * d, kEpsF64);
+          num = W * (10.0 * log10(ce * ce / err));
+          den = W;
+        }
+      }
+      num = wave_sum_f64(num);
+      den = wave_sum_f64(den);
+      if (lane == 0) p.fwseg[fo] = den > 0.0 ? limit_keep_nan(num / den, -10.0, 35.0) : (double)NAN;
+      F::stage_fence();
+      continue;
+    }
     {                                                    // critical-band energies: lane b clean, lane 32 + b processed
       const int b = lane & 31, s = lane >> 5;
       if (b < kBands) {
         const int lo = p.band_tab[3 * b], cnt = p.band_tab[3 * b + 1], wo = p.band_tab[3 * b + 2];
         double e = 0.0;
         for (int k = 0; k < cnt; ++k) {
-          const float2 pw = s_pw[wave][lo + k];
+          const auto pw = s_pw[wave][lo + k];
           e = fma(p.band_w[wo + k], (double)(s ? pw.y : pw.x), e);
         }
         s_E[wave][s][b] = 10.0 * log10(fmax(e, 1e-10));
@@ -300,7 +389,81 @@ __global__ __launch_bounds__(256) void metrics_clip_mean_kernel(const double *__
   if (threadIdx.x == 0) out[blockIdx.x] = s_s[0] / s_n[0];
 }
 
-// ================================================================ STOI (pystoi.stoi, extended=False)
+// ================================================================ exact integer sums (overall SNR, SI-SDR)
+constexpr int kSumChunk = 8192;                          // samples per workgroup: 256 lanes x 4 groups of 8
+
+__device__ __forceinline__ void sums_add(int64_t &xx, int64_t &yy, int64_t &xy, int x, int y) {
+  // one product at a time into int64: (-32768)^2 is 2^30, and two of them already overflow an int32 pair sum
+  xx += (int64_t)(x * x);
+  yy += (int64_t)(y * y);
+  xy += (int64_t)(x * y);
+}
+
+// grid (ceil(max chunks), clips): chunk c of a clip covers the 8-sample groups [a + c kSumChunk, a + (c + 1) kSumChunk) from
+// the 16-byte aligned base a below the clip's start.  A group wholly inside the clip is one 16-byte load per signal;
+// the lead and tail groups read sample by sample, inside the clip only.  part[(frame_off + c) * 3 + {0, 1, 2}].
+__global__ __launch_bounds__(256) void metrics_sums_kernel(const int16_t *__restrict__ clean, const int16_t *__restrict__ proc,
+                                                          const ClipRow *__restrict__ clips, int64_t *__restrict__ part) {
+  __shared__ int64_t s_s[3][256];
+  const ClipRow c = clips[blockIdx.y];
+  if ((int64_t)blockIdx.x >= c.n_frames) return;         // n_frames: this clip's chunk count
+  const int64_t a = c.off & ~(int64_t)7, end = c.off + c.len;
+  int64_t xx = 0, yy = 0, xy = 0;
+#pragma unroll
+  for (int g = 0; g < kSumChunk / (8 * 256); ++g) {
+    const int64_t s = a + (int64_t)blockIdx.x * kSumChunk + 8 * (int64_t)(g * 256 + threadIdx.x);
+    if (s >= end) break;
+    if (s >= c.off && s + 8 <= end) {
+      const int4 u = *reinterpret_cast<const int4 *>(clean + s), v = *reinterpret_cast<const int4 *>(proc + s);
+      const int uw[4] = {u.x, u.y, u.z, u.w}, vw[4] = {v.x, v.y, v.z, v.w};
+#pragma unroll
+      for (int i = 0; i < 4; ++i) {
+        sums_add(xx, yy, xy, (int)(int16_t)(uw[i] & 0xffff), (int)(int16_t)(vw[i] & 0xffff));
+        sums_add(xx, yy, xy, uw[i] >> 16, vw[i] >> 16);
+      }
+    } else {
+      for (int i = 0; i < 8; ++i)
+        if (s + i >= c.off && s + i < end) sums_add(xx, yy, xy, (int)clean[s + i], (int)proc[s + i]);
+    }
+  }
+  s_s[0][threadIdx.x] = xx;
+  s_s[1][threadIdx.x] = yy;
+  s_s[2][threadIdx.x] = xy;
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (threadIdx.x < o) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s_s[k][threadIdx.x] += s_s[k][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) part[(c.frame_off + blockIdx.x) * 3 + threadIdx.x] = s_s[threadIdx.x][0];
+}
+
+// grid (clips): the clip's chunk sums added up, out[clip][3]
+__global__ __launch_bounds__(256) void metrics_sums_reduce_kernel(const ClipRow *__restrict__ clips, const int64_t *__restrict__ part,
+                                                                 int64_t *__restrict__ out) {
+  __shared__ int64_t s_s[3][256];
+  const ClipRow c = clips[blockIdx.x];
+  int64_t v[3] = {0, 0, 0};
+  for (int64_t q = threadIdx.x; q < c.n_frames; q += 256) {
+#pragma unroll
+    for (int k = 0; k < 3; ++k) v[k] += part[(c.frame_off + q) * 3 + k];
+  }
+#pragma unroll
+  for (int k = 0; k < 3; ++k) s_s[k][threadIdx.x] = v[k];
+  __syncthreads();
+  for (int o = 128; o >= 1; o >>= 1) {
+    if (threadIdx.x < o) {
+#pragma unroll
+      for (int k = 0; k < 3; ++k) s_s[k][threadIdx.x] += s_s[k][threadIdx.x + o];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x < 3) out[blockIdx.x * 3 + threadIdx.x] = s_s[threadIdx.x][0];
+}
+
+// ================================================================ STOI (pystoi.stoi; extended: Jensen & Taal 2016)
 constexpr int kStoiFrame = 256, kStoiHop = 128, kStoiBands = 15, kStoiSeg = 30;
 constexpr double kStoiDyn = 40.0, kStoiClip = 5.623413251903491;   // 10^(15 / 20): beta = -15 dB
 
@@ -320,6 +483,7 @@ struct StoiParams {
   double *rs_x, *rs_y, *energy, *comp_x, *comp_y, *tob_x, *tob_y;
   int64_t *kept_src, *kept;
   double *out;
+  double *out_e;              // eSTOI (stoi_ecorr_kernel)
 };
 
 // grid (ceil(max resampled length / 256), clips): y[m] = sum_n x[n] h[(m + pre_remove) down - n up - pre_pad]
@@ -520,6 +684,82 @@ __global__ __launch_bounds__(256) void stoi_corr_kernel(const StoiParams p) {
   if (threadIdx.x == 0) p.out[blockIdx.x] = s_s[0] / (double)pairs;
 }
 
+// grid (clips), one wave per 30-frame segment at a time (wave w takes segments w, w + 4, ...): eSTOI (Jensen & Taal 2016)
+// on the band magnitudes of stoi_tob_kernel.  Both 15 x 30 matrices of a segment: rows (bands) to zero mean and unit
+// norm over the frames, then columns (frames) to zero mean and unit norm over the bands, every norm + eps (pystoi adds
+// eps-sized noise instead); the segment's value is the sum of the products / 30.  Each wave adds its segments in order,
+// the four wave sums are added in order: fixed summation order per clip.
+__global__ __launch_bounds__(64 * kMetricWaves) void stoi_ecorr_kernel(const StoiParams p) {
+  __shared__ double s_m[kMetricWaves][2][kStoiSeg * kStoiBands];
+  __shared__ double s_acc[kMetricWaves];
+  const StoiRow c = p.clips[blockIdx.x];
+  const int64_t nk = p.kept[blockIdx.x], ns = nk > 0 ? nk - 1 : 0;
+  if (ns < kStoiSeg) {                                   // as STOI: not enough frames
+    if (threadIdx.x == 0) p.out_e[blockIdx.x] = 1e-5;
+    return;
+  }
+  typedef FusedFft<256, double> F;                       // (for the wave-scope fence only)
+  const int lane = threadIdx.x & 63, wave = uniform(threadIdx.x >> 6);
+  const int64_t J = ns - kStoiSeg + 1;
+  double *mx = s_m[wave][0], *my = s_m[wave][1];
+  double acc = 0.0;
+  for (int64_t m = wave; m < J; m += kMetricWaves) {
+    const double *X = p.tob_x + (c.tob_off + m) * kStoiBands, *Y = p.tob_y + (c.tob_off + m) * kStoiBands;
+    for (int i = lane; i < kStoiSeg * kStoiBands; i += 64) {   // element (frame t, band b) at t * 15 + b
+      mx[i] = X[i];
+      my[i] = Y[i];
+    }
+    F::stage_fence();
+    {                                                    // rows: lanes 0-14 clean, 16-30 processed
+      const int b = lane & 15, s = lane >> 4;
+      if (b < kStoiBands && s < 2) {
+        double *M = s ? my : mx;
+        double mean = 0.0;
+        for (int t = 0; t < kStoiSeg; ++t) mean += M[t * kStoiBands + b];
+        mean /= kStoiSeg;
+        double nn = 0.0;
+        for (int t = 0; t < kStoiSeg; ++t) {
+          const double v = M[t * kStoiBands + b] - mean;
+          nn = fma(v, v, nn);
+        }
+        const double d = sqrt(nn) + kEpsF64;
+        for (int t = 0; t < kStoiSeg; ++t) M[t * kStoiBands + b] = (M[t * kStoiBands + b] - mean) / d;
+      }
+    }
+    F::stage_fence();
+    {                                                    // columns: lanes 0-29 clean, 32-61 processed
+      const int t = lane & 31, s = lane >> 5;
+      if (t < kStoiSeg) {
+        double *M = (s ? my : mx) + t * kStoiBands;
+        double mean = 0.0;
+        for (int b = 0; b < kStoiBands; ++b) mean += M[b];
+        mean /= kStoiBands;
+        double nn = 0.0;
+        for (int b = 0; b < kStoiBands; ++b) {
+          const double v = M[b] - mean;
+          nn = fma(v, v, nn);
+        }
+        const double d = sqrt(nn) + kEpsF64;
+        for (int b = 0; b < kStoiBands; ++b) M[b] = (M[b] - mean) / d;
+      }
+    }
+    F::stage_fence();
+    double dot = 0.0;
+    if (lane < kStoiSeg)
+      for (int b = 0; b < kStoiBands; ++b) dot = fma(mx[lane * kStoiBands + b], my[lane * kStoiBands + b], dot);
+    dot = wave_sum_f64(dot);
+    acc += dot / kStoiSeg;
+    F::stage_fence();                                    // (the next segment overwrites what other lanes just read)
+  }
+  if (lane == 0) s_acc[wave] = acc;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    double t = 0.0;
+    for (int w = 0; w < kMetricWaves; ++w) t += s_acc[w];
+    p.out_e[blockIdx.x] = t / (double)J;
+  }
+}
+
 }  // namespace cum
 
 using namespace cum;
@@ -601,9 +841,97 @@ extern "C" int cum_metrics_frames(const int16_t *clean, const int16_t *processed
   hipStream_t st = (hipStream_t)stream;
   if (int rc = upload_rows("metrics_frames", workspace, rows.data(), n_clips * sizeof(ClipRow), st)) return rc;
   if (max_nf == 0) return CUM_OK;
-  FrameParams p{clean, processed, n_samples, (const ClipRow *)workspace, window, band_tab, band_w, tw, seg_snr, llr, wss};
-  hipLaunchKernelGGL(metrics_frames_kernel, dim3((unsigned)cdiv64(max_nf, kFpb), (unsigned)n_clips), dim3(64 * kMetricWaves), 0,
-                     st, p);
+  FrameParams p{clean, processed, n_samples, (const ClipRow *)workspace, window, band_tab, band_w, tw, seg_snr, llr, wss,
+                nullptr, nullptr};
+  hipLaunchKernelGGL(metrics_frames_kernel<false>, dim3((unsigned)cdiv64(max_nf, kFpb), (unsigned)n_clips),
+                     dim3(64 * kMetricWaves), 0, st, p);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+// cum_metrics_frames_ext <- Hu & Loizou 2008: the LPC cepstrum distance (Kitawaki et al. 1988) and the frequency-weighted
+// segmental SNR (Tribolet et al. 1978) on the frames, window, LPC, FFT and critical bands of cum_metrics_frames; the
+// definitions are restated in tests/metrics_ext_ref.py
+extern "C" int cum_metrics_frames_ext(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                                      const int64_t *lengths, int64_t n_clips, int32_t rate, const double *window,
+                                      const int32_t *band_tab, const double *band_w, const double *tw, void *workspace,
+                                      int64_t workspace_bytes, double *cep, double *fwseg, int64_t n_frames_total,
+                                      void *stream) {
+  CUM_REQUIRE(rate == 16000, "metrics_frames_ext: the frame metrics run at 16 kHz only");
+  if (int rc = check_clips("metrics_frames_ext", clean, processed, n_samples, offsets, lengths, n_clips, kWin)) return rc;
+  std::vector<ClipRow> rows;
+  int64_t total, max_nf;
+  frame_rows(offsets, lengths, n_clips, rows, total, max_nf);
+  CUM_REQUIRE(total == n_frames_total, "metrics_frames_ext: n_frames_total must be the sum of the clips' frame counts");
+  CUM_REQUIRE(workspace && workspace_bytes >= cum_metrics_workspace_bytes(n_clips, total),
+              "metrics_frames_ext: workspace too small");
+  CUM_REQUIRE(window && band_tab && band_w && tw, "metrics_frames_ext: null table");
+  CUM_REQUIRE(total == 0 || (cep && fwseg), "metrics_frames_ext: null output");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = upload_rows("metrics_frames_ext", workspace, rows.data(), n_clips * sizeof(ClipRow), st)) return rc;
+  if (max_nf == 0) return CUM_OK;
+  FrameParams p{clean, processed, n_samples, (const ClipRow *)workspace, window, band_tab, band_w, tw, nullptr, nullptr,
+                nullptr, cep, fwseg};
+  hipLaunchKernelGGL(metrics_frames_kernel<true>, dim3((unsigned)cdiv64(max_nf, kFpb), (unsigned)n_clips),
+                     dim3(64 * kMetricWaves), 0, st, p);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+// per-clip mean of the frame values that are not NaN (fwsegSNR); NaN where a clip has none.  Same layout, workspace and
+// checks as cum_metrics_clip_reduce.
+extern "C" int cum_metrics_clip_nanmean(const double *values, const int64_t *lengths, int64_t n_clips, void *workspace,
+                                        int64_t workspace_bytes, double *out, void *stream) {
+  CUM_REQUIRE(n_clips > 0 && n_clips <= 65535 && lengths, "metrics_clip_nanmean: bad batch");
+  std::vector<int64_t> offs(n_clips, 0);
+  for (int64_t i = 0; i < n_clips; ++i) CUM_REQUIRE(lengths[i] >= kWin, "metrics_clip_nanmean: clip shorter than one window");
+  std::vector<ClipRow> rows;
+  int64_t total, max_nf;
+  frame_rows(offs.data(), lengths, n_clips, rows, total, max_nf);
+  CUM_REQUIRE(workspace && workspace_bytes >= cum_metrics_workspace_bytes(n_clips, total),
+              "metrics_clip_nanmean: workspace too small");
+  CUM_REQUIRE(out && (total == 0 || values), "metrics_clip_nanmean: null pointer");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = upload_rows("metrics_clip_nanmean", workspace, rows.data(), n_clips * sizeof(ClipRow), st)) return rc;
+  hipLaunchKernelGGL(metrics_clip_mean_kernel, dim3((unsigned)n_clips), dim3(256), 0, st, values, (const int32_t *)nullptr,
+                     (const ClipRow *)workspace, 1, out);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+// cum_metrics_sums: exact Sxx = sum x^2, Syy = sum y^2, Sxy = sum x y of every clip as int64 (out[i][3]), the integers
+// behind the overall SNR and SI-SDR (Le Roux et al. 2019)
+extern "C" int64_t cum_metrics_sums_workspace_bytes(const int64_t *lengths, int64_t n_clips) {
+  if (!lengths || n_clips <= 0) return -1;
+  int64_t chunks = 0;
+  for (int64_t i = 0; i < n_clips; ++i) chunks += cdiv64((lengths[i] > 0 ? lengths[i] : 0) + 7, kSumChunk);
+  return n_clips * (int64_t)sizeof(ClipRow) + chunks * 3 * 8;
+}
+
+extern "C" int cum_metrics_sums(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                                const int64_t *lengths, int64_t n_clips, void *workspace, int64_t workspace_bytes,
+                                int64_t *out, void *stream) {
+  if (int rc = check_clips("metrics_sums", clean, processed, n_samples, offsets, lengths, n_clips, 1)) return rc;
+  std::vector<ClipRow> rows(n_clips);
+  int64_t chunks = 0, max_ch = 0;
+  for (int64_t i = 0; i < n_clips; ++i) {
+    // int64 holds 2^63 / 2^30 = 2^33 full-scale products
+    CUM_REQUIRE(lengths[i] < ((int64_t)1 << 33), "metrics_sums: clip too long for exact int64 sums");
+    const int64_t nch = cdiv64((offsets[i] & 7) + lengths[i], kSumChunk);     // chunks start at the aligned base
+    rows[i] = ClipRow{offsets[i], lengths[i], chunks, nch, 0, 0, 0, 0};
+    chunks += nch;
+    max_ch = nch > max_ch ? nch : max_ch;
+  }
+  CUM_REQUIRE(workspace && workspace_bytes >= cum_metrics_sums_workspace_bytes(lengths, n_clips),
+              "metrics_sums: workspace too small");
+  CUM_REQUIRE(out, "metrics_sums: null output");
+  hipStream_t st = (hipStream_t)stream;
+  if (int rc = upload_rows("metrics_sums", workspace, rows.data(), n_clips * sizeof(ClipRow), st)) return rc;
+  const ClipRow *tab = (const ClipRow *)workspace;
+  int64_t *part = (int64_t *)((char *)workspace + n_clips * sizeof(ClipRow));
+  hipLaunchKernelGGL(metrics_sums_kernel, dim3((unsigned)max_ch, (unsigned)n_clips), dim3(256), 0, st, clean, processed, tab,
+                     part);
+  hipLaunchKernelGGL(metrics_sums_reduce_kernel, dim3((unsigned)n_clips), dim3(256), 0, st, tab, (const int64_t *)part, out);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }
@@ -667,14 +995,15 @@ extern "C" int64_t cum_metrics_stoi_workspace_bytes(const int64_t *lengths, int6
   return L.bytes;
 }
 
-extern "C" int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
-                                const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
-                                const double *window, const double *tw, const int32_t *bands, void *workspace,
-                                int64_t workspace_bytes, double *out, void *stream) {
+// the body of both STOI entries; which: bit 0 STOI -> out, bit 1 eSTOI -> out_e, on one front end
+static int stoi_run(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                    const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
+                    const double *window, const double *tw, const int32_t *bands, void *workspace, int64_t workspace_bytes,
+                    int which, double *out, double *out_e, void *stream) {
   CUM_REQUIRE(rate == 16000 || rate == 10000, "metrics_stoi: rate must be 16000 or 10000 Hz");
   if (int rc = check_clips("metrics_stoi", clean, processed, n_samples, offsets, lengths, n_clips, 1)) return rc;
   CUM_REQUIRE(rate == 10000 || (taps && n_taps > 0 && n_taps % 2 == 1), "metrics_stoi: bad resampling filter");
-  CUM_REQUIRE(window && tw && bands && out, "metrics_stoi: null pointer");
+  CUM_REQUIRE(window && tw && bands && (!(which & 1) || out) && (!(which & 2) || out_e), "metrics_stoi: null pointer");
   StoiLayout L;
   stoi_layout(offsets, lengths, n_clips, rate, L);
   CUM_REQUIRE(workspace && workspace_bytes >= L.bytes, "metrics_stoi: workspace too small");
@@ -700,6 +1029,7 @@ extern "C" int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, 
   p.tw = tw;
   p.bands = bands;
   p.out = out;
+  p.out_e = out_e;
   if (rate == 16000) {   // scipy.signal.resample_poly(x, 5, 8, window=h): zero pre-padding that centres the output
     const int up = 5, down = 8, half = (n_taps - 1) / 2;
     p.taps = taps;
@@ -717,7 +1047,27 @@ extern "C" int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, 
     hipLaunchKernelGGL(stoi_ola_kernel, dim3((unsigned)cdiv64(L.max_comp, 256), nc), dim3(256), 0, st, p);
     hipLaunchKernelGGL(stoi_tob_kernel, dim3((unsigned)cdiv64(L.max_nf, kMetricWaves), nc), dim3(64 * kMetricWaves), 0, st, p);
   }
-  hipLaunchKernelGGL(stoi_corr_kernel, dim3(nc), dim3(256), 0, st, p);
+  if (which & 1) hipLaunchKernelGGL(stoi_corr_kernel, dim3(nc), dim3(256), 0, st, p);
+  if (which & 2) hipLaunchKernelGGL(stoi_ecorr_kernel, dim3(nc), dim3(64 * kMetricWaves), 0, st, p);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
+}
+
+extern "C" int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                                const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
+                                const double *window, const double *tw, const int32_t *bands, void *workspace,
+                                int64_t workspace_bytes, double *out, void *stream) {
+  return stoi_run(clean, processed, n_samples, offsets, lengths, n_clips, rate, taps, n_taps, window, tw, bands, workspace,
+                  workspace_bytes, 1, out, nullptr, stream);
+}
+
+// cum_metrics_stoi_ex <- pystoi.stoi with extended = False (which & 1 -> out), True (which & 2 -> out_e; Jensen & Taal 2016)
+// or both; arguments, tables and workspace (cum_metrics_stoi_workspace_bytes) as cum_metrics_stoi
+extern "C" int cum_metrics_stoi_ex(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                                   const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
+                                   const double *window, const double *tw, const int32_t *bands, void *workspace,
+                                   int64_t workspace_bytes, int32_t which, double *out, double *out_e, void *stream) {
+  CUM_REQUIRE(which >= 1 && which <= 3, "metrics_stoi_ex: which is 1 (STOI), 2 (eSTOI) or 3 (both)");
+  return stoi_run(clean, processed, n_samples, offsets, lengths, n_clips, rate, taps, n_taps, window, tw, bands, workspace,
+                  workspace_bytes, which, out, out_e, stream);
 }

@@ -191,6 +191,11 @@ SIGNATURES = {
     "cum_metrics_clip_reduce": (c_i32, [_P, _P, c_i64, c_i32, _P, c_i64, _P, _P]),
     "cum_metrics_stoi_workspace_bytes": (c_i64, [_P, c_i64, c_i32]),
     "cum_metrics_stoi": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, c_i32, _P, c_i32] + [_P] * 4 + [c_i64, _P, _P]),
+    "cum_metrics_stoi_ex": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, c_i32, _P, c_i32] + [_P] * 4 + [c_i64, c_i32, _P, _P, _P]),
+    "cum_metrics_frames_ext": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, c_i32] + [_P] * 5 + [c_i64] + [_P] * 2 + [c_i64, _P]),
+    "cum_metrics_clip_nanmean": (c_i32, [_P, _P, c_i64, _P, c_i64, _P, _P]),
+    "cum_metrics_sums_workspace_bytes": (c_i64, [_P, c_i64]),
+    "cum_metrics_sums": (c_i32, [_P, _P, c_i64, _P, _P, c_i64, _P, c_i64, _P, _P]),
     "cum_prune_importance_workspace_bytes": (c_i64, [ctypes.POINTER(PruneImpDesc), c_i32]),
     "cum_prune_importance": (c_i32, [ctypes.POINTER(PruneImpDesc), c_i32, _P, _P, c_i64, _P, c_i64, _P]),
     "cum_prune_gather_workspace_bytes": (c_i64, [c_i32, c_i64]),

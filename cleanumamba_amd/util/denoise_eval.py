@@ -10,6 +10,9 @@ The test set layouts are the reference's: DNS (``clean/clean_fileid_{i}.wav`` an
   * every clip is scored in one batched call on the GPU (cleanumamba_amd.util.python_eval.eval_waveforms); PESQ and
     the composites built on it are NaN unless the ``pesq`` package is installed.
   * ``metrics`` is accepted and, as in the reference, not used.
+  * ``extra_metrics`` (not in the reference) names extended metrics of cleanumamba_amd.util.metrics.EXT_METRICS
+    (``estoi``, ``si_sdr``, ``snr``, ``cep_dist``, ``fwsegSNR``); each adds a ``Test/<name>`` length-weighted sum.  An
+    infinite or NaN clip value (a silent clip, an exact copy) makes that sum infinite or NaN.
   * ``resample=True`` takes a test set that is not at 16 kHz (VCTK-DEMAND and full-band DNS ship at 48 kHz): both files
     of such a pair are converted on the GPU (util/resample.py) before anything else, and the pair is denoised and scored
     at 16 kHz.  Without it such a pair is denoised as if it were 16 kHz and the metrics refuse its rate, as before.
@@ -78,13 +81,19 @@ def _pairs(testset_path, validation, VCTK_DEMAND, test_factor):
 
 
 def validate(net, testset_path, quantize_audio_input=False, network_processor=None, validation=True, VCTK_DEMAND=False,
-             metrics=("pesq_wb", "pesq_nb", "stoi", "DNSMOS"), test_factor=1.0, crop=None, batch_size=16, resample=False):
+             metrics=("pesq_wb", "pesq_nb", "stoi", "DNSMOS"), test_factor=1.0, crop=None, batch_size=16, resample=False,
+             extra_metrics=()):
     """Denoise the test set with ``net`` and return the reference's dict of length-weighted sums ('Test/pesq_wb', ...,
     'Test/llr_mean') plus 'Test/count', the total length; divide by 'Test/count' for the means.
 
     resample: convert a pair whose header rate is not 16000 first, on the GPU: noisy from its samples to float32, clean
     likewise and back to int16 as ``(y * 32768).round().clamp(-32768, 32767)``; ``crop`` then counts seconds at 16 kHz."""
-    result = {"Test/" + k: 0 for k in KEYS}
+    from .metrics import EXT_METRICS
+    extra_metrics = tuple(extra_metrics)
+    for k in extra_metrics:                       # before any file is read or denoised
+        if k not in EXT_METRICS:
+            raise ValueError("validate: unknown extra metric %r (have %s)" % (k, ", ".join(EXT_METRICS)))
+    result = {"Test/" + k: 0 for k in KEYS + extra_metrics}
     device, half = torch.device("cuda"), False
     for p in getattr(net, "parameters", lambda: iter(()))():
         device, half = p.device, p.dtype is torch.float16
@@ -138,7 +147,7 @@ def validate(net, testset_path, quantize_audio_input=False, network_processor=No
         return result
     for rate in sorted(set(rates)):
         sel = [i for i, r in enumerate(rates) if r == rate]
-        for r in eval_waveforms([cleans[i] for i in sel], [targets[i] for i in sel], rate):
+        for r in eval_waveforms([cleans[i] for i in sel], [targets[i] for i in sel], rate, extra=extra_metrics):
             for k in r:
                 result["Test/" + k] += r[k]
     return result

@@ -5,6 +5,16 @@
 Taal et al. 2011).  Samples are int16 values, as the reference scores them; float inputs must hold integers in the int16
 range.  Nothing here runs a metric on the CPU: the kernels are the only implementation.
 
+``EXT_METRICS`` names five more per-clip numbers that ``speech_metrics(..., metrics=...)`` computes on request, in the
+same batched way: ``estoi`` (extended STOI, Jensen & Taal 2016), ``si_sdr`` (Le Roux et al. 2019, no mean removal),
+``snr`` (overall SNR), ``cep_dist`` and ``fwsegSNR`` (LPC cepstrum distance and frequency-weighted segmental SNR as in
+Hu & Loizou 2008).  tests/metrics_ext_ref.py states their definitions in f64 numpy.  They are restatements of the
+published algorithms: pystoi, pysepm and torchmetrics are not installed where this was written, and NOTHING here has been
+compared with them.  Known deviation: pystoi adds eps-sized random noise before each eSTOI normalisation; here every norm
+gets an additive eps instead, which keeps the result reproducible.  ``si_sdr`` and ``snr`` come from three exact int64
+sums per clip (GPU); the few scalar operations on them run on the host in Python integers, because Sxx Syy - Sxy^2
+cancels catastrophically in f64 (it can come out negative for y = 3x).
+
 The constant tables are built here on the host:
   * the 25 critical bands of Klatt's weighted spectral slope measure, as published with the composite measures of Hu &
     Loizou, "Evaluation of objective quality measures for speech enhancement", IEEE TASLP 16(1), 2008: centre
@@ -199,46 +209,140 @@ def _reduce(b, values, mode, ws):
     return out
 
 
-def _stoi(b):
+def _frames_ext(b):
+    """Per-frame cepstrum distance and fwseg of an uploaded batch ((2, total) f64) and the workspace."""
+    L = hip.lib()
+    t = _tables(b.device)
+    nf = frame_counts(b.lengths)
+    total = int(nf.sum())
+    out = torch.empty((2, max(total, 1)), dtype=torch.float64, device=b.device)
+    ws = torch.empty(L.cum_metrics_workspace_bytes(b.n_clips, total), dtype=torch.uint8, device=b.device)
+    hip.check(L.cum_metrics_frames_ext(hip.ptr(b.clean), hip.ptr(b.processed), b.clean.numel(), b.hp(b.offsets),
+                                       b.hp(b.lengths), b.n_clips, b.rate, hip.ptr(t["window"]), hip.ptr(t["band_tab"]),
+                                       hip.ptr(t["band_w"]), hip.ptr(t["tw1024"]), hip.ptr(ws), ws.numel(),
+                                       hip.ptr(out[0]), hip.ptr(out[1]), total, hip.stream_ptr()))
+    return out[:, :total], np.concatenate([[0], np.cumsum(nf)]), ws
+
+
+def _nanmean(b, values, ws):
+    out = torch.empty(b.n_clips, dtype=torch.float64, device=b.device)
+    hip.check(hip.lib().cum_metrics_clip_nanmean(hip.ptr(values), b.hp(b.lengths), b.n_clips, hip.ptr(ws), ws.numel(),
+                                                 hip.ptr(out), hip.stream_ptr()))
+    return out
+
+
+def clip_sums(b):
+    """Exact (sum x^2, sum y^2, sum x y) of every clip of an uploaded batch: an (n_clips, 3) int64 tensor on the GPU."""
+    L = hip.lib()
+    ws = torch.empty(L.cum_metrics_sums_workspace_bytes(b.hp(b.lengths), b.n_clips), dtype=torch.uint8, device=b.device)
+    out = torch.empty((b.n_clips, 3), dtype=torch.int64, device=b.device)
+    hip.check(L.cum_metrics_sums(hip.ptr(b.clean), hip.ptr(b.processed), b.clean.numel(), b.hp(b.offsets),
+                                 b.hp(b.lengths), b.n_clips, hip.ptr(ws), ws.numel(), hip.ptr(out), hip.stream_ptr()))
+    return out
+
+
+def _db(num, den):
+    """10 log10(num / den) of two positive Python integers, the quotient correctly rounded."""
+    return 10.0 * math.log10(num / den)
+
+
+def snr_from_sums(sxx, syy, sxy):
+    """Overall SNR 10 log10(sum x^2 / sum (x - y)^2) from the exact integer sums: NaN for a silent clean clip, +inf for
+    y = x."""
+    d = sxx - 2 * sxy + syy
+    if sxx == 0:
+        return float("nan")
+    return float("inf") if d == 0 else _db(sxx, d)
+
+
+def si_sdr_from_sums(sxx, syy, sxy):
+    """SI-SDR (Le Roux et al. 2019, no mean removal) 10 log10(Sxy^2 / (Sxx Syy - Sxy^2)) in exact integers: NaN for a
+    silent clean clip, -inf for Sxy = 0 (a silent or orthogonal processed clip), +inf for y = a x."""
+    if sxx == 0:
+        return float("nan")
+    if sxy == 0:
+        return float("-inf")
+    q = sxx * syy - sxy * sxy
+    return float("inf") if q == 0 else _db(sxy * sxy, q)
+
+
+def _stoi(b, which=1):
+    """(STOI, eSTOI) of an uploaded batch; ``which``: 1 STOI (cum_metrics_stoi, as ever), 2 eSTOI, 3 both on one front
+    end (cum_metrics_stoi_ex); what was not asked for is None."""
     L = hip.lib()
     t = _tables(b.device)
     nbytes = L.cum_metrics_stoi_workspace_bytes(b.hp(b.lengths), b.n_clips, b.rate)
     ws = torch.empty(nbytes, dtype=torch.uint8, device=b.device)
-    out = torch.empty(b.n_clips, dtype=torch.float64, device=b.device)
-    hip.check(L.cum_metrics_stoi(hip.ptr(b.clean), hip.ptr(b.processed), b.clean.numel(), b.hp(b.offsets),
-                                 b.hp(b.lengths), b.n_clips, b.rate, hip.ptr(t["taps"]), t["taps"].numel(),
-                                 hip.ptr(t["stoi_win"]), hip.ptr(t["tw512"]), hip.ptr(t["bands"]), hip.ptr(ws),
-                                 ws.numel(), hip.ptr(out), hip.stream_ptr()))
+    out = [torch.empty(b.n_clips, dtype=torch.float64, device=b.device) if which & m else None for m in (1, 2)]
+    head = (hip.ptr(b.clean), hip.ptr(b.processed), b.clean.numel(), b.hp(b.offsets), b.hp(b.lengths), b.n_clips, b.rate,
+            hip.ptr(t["taps"]), t["taps"].numel(), hip.ptr(t["stoi_win"]), hip.ptr(t["tw512"]), hip.ptr(t["bands"]),
+            hip.ptr(ws), ws.numel())
+    if which == 1:
+        hip.check(L.cum_metrics_stoi(*head, hip.ptr(out[0]), hip.stream_ptr()))
+    else:
+        hip.check(L.cum_metrics_stoi_ex(*head, which, hip.ptr(out[0]) if which & 1 else None, hip.ptr(out[1]),
+                                        hip.stream_ptr()))
     return out
 
 
 METRICS = ("wss_dist", "llr_mean", "segSNR", "stoi")
+EXT_METRICS = ("estoi", "si_sdr", "snr", "cep_dist", "fwsegSNR")      # on request only: no default changes
+_FRAME_NAMES = ("wss_dist", "llr_mean", "segSNR")
+_EXT_FRAME_NAMES = ("cep_dist", "fwsegSNR")
+_STOI_NAMES = ("stoi", "estoi")
 
 
-def frame_metrics(clean, processed, rate=FRAME_RATE):
-    """Per-frame ``segSNR``, ``llr`` and ``wss`` of every clip: a dict of lists of f64 tensors, one per clip."""
+def frame_metrics(clean, processed, rate=FRAME_RATE, extended=False):
+    """Per-frame ``segSNR``, ``llr`` and ``wss`` of every clip: a dict of lists of f64 tensors, one per clip.  With
+    ``extended`` also ``cep`` (LPC cepstrum distance, [0, 10], NaN where either frame is all zeros) and ``fwseg``
+    (frequency-weighted segmental SNR, [-10, 35] dB, NaN where the clean frame is silent)."""
     _check_rate(rate, (FRAME_RATE,))
     b = Batch(clean, processed, rate).upload()
     out, off, _ = _frames(b)
     split = lambda v: [v[off[i]:off[i + 1]] for i in range(b.n_clips)]
-    return {"segSNR": split(out[0]), "llr": split(out[1]), "wss": split(out[2])}
+    res = {"segSNR": split(out[0]), "llr": split(out[1]), "wss": split(out[2])}
+    if extended:
+        ext, _, _ = _frames_ext(b)
+        res["cep"], res["fwseg"] = split(ext[0]), split(ext[1])
+    return res
 
 
 def speech_metrics(clean, processed, rate=FRAME_RATE, metrics=METRICS):
     """Per-clip metrics of a ragged batch: a dict name -> f64 tensor of one value per clip, for each name in ``metrics``
-    (``wss_dist``, ``llr_mean``, ``segSNR``: eval_waveform's recipe at 16 kHz; ``stoi`` at 16 or 10 kHz).
+    (``wss_dist``, ``llr_mean``, ``segSNR``: eval_waveform's recipe at 16 kHz; ``stoi`` at 16 or 10 kHz), in the order
+    asked.  Names of ``EXT_METRICS`` are accepted too: ``cep_dist`` (mean of the lowest 95 % of the frame values, NaN
+    dropped) and ``fwsegSNR`` (mean of the non-NaN frames) at 16 kHz, ``estoi`` at 16 or 10 kHz, ``si_sdr`` and ``snr`` at
+    any positive rate; ``stoi`` and ``estoi`` asked together share one front end.
 
     ``clean`` / ``processed``: lists of 1-D arrays or tensors of int16 values, pairwise of equal length, each at least
     480 samples.  Raises ValueError before any launch for an empty batch, unequal lengths, a short clip or a rate the
     requested metrics do not support."""
     metrics = tuple(metrics)
     for m in metrics:
-        if m not in METRICS:
-            raise ValueError("speech metrics: unknown metric %r (have %s)" % (m, ", ".join(METRICS)))
-    frame_names = [m for m in metrics if m != "stoi"]
-    _check_rate(rate, (FRAME_RATE,) if frame_names else STOI_RATES)
+        if m not in METRICS + EXT_METRICS:
+            raise ValueError("speech metrics: unknown metric %r (have %s)" % (m, ", ".join(METRICS + EXT_METRICS)))
+    frame_names = [m for m in metrics if m in _FRAME_NAMES]
+    ext_names = [m for m in metrics if m in _EXT_FRAME_NAMES]
+    stoi_names = [m for m in metrics if m in _STOI_NAMES]
+    if frame_names or ext_names:
+        _check_rate(rate, (FRAME_RATE,))
+    elif stoi_names:
+        _check_rate(rate, STOI_RATES)
+    elif not (isinstance(rate, (int, np.integer)) and rate > 0):      # si_sdr, snr: the rate is not used
+        raise ValueError("speech metrics: rate %r Hz is not supported (any positive rate)" % (rate,))
     b = Batch(clean, processed, rate).upload()
     res = {}
+    if ext_names:
+        vals, _, ws = _frames_ext(b)
+        if "cep_dist" in metrics:
+            res["cep_dist"] = _reduce(b, vals[0], 2, ws)
+        if "fwsegSNR" in metrics:
+            res["fwsegSNR"] = _nanmean(b, vals[1], ws)
+    if "si_sdr" in metrics or "snr" in metrics:
+        sums = [tuple(int(v) for v in row) for row in clip_sums(b).cpu().tolist()]
+        for name, fn in (("si_sdr", si_sdr_from_sums), ("snr", snr_from_sums)):
+            if name in metrics:
+                res[name] = torch.tensor([fn(*s) for s in sums], dtype=torch.float64, device=b.device)
     if frame_names:
         vals, _, ws = _frames(b)
         if "segSNR" in metrics:
@@ -247,15 +351,18 @@ def speech_metrics(clean, processed, rate=FRAME_RATE, metrics=METRICS):
             res["llr_mean"] = _reduce(b, vals[1], 2, ws)
         if "wss_dist" in metrics:
             res["wss_dist"] = _reduce(b, vals[2], 1, ws)
-    if "stoi" in metrics:
-        res["stoi"] = _stoi(b)
+    if stoi_names:
+        st, est = _stoi(b, ("stoi" in metrics) | 2 * ("estoi" in metrics))
+        if st is not None:
+            res["stoi"] = st
+        if est is not None:
+            res["estoi"] = est
     return {m: res[m] for m in metrics}
 
 
 def stoi(clean, processed, fs, extended=False):
-    """STOI of one clip, ``pystoi.stoi(x, y, fs_sig, extended=False)``'s signature; fs 16000 or 10000."""
-    if extended:
-        raise NotImplementedError("extended STOI is not implemented")
+    """STOI of one clip, ``pystoi.stoi(x, y, fs_sig, extended=False)``'s signature; fs 16000 or 10000.  ``extended``
+    gives eSTOI (Jensen & Taal 2016; an additive eps where pystoi adds eps-sized noise)."""
     _check_rate(fs, STOI_RATES)
     b = Batch([clean], [processed], fs, min_len=1).upload()
-    return float(_stoi(b)[0])
+    return float(_stoi(b, 2 if extended else 1)[1 if extended else 0][0])

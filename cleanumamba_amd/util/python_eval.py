@@ -7,6 +7,10 @@ Deviations, by design:
   * PESQ is not reimplemented.  When the ``pesq`` package imports, it is called on the CPU as the reference calls it;
     otherwise ``pesq_wb``, ``pesq_nb`` and the composites built on PESQ (CSIG, CBAK, COVL) are NaN, with one warning.
   * The frame metrics exist at 16 kHz only (the reference's eval_waveform calls them at 16 kHz whatever the rate).
+
+Beyond the reference: ``cepstrum_distance``, ``fwsegsnr`` and ``si_sdr`` mirror the extended metrics of
+cleanumamba_amd.util.metrics (restated published definitions, not compared with pysepm, pystoi or torchmetrics), and
+``eval_waveforms(..., extra=...)`` adds any of ``metrics.EXT_METRICS`` to its result dicts.
 """
 import math
 import warnings
@@ -65,6 +69,31 @@ def snr(clean_speech, processed_speech, sample_rate):
     return overall, seg
 
 
+def cepstrum_distance(clean_speech, processed_speech, sample_rate):
+    """Per-frame LPC cepstrum distance (Hu & Loizou 2008), limited to [0, 10]; NaN where a frame is all zeros."""
+    _same_length(clean_speech, processed_speech, "Both Speech Files must be same length.")
+    if sample_rate != M.FRAME_RATE:
+        raise ValueError("cepstrum_distance: only 16 kHz is supported (got %r)" % (sample_rate,))
+    fm = M.frame_metrics([np.asarray(clean_speech)], [np.asarray(processed_speech)], sample_rate, extended=True)
+    return fm["cep"][0].cpu().numpy()
+
+
+def fwsegsnr(clean_speech, processed_speech, sample_rate):
+    """Per-frame frequency-weighted segmental SNR (Hu & Loizou 2008), limited to [-10, 35] dB; NaN where the clean frame
+    is silent."""
+    _same_length(clean_speech, processed_speech, "Both Speech Files must be same length.")
+    if sample_rate != M.FRAME_RATE:
+        raise ValueError("fwsegsnr: only 16 kHz is supported (got %r)" % (sample_rate,))
+    fm = M.frame_metrics([np.asarray(clean_speech)], [np.asarray(processed_speech)], sample_rate, extended=True)
+    return fm["fwseg"][0].cpu().numpy()
+
+
+def si_sdr(clean, processed):
+    """Scale-invariant SDR in dB (Le Roux et al. 2019, no mean removal) of one clip, from exact integer sums."""
+    _same_length(clean, processed, "Both Speech Files must be same length.")
+    return float(M.speech_metrics([np.asarray(clean)], [np.asarray(processed)], metrics=("si_sdr",))["si_sdr"][0])
+
+
 def composites(pesq_mos, llr_mean, wss_dist, seg_snr):
     """CSIG, CBAK, COVL (Hu & Loizou 2008) limited to [1, 5]; NaN when PESQ is NaN."""
     if math.isnan(pesq_mos):
@@ -76,10 +105,20 @@ def composites(pesq_mos, llr_mean, wss_dist, seg_snr):
     return csig, cbak, covl
 
 
-def eval_waveforms(cleans, targets, rate):
-    """eval_waveform of every (clean, target) pair, with all clips scored in one batched call: a list of result dicts."""
-    m = M.speech_metrics(cleans, targets, M.FRAME_RATE, metrics=("wss_dist", "llr_mean", "segSNR"))
-    st = M.speech_metrics(cleans, targets, rate, metrics=("stoi",))["stoi"]
+def eval_waveforms(cleans, targets, rate, extra=()):
+    """eval_waveform of every (clean, target) pair, with all clips scored in one batched call: a list of result dicts.
+    ``extra``: names of ``metrics.EXT_METRICS`` to add as length-weighted sums like the rest (``cep_dist`` and
+    ``fwsegSNR`` at 16 kHz like the other frame metrics, ``estoi``, ``si_sdr`` and ``snr`` at ``rate``)."""
+    extra = tuple(extra)
+    for k in extra:
+        if k not in M.EXT_METRICS:
+            raise ValueError("eval_waveforms: unknown extra metric %r (have %s)" % (k, ", ".join(M.EXT_METRICS)))
+    ext_frame = tuple(k for k in extra if k in ("cep_dist", "fwsegSNR"))
+    ext_rate = tuple(k for k in extra if k not in ext_frame)
+    m = M.speech_metrics(cleans, targets, M.FRAME_RATE, metrics=("wss_dist", "llr_mean", "segSNR") + ext_frame)
+    at_rate = M.speech_metrics(cleans, targets, rate, metrics=("stoi",) + ext_rate)
+    st = at_rate.pop("stoi")
+    m.update(at_rate)
     m = {k: v.cpu().numpy() for k, v in m.items()}
     st = st.cpu().numpy()
     pesq = _pesq_fn()
@@ -104,6 +143,8 @@ def eval_waveforms(cleans, targets, rate):
         result["segSNR"] += seg * length
         result["llr_mean"] += llr_mean * length
         result["count"] += 1 * length
+        for k in extra:
+            result[k] += float(m[k][i]) * length
         out.append(result)
     return out
 

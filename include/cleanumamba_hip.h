@@ -758,6 +758,39 @@ int cum_metrics_stoi(const int16_t *clean, const int16_t *processed, int64_t n_s
                      const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
                      const double *window, const double *tw, const int32_t *bands, void *workspace,
                      int64_t workspace_bytes, double *out, void *stream);
+/* The extended metrics below restate published definitions (tests/metrics_ext_ref.py holds them in f64 numpy); none has
+ * been compared with pystoi, pysepm or torchmetrics.  Same conventions as the entries above.
+ * cum_metrics_stoi_ex <- pystoi.stoi(x, y, rate, extended=...): which & 1 writes STOI to out (the bits of
+ * cum_metrics_stoi), which & 2 writes eSTOI (Jensen & Taal, IEEE/ACM TASLP 24(11), 2016) to out_e; the front end up to
+ * the one-third-octave magnitudes runs once.  Per 30-frame segment both 15 x 30 matrices get zero-mean unit-norm rows,
+ * then zero-mean unit-norm columns (every norm + eps; pystoi adds eps-sized noise instead), the value is sum(Xn Yn) / 30,
+ * the clip's the mean over segments; 1e-5 below 30 STFT frames.  Workspace: cum_metrics_stoi_workspace_bytes. */
+int cum_metrics_stoi_ex(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                        const int64_t *lengths, int64_t n_clips, int32_t rate, const double *taps, int32_t n_taps,
+                        const double *window, const double *tw, const int32_t *bands, void *workspace,
+                        int64_t workspace_bytes, int32_t which, double *out, double *out_e, void *stream);
+/* cum_metrics_frames_ext <- the two remaining measures of Hu & Loizou 2008 on cum_metrics_frames' frames, window, tables,
+ * workspace and layout (16 kHz).  cep: (10 / ln 10) sqrt(2 sum_k (c_k - c'_k)^2) of the order-16 LPC cepstra
+ * (c_1 = -a_1, c_k = -a_k - (1/k) sum_{i<k} i c_i a_{k-i}), limited to [0, 10], NaN where either frame is all zeros.
+ * fwseg: |FFT_1024| of the frame / 32768 * window over bins 0..511, each spectrum divided by (its sum + eps), critical
+ * band sums ce_b / pe_b of these magnitudes, sum_b W_b 10 log10(ce_b^2 / max((ce_b - pe_b)^2, eps)) / sum_b W_b with
+ * W_b = ce_b^0.2 over the bands with ce_b > 0, limited to [-10, 35]; NaN where the clean frame is silent. */
+int cum_metrics_frames_ext(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                           const int64_t *lengths, int64_t n_clips, int32_t rate, const double *window,
+                           const int32_t *band_tab, const double *band_w, const double *tw, void *workspace,
+                           int64_t workspace_bytes, double *cep, double *fwseg, int64_t n_frames_total, void *stream);
+/* cum_metrics_clip_nanmean: out[i] = mean of clip i's frame values that are not NaN (fwsegSNR), NaN if it has none;
+ * layout and workspace as cum_metrics_clip_reduce (whose mode 2 is the clip reduce of cep). */
+int cum_metrics_clip_nanmean(const double *values, const int64_t *lengths, int64_t n_clips, void *workspace,
+                             int64_t workspace_bytes, double *out, void *stream);
+/* cum_metrics_sums: out[i][3] = exact int64 (sum x^2, sum y^2, sum x y) of clip i; any rate, clips of >= 1 sample.  The
+ * overall SNR 10 log10(Sxx / (Sxx - 2 Sxy + Syy)) and SI-SDR 10 log10(Sxy^2 / (Sxx Syy - Sxy^2)) (Le Roux et al., ICASSP
+ * 2019, no mean removal) follow from them in exact integer arithmetic on the host.  Workspace (bytes; -1 for bad
+ * arguments): cum_metrics_sums_workspace_bytes. */
+int64_t cum_metrics_sums_workspace_bytes(const int64_t *lengths, int64_t n_clips);
+int cum_metrics_sums(const int16_t *clean, const int16_t *processed, int64_t n_samples, const int64_t *offsets,
+                     const int64_t *lengths, int64_t n_clips, void *workspace, int64_t workspace_bytes, int64_t *out,
+                     void *stream);
 
 /* ---- structured channel pruning (cleanumamba_amd/pruning/; reference src/pruning/pruninggroup.py, util.py:328-349) --
  * Both entries take HOST descriptor tables, check every descriptor before any launch (CUM_EINVAL, nothing launched),

@@ -1,7 +1,8 @@
 """Speech metrics (util/metrics.py) on the DNS validation shape: 150 clips x 10 s at 16 kHz, all four metrics (wss_dist,
-llr_mean, segSNR, STOI) in one speech_metrics call.  GPU box only.  Prints one JSON line: the batch's wall time after a
-warm-up (device synchronised), and per-clip times.  Kernel times come from a separate run of this script under
-``rocprofv3 --kernel-trace --stats``.
+llr_mean, segSNR, STOI) in one speech_metrics call, and the same batch with the five extended metrics added (estoi,
+si_sdr, snr, cep_dist, fwsegSNR: nine in all), the two timed alternately in one run.  GPU box only.  Prints one JSON
+line: each batch's wall time after a warm-up (device synchronised), per-clip times and the ratio nine / four.  Kernel
+times come from a separate run of this script under ``rocprofv3 --kernel-trace --stats``.
 Usage: python tools/bench_metrics.py [clips] [seconds] [repeats] [out.json]"""
 import json
 import sys
@@ -33,19 +34,33 @@ dev = torch.device("cuda")
 clean_d = [torch.from_numpy(c).to(dev) for c in clean]
 proc_d = [torch.from_numpy(p).to(dev) for p in proc]
 
-r = M.speech_metrics(clean_d, proc_d)                         # warm-up (tables, library, allocator)
-torch.cuda.synchronize()
-times = []
-for _ in range(REPEATS):
+NINE = M.METRICS + M.EXT_METRICS
+
+
+def timed(names):
     torch.cuda.synchronize()
     t0 = time.perf_counter()
-    r = M.speech_metrics(clean_d, proc_d)
+    res = M.speech_metrics(clean_d, proc_d, metrics=names)
     torch.cuda.synchronize()
-    times.append(time.perf_counter() - t0)
+    return time.perf_counter() - t0, res
+
+
+timed(M.METRICS)                                              # warm-up (tables, library, allocator)
+timed(NINE)
+times, times9 = [], []
+for _ in range(REPEATS):                                      # alternating: both see the same clocks and allocator state
+    dt, r = timed(M.METRICS)
+    times.append(dt)
+    dt, r9 = timed(NINE)
+    times9.append(dt)
 res = {"clips": CLIPS, "seconds_per_clip": SECONDS, "frames": int(M.frame_counts([n] * CLIPS).sum()),
        "batch_ms_median": round(1e3 * float(np.median(times)), 2), "batch_ms_min": round(1e3 * min(times), 2),
        "per_clip_ms": round(1e3 * float(np.median(times)) / CLIPS, 3),
-       "means": {k: round(float(v.mean()), 5) for k, v in r.items()}}
+       "means": {k: round(float(v.mean()), 5) for k, v in r.items()},
+       "nine": {"batch_ms_median": round(1e3 * float(np.median(times9)), 2), "batch_ms_min": round(1e3 * min(times9), 2),
+                "per_clip_ms": round(1e3 * float(np.median(times9)) / CLIPS, 3),
+                "ratio_to_four": round(float(np.median(times9) / np.median(times)), 3),
+                "means": {k: round(float(v.mean()), 5) for k, v in r9.items()}}}
 print(json.dumps(res))
 if OUT:
     with open(OUT, "w") as f:
