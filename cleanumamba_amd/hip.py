@@ -229,6 +229,8 @@ SIGNATURES = {
     "cum_reverb_workspace_elems": (c_i64, [c_i32, c_i64]),
     "cum_reverb_pairs": (c_i32, [_P, c_i64, _P, c_i64, c_i32, c_i64, _P, _P, c_i64, _P, _P, c_i32, _P, _P, c_i64, _P, c_i64,
                                  _P]),
+    "cum_mix_workspace_elems": (c_i64, [c_i32, c_i64]),
+    "cum_mix_pairs": (c_i32, [_P, c_i64, _P, c_i32, c_i64, _P, _P, c_i64, _P, c_i64, _P, _P]),
 }
 
 _lib = None

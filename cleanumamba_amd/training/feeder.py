@@ -42,9 +42,23 @@ follow the band records (or the draw table), still in the one upload; the bank o
 construction, in uploads of its own; and cum_reverb_pairs (csrc/reverb.hip) runs first: assemble -> A, reverb A -> B,
 band B -> A, augment A -> the step's inputs (two scratch pairs, never a third).  Without ``augment`` nothing here changes.
 
+``BatchFeeder(SpeechNoiseDataset(...), ..., mix=Mix(...))`` (util/dataset.py, training/mix.py) -- a MIXING
+feeder -- trains from separate speech and noise corpora, as the DNS challenge distributes them, without the offline
+synthesiser: the plan above orders and crops the SPEECH files (one no longer than the crop is read whole and repeated
+on the device); every row's noise is laid out afresh each epoch by a generator of its own per (seed, epoch, rank, batch,
+row) -- pieces of random noise files from a random start to their end, ``gap`` zeros behind each, at most ``max_pieces``
+of them, the last one cut (``noise_plan``); the workers read the speech crop into the clean row and the pieces into the
+noisy row of the slot; the batch's SNR and level draws ride in the slot's tail as the records of cum_mix_pairs, in the
+one upload; and ``into()`` launches cum_mix_pairs (csrc/mix.hip) in the assembling kernel's place: noise scaled to an SNR
+against the active level of both signals, the mixture brought to a level in dBFS, a guard against clipping, straight
+into the step's inputs -- or, with ``augment``, over the longer crops into the scratch the chain above reads, which
+follows unchanged.  ``PcmBatch.mix_stats()`` is the rows' device table of what was applied.  ``workers=0`` (a mixing
+feeder only) reads in ``next()`` itself.  Without ``mix`` nothing here changes.
+
 ``device="cpu"`` keeps the same pipeline without pinning or streams and does the kernel's arithmetic with torch on the
 host, so the loop runs anywhere -- a rated feeder too, as long as every pair is at the model rate: there is no CPU
-resampler (util/resample.py), so any other rate is a ValueError at construction.
+resampler (util/resample.py), so any other rate is a ValueError at construction.  A mixing feeder on the CPU runs
+``mix.apply``'s NumPy arithmetic.
 """
 import ctypes
 import inspect
@@ -57,6 +71,7 @@ import torch
 from .. import hip
 from ..util import resample as rs
 from . import augment as aug
+from . import mix as mx
 
 SAMPLE_RATE = 16000
 PCM_SCALE = 1.0 / 32768.0
@@ -68,9 +83,9 @@ def _round_up(n, m):
 
 class _Slot:
     """One block of ``2 * batch * pitch`` int16 samples followed by ``batch`` int32 clip lengths -- in a rated feeder by
-    ``batch`` records of 16 int32 -- and, in an augmenting feeder, by ``aug_ints`` int32 of draw table (with a band mask:
-    the band records behind it, with a reverb: the room records behind those), as one int16 tensor so that it moves in one
-    copy."""
+    ``batch`` records of 16 int32, in a mixing feeder by ``batch`` records of 12 -- and, in an augmenting feeder, by
+    ``aug_ints`` int32 of draw table (with a band mask: the band records behind it, with a reverb: the room records behind
+    those), as one int16 tensor so that it moves in one copy."""
 
     def __init__(self, batch, pitch, device, pin, tail_ints=1, aug_ints=0):
         self.batch, self.pitch = batch, pitch
@@ -79,6 +94,7 @@ class _Slot:
         self.scratch = self.workspace = None     # device blocks of an augmenting feeder: the L + S float crops, tile sums
         self.band_scratch = self.band_workspace = None       # ... with a band mask or a reverb: the second pair; the spectra
         self.reverb_workspace = None                         # ... with a reverb: its spectra
+        self.mix_workspace = self.mix_stats = None           # device blocks of a mixing feeder: the totals; the rows' stats
         self.seq = -1                # the batch this block holds
         self.uploaded = None         # event after the upload (device blocks on a GPU)
         self.released = []           # events after the assembling kernels that read this block
@@ -99,6 +115,10 @@ class _Slot:
         behind the start of the draw table."""
         return self.flat[self._aug + 2 * at:self._aug + 2 * (at + ints)].view(torch.int32)
 
+    def mix_records(self):
+        """(batch, 12) int32 view of a mixing slot's tail: the records of cum_mix_pairs (8-byte aligned likewise)."""
+        return self.flat[2 * self.batch * self.pitch:self._aug].view(torch.int32).view(self.batch, mx.REC_INTS)
+
     def records(self):
         """(batch, 16) int32 view of a rated slot's tail (8-byte aligned: a row is 16 bytes times a whole number)."""
         return self.flat[2 * self.batch * self.pitch:self._aug].view(torch.int32).view(self.batch, rs.REC_INTS)
@@ -110,6 +130,7 @@ class _Pending:
     def __init__(self, seq, epoch, entries, windows=None, records=None, draws=None, table=None, band=None,
                  rooms=None):
         self.seq, self.epoch, self.entries = seq, epoch, entries
+        self.mix = self.mix_table = self.noise = None        # a mixing feeder's: MixDraws, its (nb, 12) records, the noise plan
         self.windows, self.records = windows, records        # a rated feeder's: [(m0, M, rate)], (nb, 16) int32 on the host
         self.draws, self.table = draws, table                # an augmenting feeder's: AugmentDraws, its packed int32 table
         self.band = band                                     # ... with a band mask: its packed band records
@@ -125,14 +146,20 @@ class PcmBatch:
     from the files;  epoch;  shape: the (B, 1, L) of the float tensors it assembles;  windows (a rated feeder's, else
     None): [(m0, M, rate)] per clip -- the clip is outputs [m0, m0 + L) of its file's M model-rate samples, or, with
     M <= L, all of them repeated;  draws (an augmenting feeder's, else None): the batch's ``AugmentDraws`` -- the plan's
-    crops are then ``draws.shift`` samples longer than L, and ``into`` applies the draws to them."""
+    crops are then ``draws.shift`` samples longer than L, and ``into`` applies the draws to them.  From a mixing feeder
+    (``mix=``): entries are the speech reads, fileids the speech paths, ``noise`` the noise rows' plan ([(noise file, start,
+    count, position in the row)] per clip) and ``mix`` the batch's ``MixDraws``."""
 
-    def __init__(self, feeder, seq, epoch, entries, slot, windows=None, records=None, draws=None):
+    def __init__(self, feeder, seq, epoch, entries, slot, windows=None, records=None, draws=None, mix=None, noise=None):
         self._feeder, self._seq, self._slot = feeder, seq, slot
         self.epoch, self.entries = epoch, entries
         self.windows, self._records, self.draws = windows, records, draws
+        self.mix, self.noise = mix, noise
         files = getattr(feeder.dataset, "files", None)
-        self.fileids = [tuple(files[i]) if files is not None else i for i, _, _ in entries]
+        if mix is not None:
+            self.fileids = [feeder.dataset.speech_files[i] for i, _, _ in entries]
+        else:
+            self.fileids = [tuple(files[i]) if files is not None else i for i, _, _ in entries]
         self.device = feeder.device
         self.shape = torch.Size((len(entries), 1, feeder.crop_length))
         self.uploaded = slot.uploaded        # the event after this batch's upload (None on the CPU)
@@ -164,12 +191,18 @@ class PcmBatch:
             if self.draws is not None:
                 clean, noisy = torch.empty(nb, length), torch.empty(nb, length)
                 strides = [length, length]
-            n = slot.src_len()[:nb] if self._records is None else slot.records()[:nb, rs.FEED_N_SRC]     # (model rate)
-            rows, n = slot.rows(nb), n.to(torch.int64).clamp(1, length)
-            idx = torch.arange(length)[None, :] % n[:, None]
-            for t, sb, src in ((clean, strides[0], rows[0]), (noisy, strides[1], rows[1])):
-                out = torch.as_strided(t, (nb, length), (sb, 1))
-                out.copy_(torch.gather(src, 1, idx).to(torch.float32) * PCM_SCALE)
+            rows = slot.rows(nb)
+            if self.mix is not None:         # speech row, noise row -> (clean, noisy): training/mix.py on the host
+                outs = [torch.as_strided(t, (nb, length), (sb, 1)) for t, sb in ((clean, strides[0]), (noisy, strides[1]))]
+                mx.apply(rows[0][:, :length], slot.mix_records()[:nb, mx.REC_N_SPEECH], rows[1][:, :length], self.mix,
+                         outs[0], outs[1], slot.mix_stats[:nb])
+            else:
+                n = slot.src_len()[:nb] if self._records is None else slot.records()[:nb, rs.FEED_N_SRC]     # (model rate)
+                n = n.to(torch.int64).clamp(1, length)
+                idx = torch.arange(length)[None, :] % n[:, None]
+                for t, sb, src in ((clean, strides[0], rows[0]), (noisy, strides[1], rows[1])):
+                    out = torch.as_strided(t, (nb, length), (sb, 1))
+                    out.copy_(torch.gather(src, 1, idx).to(torch.float32) * PCM_SCALE)
             if self.draws is not None:
                 aug.apply(clean, noisy, self.draws, out_clean, out_noisy, reverb=self._feeder.augment.reverb)
             return out_clean, out_noisy
@@ -179,7 +212,10 @@ class PcmBatch:
             if self.draws is not None:       # the block's own float scratch: the release events below cover it too
                 clean, noisy = slot.scratch
                 strides = [clean.stride(0), noisy.stride(0)]
-            if self._records is None:
+            if self.mix is not None:         # in the assembling kernel's place: csrc/mix.hip, three launches
+                mx.launch(slot.flat, slot.pitch, slot.mix_records(), nb, length, slot.mix_workspace, clean, strides[0],
+                          noisy, strides[1], slot.mix_stats)
+            elif self._records is None:
                 hip.check(hip.lib().cum_pcm_batch_f32(hip.ptr(slot.flat), slot.pitch, hip.ptr(slot.src_len()), nb, length,
                                                       hip.ptr(clean), strides[0], hip.ptr(noisy), strides[1],
                                                       ctypes.c_void_p(stream.cuda_stream)))
@@ -211,6 +247,14 @@ class PcmBatch:
             slot.released.append(done)       # the next upload into this block waits for it (on the device)
         return out_clean, out_noisy
 
+    def mix_stats(self):
+        """A mixing feeder's batch: the (B, 8) float32 stats of its rows on the feeder's device (training/mix.py: a, g, the
+        active levels, the peak, the active shares, the guard's flag), as the last ``into`` of this batch left them, for
+        logging.  Nothing is waited for: on a GPU the tensor is valid in stream order behind that ``into``."""
+        if self.mix is None:
+            raise RuntimeError("PcmBatch.mix_stats: the feeder does not mix (BatchFeeder(..., mix=Mix(...)))")
+        return self._live_slot().mix_stats[:self.shape[0]]
+
     def tensors(self):
         """(clean, noisy): two fresh (B, 1, L) float32 tensors, assembled by ``into``."""
         self._live_slot()
@@ -224,7 +268,9 @@ class BatchFeeder:
     the next ``for`` continues with the next epoch; the workers prefetch across the boundary.
 
     dataset: anything with ``__len__``, ``pair_length(n)``, ``read_pcm(n, start, count)``, (for the batch's ``fileids``)
-      ``files`` and (for a rated feeder) ``pair_rate(n)``: util/dataset.CleanNoisyPairDataset.
+      ``files`` and (for a rated feeder) ``pair_rate(n)``: util/dataset.CleanNoisyPairDataset.  With ``mix``: anything
+      with ``__len__``, ``n_noise``, ``speech_length(i)``, ``noise_length(j)``, ``read_speech`` / ``read_noise(i, start,
+      count, out)`` and ``speech_files``: util/dataset.SpeechNoiseDataset.
     crop_length: samples per clip of the batch, at the model's rate; default ``int(dataset.crop_length_sec * 16000)``.  A
       longer clip gives a random window, a shorter one is uploaded whole and repeated on the device.
     sample_rate: None -- no header rate is read, every file is taken as it is; or the model's rate (16000): every pair's
@@ -246,11 +292,28 @@ class BatchFeeder:
       every batch takes one more launch pair (csrc/bandmask.hip) between the assembling kernel and the augmenting one.
       With ``reverb`` the room records ride behind those, the bank of responses is uploaded here, once, and every batch
       takes three more launches (csrc/reverb.hip) right behind the assembling kernel; every device block owns the
-      stage's workspace (48 MB at the E8 batch)."""
+      stage's workspace (48 MB at the E8 batch).
+    mix: None, or a ``training.mix.Mix`` with a ``util.dataset.SpeechNoiseDataset`` (the one without the other is a
+      ValueError, as is ``mix`` with ``sample_rate``): the plan orders and crops the speech files, ``noise_plan(epoch, k)``
+      lays out every row's noise, the ``MixDraws`` of batch k of epoch e come from
+      ``PCG64([seed, e, rank, k, 0x4D6978])`` (``mix_draws``) and travel in the slot's tail as the records of
+      cum_mix_pairs, which takes the assembling kernel's place (csrc/mix.hip, three launches).  ``workers`` may be 0:
+      ``next()`` then reads the batch itself."""
 
     def __init__(self, dataset, batch_size, device, crop_length=None, shuffle=True, seed=0, drop_last=True, depth=2,
-                 workers=4, rank=0, world=1, timeout_s=60, sample_rate=None, augment=None):
+                 workers=4, rank=0, world=1, timeout_s=60, sample_rate=None, augment=None, mix=None):
         self.dataset = dataset
+        unpaired = hasattr(dataset, "read_speech")
+        if mix is not None and not isinstance(mix, mx.Mix):
+            raise ValueError("BatchFeeder: mix must be a training.mix.Mix or None")
+        if unpaired and mix is None:
+            raise ValueError("BatchFeeder: a dataset of separate speech and noise needs mix=Mix(...)")
+        if mix is not None and not unpaired:
+            raise ValueError("BatchFeeder: mix= takes a SpeechNoiseDataset; a dataset of pairs is already mixed")
+        if mix is not None and sample_rate is not None:
+            raise ValueError("BatchFeeder: mix= and sample_rate= do not combine (a SpeechNoiseDataset is at one rate)")
+        self.mix = mix
+        self._length = dataset.speech_length if unpaired else dataset.pair_length        # samples of clip n
         self.batch_size = int(batch_size)
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
@@ -265,7 +328,7 @@ class BatchFeeder:
         self.depth, self.workers = int(depth), int(workers)
         self.rank, self.world = int(rank), int(world)
         self.timeout_s = float(timeout_s)
-        if self.batch_size < 1 or self.crop_length < 1 or self.depth < 1 or self.workers < 1:
+        if self.batch_size < 1 or self.crop_length < 1 or self.depth < 1 or self.workers < (0 if mix is not None else 1):
             raise ValueError("BatchFeeder: batch_size, crop_length, depth and workers must be at least 1")
         if not 0 <= self.rank < self.world:
             raise ValueError(f"BatchFeeder: rank {self.rank} outside world {self.world}")
@@ -273,7 +336,7 @@ class BatchFeeder:
         if len(self) < 1:
             raise ValueError(f"BatchFeeder: {len(dataset)} pairs over {self.world} rank(s) give no batch of "
                              f"{self.batch_size}")
-        self._read_into = "out" in inspect.signature(dataset.read_pcm).parameters
+        self._read_into = unpaired or "out" in inspect.signature(dataset.read_pcm).parameters
 
         gpu = self.device.type == "cuda"
         if gpu:
@@ -283,7 +346,7 @@ class BatchFeeder:
         if self.sample_rate is not None:
             need = self._read_rates(gpu)
         self.pitch = _round_up(need, 8)
-        tail = 1 if self.sample_rate is None else rs.REC_INTS
+        tail = mx.REC_INTS if self.mix is not None else 1 if self.sample_rate is None else rs.REC_INTS
         self._aug_k = self.augment.max_taps if self.augment is not None else 0       # tap columns of the draw table
         table = aug.table_ints(self.batch_size, self._aug_k) if self.augment is not None else 0
         self._band_at = None                    # with a band mask: where its records start, in int32 behind the draw table
@@ -311,6 +374,11 @@ class BatchFeeder:
                     block.band_workspace = aug.band_workspace_for(self.batch_size, self.device)
                 if self._reverb_at is not None:
                     block.reverb_workspace = aug.reverb_workspace_for(self.batch_size, self._plan_length, self.device)
+        if self.mix is not None:
+            for block in self._dev:
+                block.mix_stats = torch.zeros(self.batch_size, mx.STATS, dtype=torch.float32, device=self.device)
+                if gpu:
+                    block.mix_workspace = mx.workspace_for(self.batch_size, self._plan_length, self.device)
         self._stream = torch.cuda.Stream(self.device) if gpu else None
 
         self._cv = threading.Condition()
@@ -402,7 +470,7 @@ class BatchFeeder:
         entries, windows = [], []
         for pos in range(self.rank, n, self.world)[:self.per_rank]:
             index = int(perm[pos])
-            length = int(self.dataset.pair_length(index))
+            length = int(self._length(index))
             if length < 1:
                 raise ValueError(f"pair {index} of the dataset is empty")
             if self.sample_rate is not None:
@@ -432,6 +500,37 @@ class BatchFeeder:
         rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch), self.rank, int(k), 0x417567]))
         return self.augment.draw(rng, self.batch_size if nb is None else nb, self.crop_length)
 
+    def mix_draws(self, epoch, k, nb=None):
+        """The ``MixDraws`` of batch ``k`` of ``epoch`` on this rank (None without ``mix``): a function of (seed, epoch,
+        rank, k) and the config alone."""
+        if self.mix is None:
+            return None
+        rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch), self.rank, int(k), 0x4D6978]))
+        return self.mix.draw(rng, self.batch_size if nb is None else nb)
+
+    def noise_plan(self, epoch, k, nb=None):
+        """[[(noise file, start, count, position in the row)] per row] of batch ``k`` of ``epoch`` on this rank (None without
+        ``mix``) -- the noise samples the workers read and where they put them: a function of (seed, epoch, rank, k, the
+        row, the noise files' lengths, the config) alone.  Row r draws from ``PCG64([seed, epoch, rank, k, r, 0x4E6F69])``:
+        a piece is a uniformly drawn file from a uniformly drawn start to its end, ``mix.gap`` zeros follow it, and pieces
+        repeat until the row's ``crop_length`` (+ shift) samples are full; the last piece is cut, and what ``max_pieces``
+        pieces leave open stays zero."""
+        if self.mix is None:
+            return None
+        rows, need = [], self._plan_length
+        for r in range(self.batch_size if nb is None else nb):
+            rng = np.random.Generator(np.random.PCG64([self.seed, int(epoch), self.rank, int(k), r, 0x4E6F69]))
+            pieces, pos = [], 0
+            while pos < need and len(pieces) < self.mix.max_pieces:
+                j = int(rng.integers(0, self.dataset.n_noise))
+                length = int(self.dataset.noise_length(j))
+                start = int(rng.integers(0, length))
+                count = min(length - start, need - pos)
+                pieces.append((j, start, count, pos))
+                pos += count + self.mix.gap
+            rows.append(pieces)
+        return rows
+
     # ------------------------------------------------------------------ workers
     def _take_row(self):
         """Under the lock: the next (pending batch, row) whose staging slot is free, or None."""
@@ -456,6 +555,9 @@ class BatchFeeder:
                 pend = _Pending(self._next_seq, epoch, plan[b])
                 if windows is not None:
                     pend.windows, pend.records = windows[b], self._records(plan[b], windows[b])
+                if self.mix is not None:
+                    pend.mix, pend.noise = self.mix_draws(epoch, b, len(plan[b])), self.noise_plan(epoch, b, len(plan[b]))
+                    pend.mix_table = torch.from_numpy(pend.mix.pack([count for _, _, count in plan[b]])).view(-1, mx.REC_INTS)
                 if self.augment is not None:
                     pend.draws = self.draws(epoch, b, len(plan[b]))
                     pend.table = torch.from_numpy(pend.draws.pack(self._aug_k))
@@ -486,36 +588,49 @@ class BatchFeeder:
                     if job is not None:
                         break
                     self._cv.wait(0.5)
-            pend, r = job
-            index, start, count = pend.entries[r]
-            error = None
-            try:
-                nb = len(pend.entries)
-                k = pend.seq % self.depth
-                flat = self._stage_np[k]
-                rows = flat[:2 * nb * self.pitch].reshape(2, nb, self.pitch)
-                if self._read_into:
-                    self.dataset.read_pcm(index, start, count, out=(rows[0, r], rows[1, r]))
-                else:
-                    pair = self.dataset.read_pcm(index, start, count)
-                    for dst, src in zip((rows[0, r], rows[1, r]), pair):
-                        src = np.asarray(src)
-                        if src.dtype != np.int16 or src.shape != (count,):
-                            raise ValueError(f"read_pcm returned {src.dtype} {src.shape}, not int16 ({count},)")
-                        dst[:count] = src
-                if pend.records is None:                # (a rated batch's tail is its record table: _upload writes it)
-                    flat[2 * self.batch_size * self.pitch:].view(np.int32)[r] = count
-            except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next() with the file's name
-                files = getattr(self.dataset, "files", None)
-                name = " / ".join(files[index]) if files is not None else f"pair {index}"
-                error = RuntimeError(f"BatchFeeder: reading {name} failed: {exc!r}")
-                error.__cause__ = exc
-            with self._cv:
-                if error is not None and pend.error is None:
-                    pend.error = error
-                pend.todo -= 1
-                if pend.todo == 0 or error is not None:
-                    self._cv.notify_all()
+            self._read_row(*job)
+
+    def _read_row(self, pend, r):
+        """Read row ``r`` of a pending batch into its staging slot and count it off."""
+        index, start, count = pend.entries[r]
+        error = None
+        try:
+            nb = len(pend.entries)
+            k = pend.seq % self.depth
+            flat = self._stage_np[k]
+            rows = flat[:2 * nb * self.pitch].reshape(2, nb, self.pitch)
+            if self.mix is not None:
+                self.dataset.read_speech(index, start, count, out=rows[0, r])
+                row, pos = rows[1, r], 0
+                for j, at_file, n, at in pend.noise[r]:          # the pieces, zeros between and behind them
+                    row[pos:at] = 0
+                    self.dataset.read_noise(j, at_file, n, out=row[at:at + n])
+                    pos = at + n
+                row[pos:self._plan_length] = 0
+            elif self._read_into:
+                self.dataset.read_pcm(index, start, count, out=(rows[0, r], rows[1, r]))
+            else:
+                pair = self.dataset.read_pcm(index, start, count)
+                for dst, src in zip((rows[0, r], rows[1, r]), pair):
+                    src = np.asarray(src)
+                    if src.dtype != np.int16 or src.shape != (count,):
+                        raise ValueError(f"read_pcm returned {src.dtype} {src.shape}, not int16 ({count},)")
+                    dst[:count] = src
+            if pend.records is None and pend.mix is None:    # (a rated or mixing batch's tail is its records: _upload)
+                flat[2 * self.batch_size * self.pitch:].view(np.int32)[r] = count
+        except Exception as exc:      # noqa: BLE001 - surfaces in the consumer's next() with the file's name
+            files = getattr(self.dataset, "files", None)
+            name = " / ".join(files[index]) if files is not None else f"pair {index}"
+            if self.mix is not None:
+                name = f"{self.dataset.speech_files[index]} (or the noise of its row)"
+            error = RuntimeError(f"BatchFeeder: reading {name} failed: {exc!r}")
+            error.__cause__ = exc
+        with self._cv:
+            if error is not None and pend.error is None:
+                pend.error = error
+            pend.todo -= 1
+            if pend.todo == 0 or error is not None:
+                self._cv.notify_all()
 
     # ------------------------------------------------------------------ consumer
     def _upload(self, pend):
@@ -523,6 +638,8 @@ class BatchFeeder:
         stage, dev = self._stage[pend.seq % self.depth], self._dev[pend.seq % (self.depth + 1)]
         if pend.records is not None:
             stage.records()[:len(pend.entries)] = pend.records
+        if pend.mix_table is not None:
+            stage.mix_records()[:len(pend.entries)] = pend.mix_table
         if pend.table is not None:
             stage.aug_table(pend.table.numel()).copy_(pend.table)
         if pend.band is not None:
@@ -568,6 +685,12 @@ class BatchFeeder:
             raise StopIteration
         seq, deadline = self._returned, time.monotonic() + self.timeout_s
         t0 = time.monotonic()
+        while not self._threads:                        # workers = 0: this thread reads, up to the end of batch seq
+            with self._cv:
+                job = self._take_row() if self._next_seq <= seq else None
+            if job is None:
+                break
+            self._read_row(*job)
         with self._cv:
             while True:
                 pend = self._pending.get(seq)
@@ -596,7 +719,8 @@ class BatchFeeder:
                                        f"{self.timeout_s:g} s")
                 time.sleep(1e-3)
         self.wait_upload_s += time.monotonic() - t1
-        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev, pend.windows, pend.records, pend.draws)
+        batch = PcmBatch(self, seq, pend.epoch, pend.entries, dev, pend.windows, pend.records, pend.draws, pend.mix,
+                         pend.noise)
         with self._cv:
             del self._pending[seq]
             self._returned = seq + 1                    # frees staging slot seq % depth; batch seq - depth goes stale

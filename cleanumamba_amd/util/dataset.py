@@ -12,6 +12,8 @@ Differences on the host side:
     to the model's rate to the device (csrc/pcm.hip, csrc/resample.hip).
   * the file-count assertions look at the directories the chosen layout reads (the reference always counts
     ``training_set``, also for ``subset="testing"``).
+  * ``SpeechNoiseDataset`` has no counterpart in the reference: two unpaired corpora, a tree of speech and a tree of
+    noise as the DNS challenge distributes them, for the feeder that mixes on the device (training/mix.py).
 The reference's import-time ``random.seed(0) / torch.manual_seed(0) / np.random.seed(0)`` is not repeated: importing a
 module here does not reseed the process.  Seed numpy's global generator to reproduce the reference's crops.
 """
@@ -260,6 +262,70 @@ class CleanNoisyPairDataset(Dataset):
 
     def __len__(self):
         return len(self.files)
+
+
+class SpeechNoiseDataset:
+    """Two unpaired corpora, as the DNS challenge distributes them: every ``*.wav`` below ``speech_root`` and every one
+    below ``noise_root``, each list sorted by relative path (so the order does not depend on the file system).  Only
+    16-bit mono PCM at ``sample_rate`` is taken: any other encoding or rate, an empty file or an empty root is a
+    ValueError here, naming the file and what it is.  There is no element access: training/feeder.py pairs speech with
+    fresh noise every epoch and training/mix.py (csrc/mix.hip) mixes them on the device.
+
+    ``len(ds)``: speech files;  ``n_noise``;  ``speech_files`` / ``noise_files``: the paths;  ``speech_length(i)``,
+    ``noise_length(j)``: samples, from the headers;  ``read_speech(i, start, count, out=None)``,
+    ``read_noise(j, start, count, out=None)``: that range as int16, reading nothing else (``out``: a writable int16
+    array of at least ``count`` elements to read into, e.g. a pinned staging row)."""
+
+    def __init__(self, speech_root, noise_root, crop_length_sec=10, sample_rate=16000):
+        self.crop_length_sec, self.sample_rate = crop_length_sec, int(sample_rate)
+        self._speech = self._scan(os.fspath(speech_root), "speech_root")
+        self._noise = self._scan(os.fspath(noise_root), "noise_root")
+        self.speech_files = [info.path for info in self._speech]
+        self.noise_files = [info.path for info in self._noise]
+
+    def _scan(self, root, what):
+        names = sorted((os.path.relpath(os.path.join(d, f), root) for d, _, files in os.walk(root) for f in files
+                        if f.lower().endswith(".wav")), key=lambda name: name.split(os.sep))
+        if not names:
+            raise ValueError(f"SpeechNoiseDataset: no *.wav file below {what} {root}")
+        infos = []
+        for name in names:
+            info = read_wav_info(os.path.join(root, name))
+            if not info.is_pcm16_mono:
+                raise ValueError(f"SpeechNoiseDataset: {info.path} is {info.describe()}; only 16-bit mono PCM is taken")
+            if info.rate != self.sample_rate:
+                raise ValueError(f"SpeechNoiseDataset: {info.path} is at {info.rate} Hz, not {self.sample_rate} "
+                                 "(other rates are not converted here)")
+            if info.frames < 1:
+                raise ValueError(f"SpeechNoiseDataset: {info.path} is empty")
+            infos.append(info)
+        return infos
+
+    def __len__(self):
+        return len(self._speech)
+
+    @property
+    def n_noise(self):
+        return len(self._noise)
+
+    def speech_length(self, i):
+        return self._speech[i].frames
+
+    def noise_length(self, j):
+        return self._noise[j].frames
+
+    @staticmethod
+    def _read(info, start, count, out):
+        start, count = int(start), int(count)
+        if start < 0 or count < 0 or start + count > info.frames:
+            raise ValueError(f"{info.path}: samples [{start}, {start + count}) are outside the file's {info.frames}")
+        return _read_range_int16(info, start, count, out)
+
+    def read_speech(self, i, start, count, out=None):
+        return self._read(self._speech[i], start, count, out)
+
+    def read_noise(self, j, start, count, out=None):
+        return self._read(self._noise[j], start, count, out)
 
 
 def load_CleanNoisyPairDataset(root="./", subset="training", dataset="dns", crop_length_sec=10, batch_size=1,

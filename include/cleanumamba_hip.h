@@ -1097,6 +1097,40 @@ int cum_reverb_pairs(const float *clean_src, int64_t clean_src_sb, const float *
                      const int32_t *rirs_host, const int32_t *rirs, int32_t n_rirs, float *workspace, float *clean,
                      int64_t clean_sb, float *noisy, int64_t noisy_sb, void *stream);
 
+/* ---- speech and noise mixed on the device (csrc/mix.hip; training/mix.py) -----------------------------
+ * cum_mix_pairs: the mixer of the DNS challenge's synthesiser in place of cum_pcm_batch_f32, for a feeder over two
+ *   unpaired corpora (the reference trains from pre-mixed pairs only, src/util/dataset.py:108-150): the noise scaled to
+ *   an SNR measured on the ACTIVE frames of both signals, the mixture brought to a level in dBFS, a guard against
+ *   clipping.  The scheme follows the synthesiser's; it has not been compared with its output.
+ *   pcm: 2 * batch rows, `pitch` int16 apart; row b is speech, row batch + b noise (cum_pcm_batch_f32's layout).
+ *   recs: device table, 12 int32 per row {n_speech, frame, thr (int64 in ints 2-3), q (f64 in ints 4-5), l (f64 in ints
+ *   6-7), clip (f32), 0, 0, 0}: q = 10^(snr_db / 10), l = 10^(level_db / 10) or NaN (keep the level), thr = floor(2^30
+ *   10^(activity_db / 10)), all formed on the host in double: the device evaluates no transcendental.
+ *   For row b, t < len:  S[t] = pcm[b][t mod n_s], n_s = n_speech clamped into [1, len];  N[t] = pcm[batch + b][t].
+ *     frames [k frame, min((k + 1) frame, len)), frame clamped into [1, len], thr into [0, 2^30]; per frame of m samples
+ *       es_k = sum S^2, en_k = sum N^2; over the row Ss = sum S^2, Snn = sum N^2, Ssn = sum S N: exact, in int64;
+ *       a frame is active iff e_k > thr m (integers)
+ *     Ps = (sum es_k over active frames) / (sum m over active frames), or Ss / len if no frame is active; Pn likewise (f64)
+ *     a = sqrt(Ps / (Pn q)) if Ps > 0, Pn > 0 and q is finite and positive, else 1;  a32 = (float) a
+ *     Em = (A Snn + 2 Ssn) A + Ss,  A = (double) a32  (f64, no fused operation)
+ *     g = sqrt(l len 2^30 / Em) if l is finite and Em > 0, else 1;  g32 = (float) g
+ *     m[t] = fmaf(a32, N[t] 2^-15, S[t] 2^-15),  peak = max_t |m[t]|  (f32)
+ *     if g32 peak > clip: g32 = clip / peak  (one f32 division)
+ *     clean[b clean_sb + t] = g32 (S[t] 2^-15),  noisy[b noisy_sb + t] = g32 m[t]
+ *   stats: NULL, or batch rows of 8 f32 {a32, g32 (as applied), Ps 2^-30, Pn 2^-30, peak, (sum m over active speech
+ *   frames) / len, the same of noise, 1.0 if the guard acted else 0.0}.
+ *   workspace: cum_mix_workspace_elems(batch, len) floats, 8-byte aligned (the workgroups' integer totals and the tiles'
+ *   peaks; written by the first two of the three launches, read by the last two).  No atomics, and every sum is an exact
+ *   integer: two runs give the same bits, and a row's result depends on its own record and samples only.  Nothing is
+ *   read behind len in a row of pcm, nothing written behind len in an output row.  Nothing is allocated, read on the
+ *   host or waited for.
+ *   CUM_EINVAL before any launch: batch outside [1, 32767], len < 1, pitch < len, pitch % 8 != 0, clean_sb or noisy_sb
+ *   below len, a null pointer (stats may be NULL), pcm / clean / noisy off a 16-byte boundary, workspace or recs off an
+ *   8-byte one, stats off a 4-byte one. */
+int64_t cum_mix_workspace_elems(int32_t batch, int64_t len);
+int cum_mix_pairs(const int16_t *pcm, int64_t pitch, const int32_t *recs, int32_t batch, int64_t len, void *workspace,
+                  float *clean, int64_t clean_sb, float *noisy, int64_t noisy_sb, float *stats, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
