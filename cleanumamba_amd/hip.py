@@ -75,6 +75,16 @@ class PruneMaskDesc(ctypes.Structure):
                 ("rows_fastest", c_i32), ("pad_", c_i32)]
 
 
+class DistillLayer(ctypes.Structure):
+    """cum_distill_layer (include/cleanumamba_hip.h): one layer's features, strides and BatchNorm buffers."""
+    _fields_ = [("e", ctypes.c_void_p), ("t", ctypes.c_void_p), ("de", ctypes.c_void_p),
+                ("rm_s", ctypes.c_void_p), ("rv_s", ctypes.c_void_p), ("rm_t", ctypes.c_void_p), ("rv_t", ctypes.c_void_p),
+                ("nbt_s", ctypes.c_void_p), ("nbt_t", ctypes.c_void_p),
+                ("e_sb", c_i64), ("e_st", c_i64), ("t_sb", c_i64), ("t_st", c_i64), ("de_sb", c_i64), ("de_st", c_i64),
+                ("B", c_i32), ("T", c_i32), ("C", c_i32), ("e_dtype", c_i32), ("t_dtype", c_i32),
+                ("momentum", ctypes.c_float), ("eps", ctypes.c_float), ("pad_", c_i32)]
+
+
 CUM_F32, CUM_BF16, CUM_F16 = 0, 1, 2
 HALF_TYPES = (torch.bfloat16, torch.float16)          # 16-bit element types the kernels read / write directly
 IO_TYPES = (torch.float32,) + HALF_TYPES
@@ -231,6 +241,9 @@ SIGNATURES = {
                                  _P]),
     "cum_mix_workspace_elems": (c_i64, [c_i32, c_i64]),
     "cum_mix_pairs": (c_i32, [_P, c_i64, _P, c_i32, c_i64, _P, _P, c_i64, _P, c_i64, _P, _P]),
+    "cum_distill_sizes": (c_i32, [ctypes.POINTER(DistillLayer), c_i32, ctypes.POINTER(c_i64)]),
+    "cum_distill_fwd": (c_i32, [ctypes.POINTER(DistillLayer), c_i32, ctypes.c_float, c_i32] + [_P] * 7),
+    "cum_distill_bwd": (c_i32, [ctypes.POINTER(DistillLayer), c_i32, ctypes.c_float] + [_P] * 5),
 }
 
 _lib = None

@@ -48,6 +48,17 @@ def decay_groups(net, weight_decay):
             {"params": [p for p in params if p.dim() < 2], "weight_decay": 0.0}]
 
 
+class _Trained(nn.Module):
+    """Student and adapters as ONE module for the optimizer and the flat storage.  The adapters register first: the flat
+    layout is the reverse of the registration order (training/flat_optim.py), so the student's parameters keep the
+    offsets they have on their own and the adapters' follow them."""
+
+    def __init__(self, student, adapters):
+        super().__init__()
+        self.adapters = adapters
+        self.student = student
+
+
 class TrainStep:
     """``step = TrainStep(net, ...); loss, grad_norm = step(clean, noisy)``, or ``step(batch)`` with a batch of
     training/feeder.BatchFeeder.
@@ -60,18 +71,43 @@ class TrainStep:
       the rest), as src/training/train.py:126-154; anything else raises ValueError.  Both on either optimizer route.
     flat_optimizer: None = on for fp32 CUDA models.  Off: torch.optim.Adam / AdamW + clip_grad_norm_ + GradScaler.
     use_graph: None = on for CUDA runs with the flat optimizer (one graph for one process; two graphs around an eager
-      whole-buffer all-reduce for several ranks, see the module docstring)."""
+      whole-buffer all-reduce for several ranks, see the module docstring).
+    distill: None, or ``(teacher, adapters)`` -- fine-tune ``net`` against ``teacher`` with the feature distillation loss
+      of src/util/util.py:259-290 (training/distill.py; ``adapters = make_adapters(net, teacher)``, weight
+      ``loss_config["kd_p"]``).  The teacher is put in eval mode, its parameters stop requiring grad and stay out of the
+      optimizer; the adapters' parameters train with the student's, behind them in the flat buffers (every offset of the
+      student's parameters is what it is without ``distill``).  The teacher's forward is part of the captured step.  One
+      process only.  Prune the student BEFORE building the adapters: an adapter that no longer fits raises."""
 
     def __init__(self, net, optimization=None, loss_config=None, autocast_dtype=None, iteration=0, repeats=1,
-                 flat_optimizer=None, use_graph=None):
+                 flat_optimizer=None, use_graph=None, distill=None):
         self.net = net
+        self.teacher = self.adapters = None
+        trained = net                    # the module whose parameters the optimizer owns
+        if distill is not None:
+            import torch.distributed as dist
+            from .distill import check_adapters
+            if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+                raise NotImplementedError("TrainStep(distill=...) runs in one process: the adapters' gradients have no "
+                                          "place in the bucketed exchange yet")
+            self.teacher, self.adapters = distill
+            check_adapters(net, self.adapters)
+            self.teacher.eval()
+            for p in self.teacher.parameters():
+                p.requires_grad_(False)
+            trained = _Trained(net, self.adapters)
+            flat_now = getattr(net, "grad_buckets", None)
+            if flat_now is not None and any(id(p) not in flat_now.flat.index for p in self.adapters.parameters()):
+                raise ValueError("TrainStep(distill=...): the student already has flat parameter storage without these "
+                                 "adapters (an earlier TrainStep); build the distillation step on a fresh model")
+        self.trained = trained
         self.opt_cfg = dict(DEFAULT_OPTIM, **(optimization or {}))
         self.loss_cfg = dict(DEFAULT_LOSS, **(loss_config or {}))
         self.repeats = int(repeats)
         dev = next(net.parameters()).device
         self.buckets = getattr(net, "grad_buckets", None)
         if flat_optimizer is None:
-            flat_optimizer = dev.type == "cuda" and all(p.dtype == torch.float32 for p in net.parameters())
+            flat_optimizer = dev.type == "cuda" and all(p.dtype == torch.float32 for p in trained.parameters())
         self.autocast_dtype = autocast_dtype
         fp16 = autocast_dtype == torch.float16
         self.scaler = None
@@ -83,10 +119,10 @@ class TrainStep:
             from .flat_optim import FlatAdam
             from .train_distributed import GradBuckets
             if self.buckets is None:          # single process: flat storage only, no exchange
-                self.buckets = net.grad_buckets = GradBuckets(net)
+                self.buckets = net.grad_buckets = GradBuckets(trained)
             grouped = {}
             if adamw:
-                grouped = dict(groups=decay_groups(net, self.opt_cfg["weight_decay"]), decoupled_weight_decay=True)
+                grouped = dict(groups=decay_groups(trained, self.opt_cfg["weight_decay"]), decoupled_weight_decay=True)
             self.optimizer = FlatAdam(self.buckets.flat, lr=self.opt_cfg["learning_rate"],
                                       betas=tuple(self.opt_cfg["betas"]), eps=self.opt_cfg["eps"],
                                       weight_decay=self.opt_cfg["weight_decay"],
@@ -94,11 +130,11 @@ class TrainStep:
         else:
             fused = bool(self.opt_cfg["fused_adam"]) and dev.type == "cuda"
             if adamw:
-                self.optimizer = torch.optim.AdamW(decay_groups(net, self.opt_cfg["weight_decay"]),
+                self.optimizer = torch.optim.AdamW(decay_groups(trained, self.opt_cfg["weight_decay"]),
                                                    lr=self.opt_cfg["learning_rate"], betas=tuple(self.opt_cfg["betas"]),
                                                    eps=self.opt_cfg["eps"], fused=fused)
             else:
-                self.optimizer = torch.optim.Adam(net.parameters(), lr=self.opt_cfg["learning_rate"],
+                self.optimizer = torch.optim.Adam(trained.parameters(), lr=self.opt_cfg["learning_rate"],
                                                   betas=tuple(self.opt_cfg["betas"]), eps=self.opt_cfg["eps"],
                                                   fused=fused, weight_decay=self.opt_cfg["weight_decay"])
             # fp16 autocast needs loss scaling (reference: GradScaler, train.py:158-160); bf16 does not
@@ -143,6 +179,8 @@ class TrainStep:
 
     def _loss(self, clean_audio, noisy_audio):
         kw = {k: v for k, v in self.loss_cfg.items() if k != "stft_config"}
+        if self.teacher is not None:
+            kw.update(teacher_net=self.teacher, student_teacher_adapter_layers=self.adapters)
         if self.autocast_dtype is not None:
             with torch.autocast(device_type="cuda", dtype=self.autocast_dtype):
                 return loss_fn(self.net, (clean_audio, noisy_audio), mrstftloss=self.mrstft, **kw)[0]
@@ -197,7 +235,8 @@ class TrainStep:
         if not ids:
             return None
         inside = [o for p, o in zip(fp.params, fp.offsets) if id(p) in ids]
-        outside = [o for p, o in zip(fp.params, fp.offsets) if id(p) not in ids]
+        behind = {id(p) for p in self.adapters.parameters()} if self.adapters is not None else set()   # (after the encoder)
+        outside = [o for p, o in zip(fp.params, fp.offsets) if id(p) not in ids and id(p) not in behind]
         if len(inside) != len(ids) or not outside or max(outside) >= min(inside):
             return None
         return min(inside)
@@ -209,11 +248,11 @@ class TrainStep:
             return self.optimizer.grad_norm
         if self.scaler is not None:
             self.scaler.unscale_(self.optimizer)
-            grad_norm = nn.utils.clip_grad_norm_(self.net.parameters(), self.opt_cfg["clip_grad_norm_max"])
+            grad_norm = nn.utils.clip_grad_norm_(self.trained.parameters(), self.opt_cfg["clip_grad_norm_max"])
             self.scaler.step(self.optimizer)
             self.scaler.update()
         else:
-            grad_norm = nn.utils.clip_grad_norm_(self.net.parameters(), self.opt_cfg["clip_grad_norm_max"])
+            grad_norm = nn.utils.clip_grad_norm_(self.trained.parameters(), self.opt_cfg["clip_grad_norm_max"])
             self.optimizer.step()
         return grad_norm
 

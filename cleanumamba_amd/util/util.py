@@ -3,8 +3,8 @@
 weight_scaling_init ........ src/util/util.py:174-181 (used by the model constructor)
 LinearWarmupCosineDecay .... src/util/util.py:69-161
 sampling ................... src/util/util.py:185-212 (blocks with carried state, not independent ones)
-loss_fn .................... src/util/util.py:215-327 (L1 + multi-resolution STFT; the
-                             cross-entropy / distillation branches are out of scope)
+loss_fn .................... src/util/util.py:215-327 (L1 + multi-resolution STFT, and the teacher / student feature
+                             distillation branch on training/distill.py; the cross-entropy branch is out of scope)
 """
 from math import cos, pi
 
@@ -103,17 +103,50 @@ def sampling(net, noisy_audio, split_sampling=False, block_size=1600):
     return net.denoise_long(noisy_audio, block_size)
 
 
+def _student_and_kd(net, teacher_net, adapters, kd_p, noisy_audio):
+    """loss_fn's teacher branch (src/util/util.py:262-288): -> (denoised audio, (kd_loss, [L_i]))."""
+    from ..training.distill import kd_feature_loss
+    if adapters is None:
+        raise ValueError("loss_fn: teacher_net needs student_teacher_adapter_layers (training/distill.py make_adapters)")
+    denoised_audio, skip_connections = net(noisy_audio, return_skip_connections=True)
+    with torch.no_grad():
+        _, teacher_skip_connections = teacher_net(noisy_audio, return_skip_connections=True)
+    return denoised_audio, kd_feature_loss(skip_connections, teacher_skip_connections, adapters, kd_p)
+
+
+def _add_kd(loss, output_dic, kd):
+    """The distillation term joins the loss (src/util/util.py:287-290); without a teacher nothing changes."""
+    if kd is None:
+        return loss, output_dic
+    kd_loss, kd_losses = kd
+    output_dic["kd_losses"] = [l.detach() for l in kd_losses]
+    output_dic["kd_loss"] = kd_loss.detach()
+    return loss + kd_loss, output_dic
+
+
 def loss_fn(net, X, cross_entropy=None, ell_p=1, ell_p_lambda=1, stft_lambda=1, mrstftloss=None, kd_p=1,
             min_max=(-1, 1), teacher_net=None, student_teacher_adapter_layers=None, **kwargs):
-    """loss = ell_p(denoised, clean) * ell_p_lambda + (sc + mag) * stft_lambda.
+    """loss = ell_p(denoised, clean) * ell_p_lambda + (sc + mag) * stft_lambda  [+ kd_loss].
 
-    X = (clean_audio, noisy_audio), both (B, 1, L).  Returns (loss, dict of components)."""
+    X = (clean_audio, noisy_audio), both (B, 1, L).  Returns (loss, dict of components).
+
+    teacher_net (src/util/util.py:259-290): the student runs with ``return_skip_connections=True``, the teacher under
+    ``no_grad``, and ``student_teacher_adapter_layers`` (training/distill.py make_adapters) turn every pair of features
+    into L_i = kd_p log sum (bn_s(embed(s_i)) - bn_t(t_i))^4; ``kd_loss = mean_i L_i`` joins the loss, and
+    ``output_dic["kd_losses"]`` / ``["kd_loss"]`` hold the detached values.  Student and teacher get the SAME input
+    tensor: in the reference the student's forward divides ``noisy_audio`` by its std in place (src/network/
+    CleanUMamba.py:262), so its teacher sees an already normalised input and normalises it again -- an accident of that
+    forward, which this project's forward (it does not mutate its argument) does not have."""
     assert type(X) == tuple and len(X) == 2
-    if cross_entropy or teacher_net is not None:
-        raise NotImplementedError("cross-entropy and distillation branches are outside the hot path")
+    if cross_entropy:
+        raise NotImplementedError("the cross-entropy branch is outside the hot path")
     clean_audio, noisy_audio = X
     output_dic = {}
-    denoised_audio = net(noisy_audio)
+    kd = None
+    if teacher_net is None:
+        denoised_audio = net(noisy_audio)
+    else:
+        denoised_audio, kd = _student_and_kd(net, teacher_net, student_teacher_adapter_layers, kd_p, noisy_audio)
     if ell_p not in (1, 2):
         raise NotImplementedError
     plain = (denoised_audio.is_cuda and clean_audio.is_cuda and denoised_audio.shape == clean_audio.shape
@@ -142,7 +175,7 @@ def loss_fn(net, X, cross_entropy=None, ell_p=1, ell_p_lambda=1, stft_lambda=1, 
                 (0.0,) + tuple(sc_w), (0.0,) + tuple(mag_w))                            # "stft_sc", "stft_mag"
         out = _Combine.apply(rows, ae_loss, *[t for pair in pairs for t in pair])
         output_dic["reconstruct"], output_dic["stft_sc"], output_dic["stft_mag"] = out[1].detach(), out[2].detach(), out[3].detach()
-        return out[0], output_dic
+        return _add_kd(out[0], output_dic, kd)
     loss = ae_loss * ell_p_lambda
     output_dic["reconstruct"] = ae_loss.data * ell_p_lambda
     if stft_lambda > 0:
@@ -150,4 +183,4 @@ def loss_fn(net, X, cross_entropy=None, ell_p=1, ell_p_lambda=1, stft_lambda=1, 
         loss = loss + (sc_loss + mag_loss) * stft_lambda
         output_dic["stft_sc"] = sc_loss.data * stft_lambda
         output_dic["stft_mag"] = mag_loss.data * stft_lambda
-    return loss, output_dic
+    return _add_kd(loss, output_dic, kd)

@@ -1131,6 +1131,53 @@ int64_t cum_mix_workspace_elems(int32_t batch, int64_t len);
 int cum_mix_pairs(const int16_t *pcm, int64_t pitch, const int32_t *recs, int32_t batch, int64_t len, void *workspace,
                   float *clean, int64_t clean_sb, float *noisy, int64_t noisy_sb, float *stats, void *stream);
 
+/* ---- teacher / student feature distillation loss (csrc/distill.hip; training/distill.py) ---------------
+ * The teacher branch of the reference's loss_fn (src/util/util.py:259-290, after arXiv:2303.11098): per layer the
+ * embedded student feature e and the teacher feature t go through BatchNorm1d(affine=False) in training mode
+ * (ad["bn_s"], ad["bn_t"], :276-279), d = s^ - t^, D = sum d^4, L = kd_p log D (:281-284).  The ~15 elementwise and
+ * reduction passes of that chain, and the four full-size tensors its autograd keeps, become three streaming passes over
+ * e and t for ALL layers at once, each one launch over work items (layer, chunk of CUM_DISTILL_ROWS rows) plus one small
+ * launch that merges the chunks' partial results in a fixed order (no atomics: two runs give the same bits):
+ *   stats  per chunk and channel (mean, M2) of e and t (Welford per lane, Chan's merge through LDS and over the chunks,
+ *          the latter in f64; every value relative to its chunk's first row, so features far from zero keep their digits)
+ *          -> cst[ch] = {mean_e hi, lo, rstd_e, 0, mean_t hi, lo, rstd_t, 0}, rstd = 1 / sqrt(M2 / n + eps), n = B T; and
+ *          the modules' training-mode side effects: running_mean = (1 - momentum) running_mean + momentum mean,
+ *          running_var likewise with M2 / (n - 1), num_batches_tracked += 1 (pointers may be NULL: no update).
+ *   loss   s^ = ((e - hi) - lo) rstd_e, t^ likewise, d = s^ - t^: per chunk sum d^4 and per channel sum d^3, sum d^3 s^
+ *          -> csum[ch] = {sum d^3, sum d^3 s^} (f64), D[layer] (f64), L[layer] = kd_p log D[layer].
+ *   bwd    de = rstd_e a (d^3 - csum[0] / n - s^ csum[1] / n), a = (float)(4 kd_p / D) G[layer] formed in f32, written in
+ *          e's element type to de (C rounded up to 8 columns per row, the columns past C and, where de_sb > T de_st, the
+ *          rows between clips written as zeros).  G: device f32, the upstream gradient of every L[layer].  Nothing flows
+ *          to t.
+ * A layer's e and t are (B, T, C) with element strides (sb, st, 1): views of the conv stack's row buffers (st = C rounded
+ * up to 8, sb = (T + 2) st) or contiguous tensors.  Elements past column C of a row and rows past T of a clip are never
+ * added into a sum.  16-byte loads are used where a side's base is 16-byte aligned and st, sb are multiples of 8 elements
+ * with st >= C rounded up to 8; other layouts are read element by element.  e_dtype, t_dtype: CUM_F32 / CUM_BF16 /
+ * CUM_F16; de has e's.  All arithmetic is f32 or f64.
+ * cum_distill_sizes: sizes[0] = f32 elements of `part`, sizes[1] = channels over all layers (cst holds 8 f32, csum 2 f64
+ *   per channel), sizes[2] = chunks over all layers (s4 holds one f32 per chunk).  D and L hold one value per layer.
+ * cum_distill_fwd: passes & 1 runs stats, passes & 2 runs loss (which reads what stats left in cst).
+ * CUM_EINVAL before any launch: n_layers outside [1, CUM_DISTILL_MAX_LAYERS], a layer with B, T or C < 1, B T < 2 or
+ * B T >= 2^31, a stride below what (T, C) need, an unknown dtype, a null e / t (de for cum_distill_bwd) or workspace. */
+#define CUM_DISTILL_MAX_LAYERS 16
+#define CUM_DISTILL_ROWS 256
+typedef struct {
+  const void *e, *t;
+  void *de;
+  float *rm_s, *rv_s, *rm_t, *rv_t;       /* running_mean / running_var of bn_s and bn_t, or NULL */
+  int64_t *nbt_s, *nbt_t;                 /* num_batches_tracked of bn_s and bn_t, or NULL */
+  int64_t e_sb, e_st, t_sb, t_st, de_sb, de_st;
+  int32_t B, T, C;
+  int32_t e_dtype, t_dtype;
+  float momentum, eps;
+  int32_t pad_;
+} cum_distill_layer;
+int cum_distill_sizes(const cum_distill_layer *layers, int32_t n_layers, int64_t *sizes);
+int cum_distill_fwd(const cum_distill_layer *layers, int32_t n_layers, float kd_p, int32_t passes, float *part, float *cst,
+                    double *csum, float *s4, double *D, float *L, void *stream);
+int cum_distill_bwd(const cum_distill_layer *layers, int32_t n_layers, float kd_p, const float *cst, const double *csum,
+                    const double *D, const float *G, void *stream);
+
 #ifdef __cplusplus
 }
 #endif
