@@ -8,6 +8,9 @@
 //   cum_rows_zero_tail       <- the rows a clip does not have when it runs alone: the GLU output of a decoder layer
 //                               (CleanUMamba.py:121-130) past the clip's own row count is cleared
 //   cum_unframe_rows_ragged  <- x[:, :, :L] * std of every clip (CleanUMamba.py:319), zeros behind L
+//   cum_unframe_rows_ragged_pcm16  the same crop, quantised to int16 into one flat buffer (the layout of the metric
+//                               kernels, csrc/metrics.hip): validate's `(y * 32767).clamp(..).to(int16)` on the device
+//   cum_pcm16_from_f32_ragged   the same quantisers on f32 rows (the output of cum_resample_ragged)
 //
 // Rows arrive as the files hold them (int16 PCM, scaled by 2^-15: exact in f32) or as f32.  `len` / `valid` are device
 // i32 tables, clamped inside the kernels: a bad table never indexes outside a row.  All four move bytes and do nothing
@@ -203,6 +206,73 @@ __global__ __launch_bounds__(RT) void unframe_rows_ragged_kernel(const T *__rest
   }
 }
 
+// ---------------------------------------------------------------- f32 values -> int16 PCM in ONE flat buffer
+// The two quantisers of util/denoise_eval.py, each one f32 product rounded once and then a conversion:
+//   mode 0  (y * 32767).clamp(-32768, 32767).to(int16): truncation toward zero (validate's denoised signal)
+//   mode 1  (y * 32768).round().clamp(-32768, 32767):   round half to even (validate's converted clean signal)
+// NaN gives 0 in both modes; +-inf clamps to 32767 / -32768.
+__device__ __forceinline__ int16_t rg_quant(float v, int mode) {
+  float w = mode == 0 ? v * 32767.f : rintf(v * 32768.f);
+  if (!(w == w)) return 0;
+  w = fminf(fmaxf(w, -32768.f), 32767.f);
+  return (int16_t)(int)w;                        // w is finite here; mode 0 truncates, mode 1 is already an integer
+}
+
+// Clip b's n samples go to dst = out + off[b], which may start at any 2-byte position.  Chunk 0 is the head: the
+// `head` samples in front of the first 16-byte boundary of dst; chunk c >= 1 is the 8 samples [head + 8 (c - 1), ...)
+// behind it -- one 16-byte store where it is whole, 2-byte stores for the head and the tail.  `get(t)` is sample t as
+// f32.  Nothing outside [dst, dst + n) is written.
+template <typename Get>
+__device__ __forceinline__ void rg_store_pcm16(int16_t *__restrict__ dst, int64_t n, int mode, Get get) {
+  int64_t head = (int64_t)((16 - (reinterpret_cast<uintptr_t>(dst) & 15)) & 15) / 2;
+  head = head > n ? n : head;
+  const int64_t chunks = 1 + (n - head + 7) / 8;
+  for (int64_t c = (int64_t)blockIdx.x * RT + threadIdx.x; c < chunks; c += (int64_t)gridDim.x * RT) {
+    const int64_t t0 = c == 0 ? 0 : head + 8 * (c - 1);
+    const int64_t t1 = c == 0 ? head : (t0 + 8 < n ? t0 + 8 : n);
+    if (c > 0 && t1 - t0 == 8) {
+      rg_short8 q;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) q[j] = rg_quant(get(t0 + j), mode);
+      *reinterpret_cast<rg_short8 *>(dst + t0) = q;
+    } else {
+      for (int64_t t = t0; t < t1; ++t) dst[t] = rg_quant(get(t), mode);
+    }
+  }
+}
+
+// grid (workgroups along the clip, B): cum_unframe_rows_ragged with the quantising store.
+template <typename T>
+__global__ __launch_bounds__(RT) void unframe_rows_ragged_pcm16_kernel(const T *__restrict__ rows, int64_t Lmax, int64_t Tn,
+                                                                      const int32_t *__restrict__ len,
+                                                                      const float *__restrict__ s, int mode,
+                                                                      int16_t *__restrict__ out,
+                                                                      const int64_t *__restrict__ off) {
+  const int b = blockIdx.y;
+  int64_t n = len[b];
+  n = n < 0 ? 0 : (n > Lmax ? Lmax : n);
+  n = n > Tn ? Tn : n;
+  const int64_t o = off[b];
+  if (o < 0) return;
+  const float sc = s ? s[b] : 1.f;
+  const T *__restrict__ src = rows + (1 + (int64_t)b * (Tn + 2)) * 8;
+  rg_store_pcm16(out + o, n, mode, [&](int64_t t) { return (float)src[t * 8] * sc; });
+}
+
+// grid (workgroups along the clip, B): f32 rows `stride` apart (the output of cum_resample_ragged) -> the flat buffer.
+__global__ __launch_bounds__(RT) void pcm16_from_f32_ragged_kernel(const float *__restrict__ x, int64_t Lmax, int64_t stride,
+                                                                  const int32_t *__restrict__ len, int mode,
+                                                                  int16_t *__restrict__ out,
+                                                                  const int64_t *__restrict__ off) {
+  const int b = blockIdx.y;
+  int64_t n = len[b];
+  n = n < 0 ? 0 : (n > Lmax ? Lmax : n);
+  const int64_t o = off[b];
+  if (o < 0) return;
+  const float *__restrict__ row = x + (int64_t)b * stride;
+  rg_store_pcm16(out + o, n, mode, [&](int64_t t) { return row[t]; });
+}
+
 static unsigned rg_grid(int64_t items) {
   int64_t g = (items + RT - 1) / RT;
   return (unsigned)(g < 1 ? 1 : (g > 256 ? 256 : g));
@@ -306,6 +376,53 @@ extern "C" int cum_unframe_rows_ragged(int32_t dtype, const void *rows, int32_t 
     hipLaunchKernelGGL(unframe_rows_ragged_kernel<__bf16>, g, b, 0, st, (const __bf16 *)rows, lmax, T, len, scale, y);
   else
     hipLaunchKernelGGL(unframe_rows_ragged_kernel<f16>, g, b, 0, st, (const f16 *)rows, lmax, T, len, scale, y);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+#define RG_PCM16_TABLES_OK(len, out, off)                                                            \
+  ((reinterpret_cast<uintptr_t>(len) & 3) == 0 && (reinterpret_cast<uintptr_t>(out) & 1) == 0 &&     \
+   (reinterpret_cast<uintptr_t>(off) & 7) == 0)
+
+extern "C" int cum_unframe_rows_ragged_pcm16(int32_t dtype, const void *rows, int32_t batch, int64_t lmax, int64_t T,
+                                             const int32_t *len, const float *scale, int32_t mode, int16_t *out_i16,
+                                             const int64_t *out_offset, void *stream) {
+  CUM_REQUIRE(dtype_ok(dtype), "unframe_rows_ragged_pcm16: bad dtype");
+  CUM_REQUIRE(RG_BATCH_OK(batch), "unframe_rows_ragged_pcm16: batch must be in [1, 65534]");
+  CUM_REQUIRE(lmax >= 1, "unframe_rows_ragged_pcm16: lmax must be at least 1");
+  CUM_REQUIRE(T >= lmax, "unframe_rows_ragged_pcm16: T must be at least lmax");
+  CUM_REQUIRE(mode == 0 || mode == 1, "unframe_rows_ragged_pcm16: mode must be 0 (x 32767, truncate) or 1 (x 32768, round)");
+  CUM_REQUIRE(rows && len && out_i16 && out_offset, "unframe_rows_ragged_pcm16: null pointer");
+  CUM_REQUIRE((reinterpret_cast<uintptr_t>(rows) & 15) == 0, "unframe_rows_ragged_pcm16: rows must be 16-byte aligned");
+  CUM_REQUIRE(RG_PCM16_TABLES_OK(len, out_i16, out_offset) && (reinterpret_cast<uintptr_t>(scale) & 3) == 0,
+              "unframe_rows_ragged_pcm16: len, scale, out_i16 or out_offset is misaligned");
+  hipStream_t st = (hipStream_t)stream;
+  const dim3 g(rg_grid((lmax + 7) / 8 + 1), (unsigned)batch), b(RT);
+  if (dtype == CUM_F32)
+    hipLaunchKernelGGL(unframe_rows_ragged_pcm16_kernel<float>, g, b, 0, st, (const float *)rows, lmax, T, len, scale, mode,
+                       out_i16, out_offset);
+  else if (dtype == CUM_BF16)
+    hipLaunchKernelGGL(unframe_rows_ragged_pcm16_kernel<__bf16>, g, b, 0, st, (const __bf16 *)rows, lmax, T, len, scale,
+                       mode, out_i16, out_offset);
+  else
+    hipLaunchKernelGGL(unframe_rows_ragged_pcm16_kernel<f16>, g, b, 0, st, (const f16 *)rows, lmax, T, len, scale, mode,
+                       out_i16, out_offset);
+  CUM_CHECK_LAUNCH();
+  return CUM_OK;
+}
+
+extern "C" int cum_pcm16_from_f32_ragged(const float *x, int32_t batch, int64_t lmax, int64_t stride, const int32_t *len,
+                                         int32_t mode, int16_t *out_i16, const int64_t *out_offset, void *stream) {
+  CUM_REQUIRE(RG_BATCH_OK(batch), "pcm16_from_f32_ragged: batch must be in [1, 65534]");
+  CUM_REQUIRE(lmax >= 1, "pcm16_from_f32_ragged: lmax must be at least 1");
+  CUM_REQUIRE(stride >= lmax, "pcm16_from_f32_ragged: stride must be at least lmax");
+  CUM_REQUIRE(mode == 0 || mode == 1, "pcm16_from_f32_ragged: mode must be 0 (x 32767, truncate) or 1 (x 32768, round)");
+  CUM_REQUIRE(x && len && out_i16 && out_offset, "pcm16_from_f32_ragged: null pointer");
+  CUM_REQUIRE(RG_PCM16_TABLES_OK(len, out_i16, out_offset) && (reinterpret_cast<uintptr_t>(x) & 3) == 0,
+              "pcm16_from_f32_ragged: x, len, out_i16 or out_offset is misaligned");
+  const dim3 g(rg_grid((lmax + 7) / 8 + 1), (unsigned)batch), b(RT);
+  hipLaunchKernelGGL(pcm16_from_f32_ragged_kernel, g, b, 0, (hipStream_t)stream, x, lmax, stride, len, mode, out_i16,
+                     out_offset);
   CUM_CHECK_LAUNCH();
   return CUM_OK;
 }

@@ -16,6 +16,10 @@ reference does.  Differences from the reference, on purpose:
     the rate (torchaudio.load's second result is dropped, src/util/dataset.py:203) and so denoises such a file at the
     wrong rate.  With ``resample=True`` (``--resample``) such a file is converted to 16000 Hz on the GPU, denoised,
     converted back and written at its own rate and its own length (util/resample.py, DESIGN.md 7g);
+  * ``pcm16=True`` (``--pcm16``) writes (and returns) int16 PCM instead of float32: the last kernel of each forward
+    quantises on the device, ``(y * 32768)`` rounded half to even and clamped (``denoise_batch_pcm16(mode=1)``), and
+    the samples are downloaded as int16, half the bytes.  With ``resample=True`` the quantisation follows the conversion
+    back to the file's own rate.  The default stays float32;
   * no ``torchinfo`` model summary is printed and there is no ``tqdm`` bar.
 """
 import argparse
@@ -27,7 +31,7 @@ import numpy as np
 import torch
 
 from ..network import convstack as cs
-from ..network.ragged import PCM_SCALE, plan_batches
+from ..network.ragged import PCM_SCALE, pcm16_from_f32_ragged, plan_batches
 from ..util.dataset import WAVE_FORMAT_PCM, NosyOnlyDataset, _read_whole_float
 from ..util.resample import out_length, plan as resample_plan
 from .loading_pretrained_models import load_pretrained_CleanUMamba
@@ -73,8 +77,21 @@ def _clip_f32(row):
     return row.to(torch.float32) * PCM_SCALE if row.dtype == torch.int16 else row
 
 
+def _quantise(cleans, device, mode=1):
+    """1-D f32 clips (host or device) -> their int16 PCM as host arrays: one quantising launch into one flat device
+    buffer (``pcm16_from_f32_ragged``), one int16 download."""
+    lens = np.array([int(c.shape[0]) for c in cleans], np.int64)
+    offsets = np.cumsum(lens) - lens
+    rows = torch.nn.utils.rnn.pad_sequence([c.to(device) for c in cleans], batch_first=True).contiguous()
+    flat = torch.empty(int(lens.sum()), dtype=torch.int16, device=device)
+    pcm16_from_f32_ragged(rows, torch.from_numpy(lens.astype(np.int32)).to(device), flat,
+                          torch.from_numpy(offsets).to(device), mode)
+    host = flat.cpu()
+    return [host[o:o + n] for o, n in zip(offsets.tolist(), lens.tolist())]
+
+
 def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batch=32, budget_samples=32 * 160000,
-            autocast_dtype=None, resample=False):
+            autocast_dtype=None, resample=False, pcm16=False):
     """
     Denoise audio
 
@@ -86,6 +103,8 @@ def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batc
     autocast_dtype:                 torch.float16 / torch.bfloat16 to run under autocast, None for float32
     resample:                       take files at any sample rate: each is converted to the model's rate, denoised,
                                     converted back and written (and returned) at its own rate and length
+    pcm16:                          write (and return as all_cleaned_audio) int16 PCM, quantised on the device by
+                                    ``(y * 32768).round().clamp(-32768, 32767)``, instead of float32
     """
     dataset = NosyOnlyDataset(folder=input_directory)
     rates = [dataset.info(n).rate for n in range(len(dataset))]
@@ -120,7 +139,13 @@ def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batc
             # the next batch is read while the device runs this one
             staged = _stage(dataset, batches[k + 1].indices, pool) if k + 1 < len(batches) else None
             brates = [rates[n] for n in batch.indices]
-            if all(r == SAMPLE_RATE for r in brates):
+            if pcm16 and all(r == SAMPLE_RATE for r in brates):
+                # the batch as planned (its clips alone plan into the same one batch), quantised by its last kernel
+                flat, offs, _ = model.denoise_batch_pcm16([stage[b, :lens[b]] for b in range(len(lens))], mode=1,
+                                                          max_batch=max_batch, budget_samples=budget_samples)
+                flat = flat.cpu()                                          # int16: half the bytes of the f32 result
+                cleans = [flat[o:o + n] for o, n in zip(offs.tolist(), lens)]
+            elif all(r == SAMPLE_RATE for r in brates):
                 if batch.long:
                     clean = model.denoise_batch([stage[0, :lens[0]]], max_batch=max_batch, budget_samples=budget_samples)[0]
                     clean = clean.view(1, 1, -1)
@@ -132,9 +157,11 @@ def denoise(checkpoint_path, input_directory, output_directory=None, *, max_batc
             elif batch.long:                                               # host in, host out: a piece at a time
                 cleans = [model.denoise_long(_clip_f32(stage[0, :lens[0]]).view(1, -1), rate=brates[0])[0, 0]]
             else:
-                cleans = [c.cpu() for c in model.denoise_batch([stage[b, :lens[b]] for b in range(len(lens))],
-                                                               max_batch=max_batch, budget_samples=budget_samples,
-                                                               rates=brates)]
+                cleans = model.denoise_batch([stage[b, :lens[b]] for b in range(len(lens))], max_batch=max_batch,
+                                             budget_samples=budget_samples, rates=brates)
+                cleans = cleans if pcm16 else [c.cpu() for c in cleans]    # (quantised below, where they are)
+            if pcm16 and cleans[0].dtype != torch.int16:                   # converted back to the files' rates first
+                cleans = _quantise(cleans, device)
             for b, n in enumerate(batch.indices):
                 noisy = stage[b, :lens[b]].numpy()
                 noisy = noisy.astype(np.float32) * np.float32(PCM_SCALE) if noisy.dtype == np.int16 else noisy.copy()
@@ -156,8 +183,11 @@ if __name__ == "__main__":
                         help='Output folder path to save the audio to')
     parser.add_argument('--max_batch', type=int, default=32, help='Most files in one forward')
     parser.add_argument('--autocast', choices=['f16', 'bf16'], default=None, help='Run under autocast in this type')
+    parser.add_argument('--pcm16', action='store_true',
+                        help='Write int16 PCM (quantised on the GPU, round half to even) instead of float32')
     parser.add_argument('--resample', action='store_true',
                         help='Take files at any sample rate: convert to 16000 Hz, denoise, write at the file\'s own rate')
     args = parser.parse_args()
     denoise(args.checkpoint_path, args.input_directory, args.output_directory, max_batch=args.max_batch,
-            autocast_dtype={None: None, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.autocast], resample=args.resample)
+            autocast_dtype={None: None, 'f16': torch.float16, 'bf16': torch.bfloat16}[args.autocast], resample=args.resample,
+            pcm16=args.pcm16)

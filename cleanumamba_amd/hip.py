@@ -219,6 +219,8 @@ SIGNATURES = {
     "cum_frame_rows_ragged": (c_i32, [c_i32, c_i32, _P, c_i32, c_i64, c_i64, _P, c_i64, c_i64, _P, _P, _P]),
     "cum_rows_zero_tail": (c_i32, [c_i32, _P, c_i32, c_i64, c_i32, _P, _P]),
     "cum_unframe_rows_ragged": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, _P, _P, _P]),
+    "cum_unframe_rows_ragged_pcm16": (c_i32, [c_i32, _P, c_i32, c_i64, c_i64, _P, _P, c_i32, _P, _P, _P]),
+    "cum_pcm16_from_f32_ragged": (c_i32, [_P, c_i32, c_i64, c_i64, _P, c_i32, _P, _P, _P]),
     "cum_dech_fwd_ragged": (c_i32, [c_i32, c_i64, c_i32, c_i32, _P, c_i32, _P, c_i64, _P, _P, _P, _P, _P, _P, c_i64, _P]),
     "cum_dec7_fwd_ragged": (c_i32, [c_i32, c_i64, c_i32, c_i32, _P, c_i32, _P, _P, _P, _P, _P, _P, c_i64, _P]),
     "cum_resample_tile": (c_i32, []),

@@ -393,12 +393,21 @@ class CleanUMamba(nn.Module):
         return denoise_long(self, noisy, block_size=block_size, block_hops=block_hops, rate=rate, model_rate=model_rate)
 
     # ------------------------------------------------------------ ragged batches
-    def forward_ragged(self, x, lengths):
+    def forward_ragged(self, x, lengths, pcm16=None):
         """``forward`` on a batch of clips of DIFFERENT lengths in one pass (network/ragged.py).  x: (B, Lmax) int16 PCM, or
         (B, 1, Lmax) / (B, Lmax) f32, on the GPU, clip b in its first lengths[b] samples; lengths: a host sequence or a
-        device i32 tensor.  -> (B, 1, Lmax) f32: clip b's ``forward`` in [b, 0, :lengths[b]], zeros behind.  no_grad only."""
+        device i32 tensor.  -> (B, 1, Lmax) f32: clip b's ``forward`` in [b, 0, :lengths[b]], zeros behind.  no_grad only.
+        pcm16 = (flat int16 device buffer, device i64[B] sample offsets, mode): clip b is quantised into
+        flat[offsets[b] : offsets[b] + lengths[b]] instead (mode 0: * 32767, truncated; 1: * 32768, rounded) -> None."""
         from .ragged import forward_ragged
-        return forward_ragged(self, x, lengths)
+        return forward_ragged(self, x, lengths, pcm16=pcm16)
+
+    def denoise_batch_pcm16(self, clips, mode=0, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+        """``denoise_batch`` into ONE flat int16 device buffer (network/ragged.py): -> (flat, offsets, lengths), clip i
+        at flat[offsets[i] : offsets[i] + lengths[i]], quantised on the device by ``mode``."""
+        from .ragged import denoise_batch_pcm16
+        return denoise_batch_pcm16(self, clips, mode=mode, max_batch=max_batch, budget_samples=budget_samples,
+                                   max_waste=max_waste)
 
     def denoise_batch(self, clips, max_batch=32, budget_samples=32 * 160000, max_waste=0.25, rates=None, model_rate=16000):
         """[model(c[None, None])[0, 0, :len(c)] for c in clips] for a list of 1-D clips (int16 PCM or f32, host or device)

@@ -15,10 +15,13 @@ makes.
   forward_ragged    one padded batch: per-clip std, framing, the masked decoder, per-clip crop (csrc/ragged.hip)
   denoise_batch     a list of clips of any lengths -> their denoised versions, in order; with ``rates`` each clip at
                     its own sample rate (converted to the model's and back by util/resample.py)
+  denoise_batch_pcm16  the same plan and forwards, quantised on the device into one flat int16 buffer (the layout
+                    util/metrics.py scores): nothing of the audio comes back to the host
 """
 import collections
 import ctypes
 
+import numpy as np
 import torch
 
 from .. import hip
@@ -149,7 +152,46 @@ def unframe_ragged(buf, geo, lens, std, Lmax):
     return y
 
 
-def forward_ragged(model, x, lengths):
+def _check_flat(flat, offsets, B, what):
+    if not (torch.is_tensor(flat) and flat.is_cuda and flat.dtype == torch.int16 and flat.dim() == 1
+            and flat.is_contiguous()):
+        raise ValueError(f"{what}: the flat buffer must be a contiguous 1-D int16 tensor on the GPU")
+    if not (torch.is_tensor(offsets) and offsets.device == flat.device and offsets.dtype == torch.int64
+            and offsets.shape == (B,) and offsets.is_contiguous()):
+        raise ValueError(f"{what}: offsets must be a contiguous int64[{B}] tensor on the flat buffer's device")
+
+
+def unframe_ragged_pcm16(buf, geo, lens, std, Lmax, flat, offsets, mode):
+    """Row buffer of the 1-channel output -> int16 PCM in ``flat``: clip b's rows * std, quantised by ``mode`` (0:
+    * 32767, truncated; 1: * 32768, rounded half to even), at flat[offsets[b] : offsets[b] + lens[b]] (device i64[B])."""
+    _check_flat(flat, offsets, geo.B, "unframe_ragged_pcm16")
+    with torch.cuda.device(buf.device):
+        hip.check(hip.lib().cum_unframe_rows_ragged_pcm16(hip.dtype_code(buf.dtype), hip.ptr(buf), geo.B, Lmax, geo.T,
+                                                          hip.ptr(lens), hip.ptr(std), int(mode), hip.ptr(flat),
+                                                          hip.ptr(offsets), hip.stream_ptr()))
+
+
+def pcm16_from_f32_ragged(x, lens, flat, offsets, mode):
+    """(B, pitch) f32 device rows (``resample_ragged``'s output), device i32[B] lengths -> int16 PCM in ``flat`` at the
+    device i64[B] sample offsets, quantised by ``mode`` as ``unframe_ragged_pcm16`` does."""
+    if not (x.is_cuda and x.dtype == torch.float32 and x.dim() == 2 and x.stride(1) == 1):
+        raise ValueError("pcm16_from_f32_ragged takes (B, pitch) float32 rows on the GPU")
+    B, Lmax = x.shape
+    _check_flat(flat, offsets, B, "pcm16_from_f32_ragged")
+    with torch.cuda.device(x.device):
+        hip.check(hip.lib().cum_pcm16_from_f32_ragged(hip.ptr(x), B, Lmax, x.stride(0), hip.ptr(lens), int(mode),
+                                                      hip.ptr(flat), hip.ptr(offsets), hip.stream_ptr()))
+
+
+def ragged_supported(model):
+    """What ``forward_ragged`` needs of a model: the fused conv stack and one output channel."""
+    return bool(getattr(model, "use_fused_convs", True)) and hasattr(model, "encoder_n_layers") and cs.supported(model) \
+        and model.channels_output == 1
+
+
+def forward_ragged(model, x, lengths, pcm16=None):
+    """pcm16 = (flat int16 device buffer, device i64[B] sample offsets, mode): the last step quantises each clip into
+    ``flat`` (``unframe_ragged_pcm16``) and nothing is returned; None: the (B, 1, Lmax) f32 result."""
     if torch.is_grad_enabled():
         raise RuntimeError("forward_ragged is inference only: call it under torch.no_grad()")
     x2 = _rows2d(x)
@@ -165,6 +207,10 @@ def forward_ragged(model, x, lengths):
     if len(lengths) != B:
         raise ValueError(f"forward_ragged: {len(lengths)} lengths for {B} clips")
     _check_lengths(lengths, model.normalize_input, Lmax)
+    if pcm16 is not None:                        # before any launch
+        _check_flat(pcm16[0], pcm16[1], B, "forward_ragged")
+        if pcm16[2] not in (0, 1):
+            raise ValueError("forward_ragged: pcm16 mode must be 0 (* 32767, truncated) or 1 (* 32768, rounded)")
     E = model.encoder_n_layers
     tables = RaggedTables(lengths, Lmax, E, model.kernel_size, model.stride, x2.device)
     std = clip_std_ragged(x2, tables.len, 1e-3) if model.normalize_input else None
@@ -174,6 +220,10 @@ def forward_ragged(model, x, lengths):
     with cs.small_m_gemms():                     # as ``forward`` without grad
         buf, geo, _, _ = model._forward_fused(buf, B, T0, dt, ragged=tables)
     model.__dict__["_ragged_routes"] = tables.routes
+    if pcm16 is not None:
+        flat, offsets, mode = pcm16
+        unframe_ragged_pcm16(buf, geo, tables.len, std, Lmax, flat, offsets, mode)
+        return None
     return unframe_ragged(buf, geo, tables.len, std, Lmax)
 
 
@@ -234,14 +284,64 @@ def denoise_batch(model, clips, max_batch=32, budget_samples=32 * 160000, max_wa
     return out
 
 
-def _resample_group(clips, rate_in, rate_out, device, max_batch):
+def denoise_batch_pcm16(model, clips, mode=0, max_batch=32, budget_samples=32 * 160000, max_waste=0.25):
+    """``denoise_batch`` whose result stays on the device as int16 PCM: the same plan, the same staging and the same
+    forwards, every batch quantised by its last kernel (``mode`` 0: * 32767, clamped, truncated -- validate's rule; 1:
+    * 32768, rounded half to even, clamped) into ONE flat int16 device buffer, clips packed back to back in the caller's
+    order -- the layout of util/metrics.py ``Batch``.  -> (flat, offsets, lengths): the buffer and two host int64 arrays;
+    clip i is flat[offsets[i] : offsets[i] + lengths[i]].  A clip over the budget goes through ``denoise_long`` and is
+    quantised by ``pcm16_from_f32_ragged``."""
+    if torch.is_grad_enabled():
+        with torch.no_grad():
+            return denoise_batch_pcm16(model, clips, mode, max_batch, budget_samples, max_waste)
+    clips = list(clips)
+    for c in clips:
+        if not torch.is_tensor(c) or c.dim() != 1 or c.dtype not in (torch.int16, torch.float32):
+            raise ValueError("denoise_batch_pcm16 takes 1-D int16 or float32 tensors")
+    if mode not in (0, 1):
+        raise ValueError("denoise_batch_pcm16: mode must be 0 (* 32767, truncated) or 1 (* 32768, rounded)")
+    lengths = np.array([int(c.shape[0]) for c in clips], np.int64)
+    _check_lengths(lengths.tolist(), model.normalize_input)
+    offsets = (np.cumsum(lengths) - lengths).astype(np.int64)
+    device = next(model.parameters()).device
+    flat = torch.empty(int(lengths.sum()), dtype=torch.int16, device=device)
+    batches = plan_batches(lengths.tolist(), model.valid_length, max_batch, budget_samples, max_waste)
+    # one upload for the offsets of every batch (and one for the lengths of the long clips): a batch takes its slice
+    order = [i for batch in batches for i in batch.indices]
+    offs_dev = torch.from_numpy(offsets[order]).to(device)
+    lens_dev = torch.from_numpy(lengths[order].astype(np.int32)).to(device)
+    at = 0
+    for batch in batches:
+        B = len(batch.indices)
+        offs, at = offs_dev[at:at + B], at + B
+        if batch.long:
+            i = batch.indices[0]
+            c = clips[i]
+            c = (c.to(torch.float32) * PCM_SCALE) if c.dtype == torch.int16 else c
+            y = model.denoise_long(c.to(device).view(1, -1))
+            pcm16_from_f32_ragged(y[0, :, :int(lengths[i])], lens_dev[at - 1:at], flat, offs, mode)
+            continue
+        rows, Lmax = stack_clips([clips[i] for i in batch.indices], device)
+        forward_ragged(model, rows[:, :Lmax], [int(lengths[i]) for i in batch.indices], pcm16=(flat, offs, mode))
+    return flat, offsets, lengths
+
+
+def _resample_group(clips, rate_in, rate_out, device, max_batch, pcm16=None):
     """1-D clips of one rate -> their conversions to ``rate_out`` (f32 device tensors), ``max_batch`` clips a launch.
-    int16 clips stay int16 up to the kernel."""
+    int16 clips stay int16 up to the kernel.  pcm16 = (flat int16 device buffer, device i64[len(clips)] sample offsets,
+    mode): every launch's rows are quantised into ``flat`` at their clips' offsets instead (``pcm16_from_f32_ragged``)
+    and nothing is returned; the lengths table is uploaded once per launch and stays on the device."""
     from ..util.resample import resample_ragged
     out = []
     for k in range(0, len(clips), max_batch):
         part = clips[k:k + max_batch]
         rows, Lmax = stack_clips(part, device)
+        if pcm16 is not None:
+            flat, offsets, mode = pcm16
+            lens = torch.tensor([int(c.shape[0]) for c in part], dtype=torch.int32).to(device)
+            y, n = resample_ragged(rows[:, :Lmax], lens, rate_in, rate_out)
+            pcm16_from_f32_ragged(y, n, flat, offsets[k:k + len(part)], mode)
+            continue
         y, n = resample_ragged(rows[:, :Lmax], [int(c.shape[0]) for c in part], rate_in, rate_out)
         out += [y[b, :n[b]] for b in range(len(part))]
     return out

@@ -22,6 +22,7 @@ The constant tables are built here on the host:
   * the 15 one-third-octave bands of STOI from 150 Hz over a 512-point FFT at 10 kHz, and the 16 k -> 10 k polyphase
     filter (Kaiser-windowed sinc, 60 dB rejection) of STOI's Octave-compatible resampler.
 """
+import copy
 import ctypes
 import math
 
@@ -163,7 +164,48 @@ class Batch:
         self.n_clips = len(cs)
         self._cs, self._ps = cs, ps
 
+    @classmethod
+    def from_flat(cls, clean_flat, processed_flat, lengths, rate, offsets=None, min_len=WIN):
+        """A batch over audio that is already on the device: two flat int16 tensors sharing ONE offsets / lengths table
+        (clip i at [offsets[i], offsets[i] + lengths[i]) of both; ``offsets`` None: packed back to back).  Offsets may
+        leave gaps (cropped clips stay where they are).  The checks of the constructor apply -- an empty batch, a clip
+        under ``min_len`` samples, more than 65535 clips -- and nothing is copied."""
+        lengths = np.ascontiguousarray(np.asarray(lengths, np.int64).reshape(-1))
+        if lengths.size == 0:
+            raise ValueError("speech metrics: empty batch")
+        if lengths.size > 65535:
+            raise ValueError("speech metrics: at most 65535 clips per batch")
+        for i, n in enumerate(lengths.tolist()):
+            if n < min_len:
+                raise ValueError("speech metrics: clip %d has %d samples, fewer than one %d-sample window" % (i, n, min_len))
+        offsets = np.concatenate([[0], np.cumsum(lengths)[:-1]]).astype(np.int64) if offsets is None else \
+            np.ascontiguousarray(np.asarray(offsets, np.int64).reshape(-1))
+        if offsets.size != lengths.size:
+            raise ValueError("speech metrics: %d offsets for %d lengths" % (offsets.size, lengths.size))
+        for name, t in (("clean", clean_flat), ("processed", processed_flat)):
+            if t.dtype != torch.int16 or t.dim() != 1 or not t.is_contiguous():
+                raise ValueError("speech metrics: the flat %s buffer must be a contiguous 1-D int16 tensor" % name)
+            if not t.is_cuda:
+                raise RuntimeError("speech metrics run only on a ROCm GPU; there is no CPU fallback")
+        if clean_flat.device != processed_flat.device or clean_flat.numel() != processed_flat.numel():
+            raise ValueError("speech metrics: the flat buffers must have one device and one size")
+        if int(offsets.min()) < 0 or int((offsets + lengths).max()) > clean_flat.numel():
+            raise ValueError("speech metrics: a clip reaches outside the flat buffers")
+        b = cls.__new__(cls)
+        b.rate, b.lengths, b.offsets, b.n_clips = rate, lengths, offsets, int(lengths.size)
+        b.device, b.clean, b.processed = clean_flat.device, clean_flat, processed_flat
+        b._cs = b._ps = None
+        return b
+
+    def at_rate(self, rate):
+        """The same buffers and tables declared at another rate (no copy, no upload)."""
+        b = copy.copy(self)
+        b.rate = rate
+        return b
+
     def upload(self):
+        if self._cs is None:                     # from_flat: already resident
+            return self
         if not torch.cuda.is_available():
             raise RuntimeError("speech metrics run only on a ROCm GPU; there is no CPU fallback")
         dev = torch.device("cuda", torch.cuda.current_device())
@@ -307,7 +349,7 @@ def frame_metrics(clean, processed, rate=FRAME_RATE, extended=False):
     return res
 
 
-def speech_metrics(clean, processed, rate=FRAME_RATE, metrics=METRICS):
+def speech_metrics(clean, processed=None, rate=FRAME_RATE, metrics=METRICS):
     """Per-clip metrics of a ragged batch: a dict name -> f64 tensor of one value per clip, for each name in ``metrics``
     (``wss_dist``, ``llr_mean``, ``segSNR``: eval_waveform's recipe at 16 kHz; ``stoi`` at 16 or 10 kHz), in the order
     asked.  Names of ``EXT_METRICS`` are accepted too: ``cep_dist`` (mean of the lowest 95 % of the frame values, NaN
@@ -316,7 +358,11 @@ def speech_metrics(clean, processed, rate=FRAME_RATE, metrics=METRICS):
 
     ``clean`` / ``processed``: lists of 1-D arrays or tensors of int16 values, pairwise of equal length, each at least
     480 samples.  Raises ValueError before any launch for an empty batch, unequal lengths, a short clip or a rate the
-    requested metrics do not support."""
+    requested metrics do not support.
+
+    ``clean`` may be a ready ``Batch`` (``Batch.from_flat``: audio already on the device) with ``processed`` None: it is
+    scored at ``rate`` as it stands, with no copy and no upload; a caller that needs several rate classes passes the same
+    batch again with the other rate."""
     metrics = tuple(metrics)
     for m in metrics:
         if m not in METRICS + EXT_METRICS:
@@ -330,7 +376,12 @@ def speech_metrics(clean, processed, rate=FRAME_RATE, metrics=METRICS):
         _check_rate(rate, STOI_RATES)
     elif not (isinstance(rate, (int, np.integer)) and rate > 0):      # si_sdr, snr: the rate is not used
         raise ValueError("speech metrics: rate %r Hz is not supported (any positive rate)" % (rate,))
-    b = Batch(clean, processed, rate).upload()
+    if isinstance(clean, Batch):
+        if processed is not None:
+            raise ValueError("speech metrics: a ready Batch holds both signals; processed must be None")
+        b = clean.at_rate(rate).upload()
+    else:
+        b = Batch(clean, processed, rate).upload()
     res = {}
     if ext_names:
         vals, _, ws = _frames_ext(b)

@@ -149,6 +149,54 @@ def eval_waveforms(cleans, targets, rate, extra=()):
     return out
 
 
+def eval_batch(batch, rate, extra=()):
+    """``eval_waveforms`` on one resident ``metrics.Batch`` (``Batch.from_flat``: both signals already on the device as
+    flat int16 buffers): the same list of result dicts, from the same kernels -- the frame metrics on the batch at
+    16 kHz, STOI and the rate metrics on the same buffers at ``rate``, with no copy and no second upload.  Only the
+    per-clip scalars come back to the host; the int16 clips are downloaded for PESQ only where ``pesq`` imports."""
+    extra = tuple(extra)
+    for k in extra:
+        if k not in M.EXT_METRICS:
+            raise ValueError("eval_batch: unknown extra metric %r (have %s)" % (k, ", ".join(M.EXT_METRICS)))
+    ext_frame = tuple(k for k in extra if k in ("cep_dist", "fwsegSNR"))
+    ext_rate = tuple(k for k in extra if k not in ext_frame)
+    m = M.speech_metrics(batch, None, M.FRAME_RATE, metrics=("wss_dist", "llr_mean", "segSNR") + ext_frame)
+    at_rate = M.speech_metrics(batch, None, rate, metrics=("stoi",) + ext_rate)
+    st = at_rate.pop("stoi")
+    m.update(at_rate)
+    m = {k: v.cpu().numpy() for k, v in m.items()}
+    st = st.cpu().numpy()
+    pesq = _pesq_fn()
+    if pesq is not None:
+        clean_host, target_host = batch.clean.cpu().numpy(), batch.processed.cpu().numpy()
+    out = []
+    for i in range(batch.n_clips):
+        length = int(batch.lengths[i])
+        wss_dist, llr_mean, seg = float(m["wss_dist"][i]), float(m["llr_mean"][i]), float(m["segSNR"][i])
+        if pesq is not None:
+            o = int(batch.offsets[i])
+            clean, target = clean_host[o:o + length], target_host[o:o + length]
+            pesq_wb, pesq_nb = pesq(16000, clean, target, "wb"), pesq(16000, clean, target, "nb")
+        else:
+            pesq_wb = pesq_nb = float("nan")
+        csig, cbak, covl = composites(pesq_wb, llr_mean, wss_dist, seg)
+        result = defaultdict(int)
+        result["pesq_wb"] += pesq_wb * length
+        result["pesq_nb"] += pesq_nb * length
+        result["stoi"] += float(st[i]) * length
+        result["CSIG"] += csig * length
+        result["CBAK"] += cbak * length
+        result["COVL"] += covl * length
+        result["wss_dist"] += wss_dist * length
+        result["segSNR"] += seg * length
+        result["llr_mean"] += llr_mean * length
+        result["count"] += 1 * length
+        for k in extra:
+            result[k] += float(m[k][i]) * length
+        out.append(result)
+    return out
+
+
 def eval_waveform(clean, target_wav, rate):
     """Length-weighted metrics of one clip (python_eval.py:81): pesq_wb, pesq_nb, stoi, CSIG, CBAK, COVL, wss_dist,
     segSNR, llr_mean and count.  The frame metrics run at 16 kHz, STOI at ``rate``, as in the reference."""

@@ -903,6 +903,27 @@ int cum_rows_zero_tail(int32_t dtype, void *rows, int32_t batch, int64_t T, int3
 int cum_unframe_rows_ragged(int32_t dtype, const void *rows, int32_t batch, int64_t lmax, int64_t T, const int32_t *len,
                             const float *scale, float *y, void *stream);
 
+/* int16 PCM of a ragged batch in ONE flat buffer, the layout the metric kernels read (csrc/metrics.hip): clip b's
+ * samples stand at out_i16[out_offset[b] .. out_offset[b] + len[b]), out_offset a device i64[batch] table of sample
+ * offsets.  Clips are packed back to back, so a clip may start at any 2-byte position: stores are 16 bytes where the
+ * destination is aligned, 2 bytes in front of the first boundary and behind the last.  Nothing outside a clip's range
+ * is written (a negative offset skips the clip; ranges must not overlap).  No atomics: the same bits on every run.
+ * mode 0 <- `(y * 32767).clamp(-32768, 32767).to(torch.int16)` (util/denoise_eval.py, the denoised signal):
+ *   w = v * 32767.0f (f32, rounded once), clamped to [-32768, 32767], converted truncating toward zero.
+ * mode 1 <- `(y * 32768).round().clamp(-32768, 32767)` (the converted clean signal): w = v * 32768.0f, rounded half to
+ *   even, clamped.
+ * NaN gives 0 in both modes; +inf gives 32767, -inf -32768.
+ * cum_unframe_rows_ragged_pcm16: cum_unframe_rows_ragged with that store: v = (float)rows[1 + b (T + 2) + t][0] *
+ *   scale[b] (one f32 product, as the f32 entry forms it; scale may be NULL) for t < len[b] clamped into [0, lmax].
+ * cum_pcm16_from_f32_ragged: v = x[b stride + t] for t < len[b] clamped into [0, lmax] (rows of cum_resample_ragged).
+ * batch < 1, lmax < 1, T < lmax / stride < lmax, a mode other than 0 or 1, a null pointer or a misaligned buffer (rows
+ * 16 bytes, out_offset 8, len / scale / x 4, out_i16 2): CUM_EINVAL before any launch. */
+int cum_unframe_rows_ragged_pcm16(int32_t dtype, const void *rows, int32_t batch, int64_t lmax, int64_t T,
+                                  const int32_t *len, const float *scale, int32_t mode, int16_t *out_i16,
+                                  const int64_t *out_offset, void *stream);
+int cum_pcm16_from_f32_ragged(const float *x, int32_t batch, int64_t lmax, int64_t stride, const int32_t *len,
+                              int32_t mode, int16_t *out_i16, const int64_t *out_offset, void *stream);
+
 /* cum_dech_fwd_ragged / cum_dec7_fwd_ragged: cum_dech_fwd / cum_dec7_fwd (the decoder layers of
  * src/network/CleanUMamba.py:121-130 at widths 128 and 64, which never store their GLU output) for a ragged batch: the
  * GLU output of clip c = row / pitch is kept for its first min(valid_rows[c], valid) rows only; M must be batch x pitch.
